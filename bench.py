@@ -1,12 +1,16 @@
 #!/usr/bin/env python
 """Headline benchmark: ``ae_combined`` training slices/s on synthetic ACDC-shaped batches (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--dump-outputs DIR] [--full]
 
 A step = one ae_combined training step (4 network passes, backward, Adam) over one batch of 12 synthetic triplets
 (36 slices of 160x160) that is already resident in HBM.  N > 1: launched by torch.distributed.run, one rank per GPU
 over RCCL; the 12 triplets are sharded over the ranks (fixed global batch -> strong scaling).
 Rank 0 prints ONE JSON line (see DESIGN.md section "Measurement").
+
+A plain run sets up, runs W warm-up and K timed steps and prints the headline line.  ``--full`` adds what takes runs of
+its own: the roofline, the CPU baseline and (N = 1, c2) the secondary configurations.  ``--dump-outputs DIR`` writes what
+the last timed step handed its caller (logged losses, model state after the update) as DIR/<name>.npy.
 """
 import argparse
 import hashlib
@@ -192,6 +196,34 @@ def timed_steps(trainer, pool, steps, warmup, dp=None):
         dp.barrier()
     dt = time.perf_counter() - t0
     return dp.max_over_ranks(dt) if dp is not None else dt
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(trainer, outdir):
+    """``--dump-outputs DIR``: what the timed path handed its caller after the LAST timed step, one ``DIR/<name>.npy`` each -- every
+    scalar the step logged (``<loss key>.npy``, float64, shape (1,)) and the model's state after the step's Adam update
+    (``state.<state_dict key>.npy``: floating tensors as float32, integer counters as float64).  Above 64 MiB in all, an array larger
+    than its share of the budget is replaced by a fixed sample of its flattened values (``<name>.sample.npy``, RandomState(0) indices)."""
+    import numpy as np
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    arrays = {}
+    for k in sorted(trainer.losses):
+        if len(trainer.losses[k]):
+            arrays[k] = np.asarray([trainer.losses[k][-1]], dtype=np.float64)
+    for k, v in trainer.model.state_dict().items():
+        a = v.detach().cpu().numpy()
+        arrays["state." + k] = a.astype(np.float64 if a.dtype == np.float64 or not np.issubdtype(a.dtype, np.floating) else np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        n = max(1, DUMP_LIMIT_BYTES * a.nbytes // max(total, 1) // a.itemsize)
+        if total > DUMP_LIMIT_BYTES and a.size > n:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, n, replace=False))
+            a, name = a.reshape(-1)[idx], name + ".sample"
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def make_trainer(config, device, B, H, scales3=False, graph=True, npool=4, dp=None):
@@ -598,6 +630,10 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", choices=["c2", "c3", "c4", "c5"], default="c2")
+    ap.add_argument("--full", action="store_true", help="beyond the headline figure: the roofline, the CPU baseline and (N=1, c2) the "
+                    "secondary measurements; --no-roofline / --no-cpu-baseline / --no-secondary leave single parts out")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (logged losses, model "
+                    "state after the update) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--triplets", type=int, default=0, help="global batch in triplets (default: the BASELINE workload; other values are for experiments only)")
@@ -610,6 +646,10 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary single-GPU measurements (c3, c3 with scales 3, c4, c5, "
                     "small shards, inference)")
     opt = ap.parse_args()
+    if opt.steps < 1 or opt.warmup < 0:
+        raise SystemExit("bench: --steps must be >= 1 and --warmup >= 0")
+    if not opt.full:
+        opt.no_roofline = opt.no_cpu_baseline = opt.no_secondary = True
 
     from superresolution_aniso_mri_amd import engine
     from superresolution_aniso_mri_amd.parallel import DataParallelContext
@@ -640,6 +680,8 @@ def main():
             if not getattr(trainer, "_graphs", None):
                 raise SystemExit("bench: the step graph was requested but never captured")
         loss = trainer.losses["loss_ae"][-1]
+        if opt.dump_outputs and dp.rank == 0:
+            dump_outputs(trainer, opt.dump_outputs)
         roofline = None
         if not opt.no_roofline and not dp.active:
             del trainer, pool
