@@ -318,6 +318,18 @@ size_t aesr_ssim_workspace_doubles(int Z, int H, int W);
 int aesr_ssim_mse(const float* a, const float* b, double* workspace, double* ssim, double* mse, int Z, int H, int W, int win,
                   double data_range, double k1, double k2, void* stream);
 
+/* ---- long-axis (through-plane) views for the same metrics (evaluate/metrics.py:65-243 with eval_axis = 1 or 2: np.swapaxes(v, 0, eval_axis)
+ * of both volumes, slices whose reference is black are not scored) -- csrc/long_axis.hip ----------------------------------------------
+ * ref, rec: [Z][H][W] fp32.  ref_view, rec_view: Z*H*W floats each, the contiguous np.swapaxes(., 0, axis): [H][Z][W] (axis 1) or
+ * [W][H][Z] (axis 2), bitwise copies of the elements.  black: H (axis 1) or W (axis 2) bytes; black[s] = 1 iff every element of
+ * ref_view[s] is exactly 0 (+0.0 or -0.0), else 0.  For the non-negative images the evaluation works on (normalised to [0, 1]) this is
+ * the reference's `np.sum(slice) == 0`; a signed slice whose sum cancels to 0 is NOT black here (nor is one that holds a NaN).
+ * One pass: every input element is read once, every view element written once, the flags come from the same words (axis 1: one kernel;
+ * axis 2: a memset node of W bytes on `stream` presets black[], then one kernel).  No workspace; the outputs must not overlap the inputs.  axis outside {1, 2}, a null pointer, a non-positive size or Z*H*W >= 2^30: AESR_ERR_ARG, nothing
+ * is launched. */
+int aesr_long_axis_views(const float* ref, const float* rec, float* ref_view, float* rec_view, unsigned char* black, int Z, int H, int W,
+                         int axis, void* stream);
+
 /* ---- BatchNorm2d (train) [+ AvgPool2d(2)] as ONE launch per direction, for SMALL batches (csrc/bn_fused.hip) -----------------------
  * The shard of a data-parallel rank (6 images) makes a BatchNorm call three ~5 us launches each way; a layer of that size fits the LDS
  * of the chip, so one launch of 256 workgroups keeps it there between the statistics and the normalisation, with one grid-wide barrier

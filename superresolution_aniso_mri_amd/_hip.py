@@ -136,6 +136,7 @@ SIGNATURES = {
     "aesr_triplet_assemble": (c_int, [P, ctypes.POINTER(TripletDesc), c_int, c_int, P, P, P]),
     "aesr_ssim_workspace_doubles": (c_size_t, [c_int, c_int, c_int]),
     "aesr_ssim_mse": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_double, c_double, c_double, P]),
+    "aesr_long_axis_views": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "aesr_vif_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "aesr_vif_mscale": (c_int, [P, P, P, P, c_int, c_int, c_int, DP, IP, c_double, P]),
     "aesr_adam_state_init": (None, [FP, c_double, c_double, c_double]),

@@ -1281,6 +1281,16 @@ int aesr_ssim_mse(const float* a, const float* b, double* workspace, double* ssi
     return aesr_launch_ssim_mse(a, b, workspace, ssim, mse, Z, H, W, win, data_range, k1, k2, (hipStream_t)stream);
 }
 
+int aesr_long_axis_views(const float* ref, const float* rec, float* ref_view, float* rec_view, unsigned char* black, int Z, int H, int W,
+                         int axis, void* stream) {
+    AESR_CHECK_ARG(ref && rec && ref_view && rec_view && black, "aesr_long_axis_views: null pointer");
+    AESR_CHECK_ARG(axis == 1 || axis == 2, "aesr_long_axis_views: axis=%d must be 1 or 2 (axis 0 is the volume itself)", axis);
+    AESR_CHECK_ARG(Z > 0 && H > 0 && W > 0, "aesr_long_axis_views: empty shape %d x %d x %d", Z, H, W);
+    AESR_CHECK_ARG((size_t)Z * H < ((size_t)1 << 30) && (size_t)Z * H * W < ((size_t)1 << 30),
+                   "aesr_long_axis_views: %d x %d x %d has 2^30 elements or more", Z, H, W);
+    return aesr_launch_long_axis_views(ref, rec, ref_view, rec_view, black, Z, H, W, axis, (hipStream_t)stream);
+}
+
 // (the shapes aesr_vif_mscale takes; anything else has no workspace: the layout arithmetic is int -- sanitizer sweep, round 6)
 size_t aesr_vif_workspace_bytes(int Z, int H, int W) {
     return (Z > 0 && Z <= 65535 && H > 0 && W > 0 && (size_t)H * W < ((size_t)1 << 30)) ? aesr_vif_workspace_bytes_impl(Z, H, W) : 0;

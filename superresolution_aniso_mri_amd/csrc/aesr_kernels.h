@@ -226,6 +226,8 @@ int aesr_launch_vif_mscale(const float* ref, const float* dist, void* workspace,
                            const int* radii, double sigma_nsq, hipStream_t st);
 int aesr_launch_ssim_mse(const float* a, const float* b, double* partial, double* ssim, double* mse, int Z, int H, int W, int win,
                          double data_range, double k1, double k2, hipStream_t st);
+int aesr_launch_long_axis_views(const float* ref, const float* rec, float* ref_view, float* rec_view, unsigned char* black, int Z, int H,
+                                int W, int axis, hipStream_t st);
 #define TRIPLET_MAX 64
 struct TripletDesc { long long vol_off; int H, W, z_from, z_to, z_between, oy, ox, k; float gain, cutoff; };
 struct TripletTable { TripletDesc d[TRIPLET_MAX]; };

@@ -8,7 +8,11 @@ Per checkpoint and volume: pad / centre-crop to ``ps_evaluate`` (AdjustToPatchSi
 paired slice against the original: all slices, the synthesised ones (s_mask) and the reconstructed ones (r_mask) --
 SSIM and PSNR from ONE device pass per volume (``evaluate.metrics.slice_ssim_psnr``), VIF from another
 (``evaluate.metrics.slice_vif``: the reference's ``vifp_mscale`` on uint8 slices, evaluate/vifvec.py:7-63); LPIPS per slice is off, as in
-the reference's call (``compute_percept_loss = False``)."""
+the reference's call (``compute_percept_loss = False``).
+
+``eval_axis`` 1 or 2 scores the same volumes in their long-axis views (``evaluate.metrics`` with ``eval_axis``): SSIM / PSNR / VIF of the whole
+volume only -- the synthesised / reconstructed masks select short-axis slices, so the reference leaves those lists empty
+(create_HR_images.py:164-175) and its ``model_perf_synth_..._axis<k>.npz`` rows are the mean of nothing, NaN."""
 import glob
 import os
 import types
@@ -62,11 +66,19 @@ def generate_synth_slices_mask(orig_num_slices, downsample_steps):
     return ~s_mask, s_mask
 
 
-def compute_metrics(images_ref, new_images, downsample_steps, data_range=1.0, compute_percept_loss=False, percept_loss=None):
+def compute_metrics(images_ref, new_images, downsample_steps, data_range=1.0, compute_percept_loss=False, percept_loss=None, eval_axis=0):
     """{'ssim','psnr','vif' and their '_synth' / '_recon' forms [,'lpips']} of one volume (create_HR_images.py:121-178; LPIPS over all
     scored slices only, as there: the masked calls pass compute_percept_loss=False).  VIF: mean over the slices of the selection whose
-    score is finite (evaluate/metrics.py:100-106)."""
+    score is finite (evaluate/metrics.py:100-106).  ``eval_axis`` 1 / 2: 'ssim', 'psnr', 'vif' of the long-axis view, no '_synth' / '_recon'
+    keys, and 'lpips' still at axis 0 (the reference does not pass eval_axis to it)."""
     last = _common.determine_last_slice(images_ref.shape[0], downsample_steps) + 1
+    if eval_axis != 0:
+        ref, new = images_ref[:last], new_images[:last]
+        per = _metrics.long_axis_slice_scores(("ssim", "psnr", "vif"), ref, new, eval_axis, data_range=data_range)    # one view launch for the three
+        out = {k: _metrics._mean_or_nan(scores[keep]) for k, (scores, keep) in per.items()}
+        if compute_percept_loss:
+            out["lpips"] = _metrics.compute_lpips_for_batch(ref, new, criterion=percept_loss)
+        return out
     r_mask, s_mask = generate_synth_slices_mask(images_ref.shape[0], downsample_steps)
     ssim, psnr, _ = _metrics.slice_ssim_psnr(images_ref[:last], new_images[:last], data_range=data_range)
 
@@ -97,9 +109,8 @@ def _as_list(data_generator):
 def evaluate_interpolation_performance(trainer, myargs, data_generator, transform=None, downsample_steps=None, file_suffix=None,
                                        patient_id=None, eval_axis=0, compute_percept_loss=False, percept_loss=None):
     """evaluate/evaluate_interpolations.py:45-63 -> create_hr_images(generate_inbetween_slices=True, use_original_slice=False,
-    num_interpolations = downsample_steps - 1): result lists per volume."""
-    if eval_axis != 0:
-        raise NotImplementedError("long-axis (eval_axis != 0) evaluation is outside the ae_combined path")
+    num_interpolations = downsample_steps - 1): result lists per volume.  ``eval_axis`` 1 / 2: the '_synth' / '_recon' lists stay empty."""
+    _metrics._check_axis(eval_axis)
     alpha_range = np.linspace(0, 1, (downsample_steps - 1) + 2, endpoint=True)[1:-1]
     keys = ("ssim", "psnr", "vif", "ssim_synth", "psnr_synth", "vif_synth", "ssim_recon", "psnr_recon", "vif_recon")
     res = {k: [] for k in keys + ("lpips", "lpips_synth", "lpips_recon")}
@@ -115,23 +126,27 @@ def evaluate_interpolation_performance(trainer, myargs, data_generator, transfor
         out = _common.create_super_volume(trainer, images, alpha_range=alpha_range, use_original=False,
                                           downsample_steps=downsample_steps, generate_inbetween_slices=True)
         m = compute_metrics(images if ref is None else ref, out["upsampled_image"], downsample_steps,
-                            compute_percept_loss=compute_percept_loss, percept_loss=percept_loss)
+                            compute_percept_loss=compute_percept_loss, percept_loss=percept_loss, eval_axis=eval_axis)
         for k in keys:
-            res[k].append(m[k])
+            if k in m:
+                res[k].append(m[k])
         if compute_percept_loss:
             res["lpips"].append(m["lpips"])
     return res
 
 
 def store_top_scores(model_nbr, top_scores, ssim_results, psnr_results, vif_results):
-    top_scores[model_nbr] = np.array([np.mean(np.array(ssim_results)), np.mean(np.array(psnr_results)), np.mean(np.array(vif_results))])
+    def mean(v):                                    # np.mean of an empty list (the long-axis '_synth' rows): nan, without numpy's warning
+        return np.mean(np.array(v)) if len(v) else np.float64("nan")
+    top_scores[model_nbr] = np.array([mean(ssim_results), mean(psnr_results), mean(vif_results)])
     return top_scores
 
 
 def find_best_val_model(data_generator, exper_src_dir, epoch_range=None, ps_evaluate=None, eval_axis=0, downsample_steps=None,
                         patient_id=None, limit_4d=False, func_get_trainer=None):
     """Scores every ``<exper_src_dir>/models/<epoch>.models`` of ``epoch_range``; writes ``model_perf_<a>_to_<b>_axis<k>.npz``
-    (all slices) and ``model_perf_synth_...npz`` (synthesised slices only) as the reference does; returns {epoch: [ssim, psnr, vif]}."""
+    (all slices) and ``model_perf_synth_...npz`` (synthesised slices only; NaN rows for ``eval_axis`` 1 / 2, where the reference scores no slice subset) as the reference does; returns
+    {epoch: [ssim, psnr, vif]}."""
     if func_get_trainer is None:
         from ..kwatsch.get_trainer import get_trainer_dynamic as func_get_trainer
     exper_src_dir = os.path.expanduser(exper_src_dir)

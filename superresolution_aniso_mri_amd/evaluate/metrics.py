@@ -10,7 +10,16 @@ pass ``data_range=2.0`` to reproduce numbers produced with such an installation.
 ``compute_lpips_for_batch`` (:210-243) scores all kept slices with ONE batched LPIPS pass instead of a criterion call and a host
 sync per slice.  ``compute_vif_for_batch`` (:65-109 -> evaluate/vifvec.py:7-63 ``vifp_mscale``) scores all slices of a volume with
 one device pass (``aesr_vif_mscale``, csrc/vif.hip) in the reference's own arithmetic: uint8 images, uint8 Gaussian filter, products
-modulo 256 -- see oracle/vif_oracle.py.  Not covered: the HD metrics of the same file (outside the ae_combined path)."""
+modulo 256 -- see oracle/vif_oracle.py.
+
+Long-axis views (``eval_axis`` 1 or 2 of a 3-D input; a 2-D image ignores it): ``long_axis_views`` makes ``np.swapaxes(v, 0, eval_axis)``
+of both volumes and the per-slice "reference is black" flags in one device pass (``aesr_long_axis_views``, csrc/long_axis.hip); the
+same per-slice kernels then score the swapped volume in one pass and ``long_axis_slice_scores`` applies the reference's selection:
+normalisation before the swap; original-slice ids computed from the shape BEFORE the swap and used as indices of the swapped slices
+(the reference's quirk; ids beyond the swapped slice count never match); black slices skipped for SSIM / PSNR / VIF but not for LPIPS;
+SSIM window 5 when a slice side is below 8; non-finite PSNR / VIF dropped; ``nan`` when nothing is left.  "Black" is "every element is
+exactly 0", which equals the reference's ``np.sum(slice) == 0`` for the non-negative images this evaluation works on.
+Not covered: the HD metrics of the same file (outside the ae_combined path)."""
 import numpy as np
 import torch
 
@@ -118,11 +127,90 @@ def slice_vif(l_images, l_reconstructions, sigma_nsq=2.0, device="cuda"):
     return out
 
 
+def _is_single_image(t):
+    """True when the reference's squeeze rule (evaluate/metrics.py:48-62: squeeze only above 3 dimensions) leaves a 2-D image."""
+    shape = tuple(t.shape)
+    if len(shape) > 3:
+        shape = tuple(n for n in shape if n != 1)
+    return len(shape) == 2
+
+
+def _check_axis(eval_axis):
+    if eval_axis not in (0, 1, 2):
+        raise ValueError("eval_axis must be 0 (the acquired plane), 1 or 2 (long-axis views), got %r" % (eval_axis,))
+
+
+def _mean_or_nan(values):
+    return float(np.mean(values)) if values.size else float("nan")
+
+
+def long_axis_views(l_images, l_reconstructions, eval_axis, device="cuda"):
+    """(ref_view, rec_view, black): ``np.swapaxes(v, 0, eval_axis)`` of both volumes as contiguous device tensors ([H,Z,W] for axis 1,
+    [W,H,Z] for axis 2) and a numpy bool array with one entry per swapped slice, True where the reference slice is exactly 0 everywhere.
+    One device pass (``aesr_long_axis_views``); the flag array is the only thing copied to the host."""
+    if eval_axis not in (1, 2):
+        raise ValueError("long-axis views exist for eval_axis 1 and 2, got %r" % (eval_axis,))
+    a, b = _as_volume(l_images, device), _as_volume(l_reconstructions, device)
+    if a.shape != b.shape:
+        raise ValueError("shape mismatch %s vs %s" % (tuple(a.shape), tuple(b.shape)))
+    _hip.require_gpu_tensor(a, "images")
+    Z, H, W = a.shape
+    shape = (H, Z, W) if eval_axis == 1 else (W, H, Z)
+    ref_view, rec_view = torch.empty(shape, device=a.device, dtype=torch.float32), torch.empty(shape, device=a.device, dtype=torch.float32)
+    black = torch.empty(shape[0], device=a.device, dtype=torch.uint8)
+    check(lib.aesr_long_axis_views(ptr(a), ptr(b), ptr(ref_view), ptr(rec_view), ptr(black), Z, H, W, int(eval_axis), stream()),
+          "aesr_long_axis_views")
+    return ref_view, rec_view, black.cpu().numpy().astype(bool)
+
+
+def long_axis_slice_scores(metric, l_images, l_reconstructions, eval_axis, normalize=False, downsample_steps=None, conv_interpol=False,
+                           data_range=1.0, device="cuda"):
+    """(scores[S], keep[S]) of the S long-axis slices of a volume pair: ``metric`` "ssim", "psnr" or "vif" of every swapped slice from one
+    pass of the per-slice kernel, and the slices the reference's loop scores (evaluate/metrics.py:65-194 with eval_axis != 0; the rules
+    are listed in the module docstring).  ``compute_*_for_batch`` return the mean of ``scores[keep]``.  A tuple of metrics returns
+    {metric: (scores, keep)} from ONE view launch, one SSIM / MSE pass and one VIF pass."""
+    metrics = (metric,) if isinstance(metric, str) else tuple(metric)
+    for m in metrics:
+        if m not in ("ssim", "psnr", "vif"):
+            raise ValueError("metric must be 'ssim', 'psnr' or 'vif', got %r" % (m,))
+    a, b = _as_volume(l_images, device), _as_volume(l_reconstructions, device)
+    if normalize:
+        b = rescale_intensities(b, percs=(0, 100))
+    ref_view, rec_view, black = long_axis_views(a, b, eval_axis, device=device)
+    scored = ~black
+    if downsample_steps is not None:
+        ids = determine_original_sliceids(a, downsample_steps, conv_interpol)          # from Z, used on the swapped slices: the reference's quirk
+        scored[ids[ids < scored.shape[0]]] = False
+    side = min(ref_view.shape[1:])
+    out = {}
+    if "ssim" in metrics and side < 5:
+        if scored.any():                            # (with nothing to score the reference never reaches skimage: nan)
+            raise ValueError("SSIM needs slices of at least 5 x 5 pixels (win_size 5); the eval_axis=%d slices of a %s volume are %s"
+                             % (eval_axis, tuple(a.shape), tuple(ref_view.shape[1:])))
+        out["ssim"] = (np.full(scored.shape[0], np.nan), scored.copy())
+    if ("ssim" in metrics and "ssim" not in out) or "psnr" in metrics:
+        if side < 3:
+            raise ValueError("the per-slice kernel takes slices of at least 3 x 3 pixels; the eval_axis=%d slices of a %s volume are %s"
+                             % (eval_axis, tuple(a.shape), tuple(ref_view.shape[1:])))
+        # (PSNR of slices thinner than 5: the kernel's SSIM half runs with its smallest window and is not used)
+        ssim, psnr, _ = slice_ssim_psnr(ref_view, rec_view, data_range=data_range, win_size=None if side >= 5 else 3, device=device)
+        out.setdefault("ssim", (ssim, scored.copy()))
+        out["psnr"] = (psnr, scored & np.isfinite(psnr))
+    if "vif" in metrics:
+        vif = slice_vif(ref_view, rec_view, device=device)
+        out["vif"] = (vif, scored & np.isfinite(vif))
+    return out[metric] if isinstance(metric, str) else {m: out[m] for m in metrics}
+
+
 def compute_vif_for_batch(l_images, l_reconstructions, eval_axis=0, normalize=False, downsample_steps=None, conv_interpol=False,
                           device="cuda"):
     """Mean VIF over the slices of a volume whose score is finite (original slices skipped when ``downsample_steps`` is given); a single
     2-D image returns its score.  evaluate/metrics.py:65-109."""
     _check_axis(eval_axis)
+    if eval_axis != 0 and not _is_single_image(l_images):
+        scores, keep = long_axis_slice_scores("vif", l_images, l_reconstructions, eval_axis, normalize, downsample_steps, conv_interpol,
+                                              device=device)
+        return _mean_or_nan(scores[keep])
     single = (torch.as_tensor(l_images).squeeze().dim() == 2) if not isinstance(l_images, np.ndarray) else (np.squeeze(l_images).ndim == 2)
     a, b = _as_volume(l_images, device), _as_volume(l_reconstructions, device)
     if normalize:
@@ -136,15 +224,14 @@ def compute_vif_for_batch(l_images, l_reconstructions, eval_axis=0, normalize=Fa
     return float(np.mean(vif[keep])) if keep.any() else float("nan")
 
 
-def _check_axis(eval_axis):
-    if eval_axis != 0:
-        raise NotImplementedError("long-axis (eval_axis != 0) evaluation is outside the ae_combined path")
-
-
 def compute_ssim_for_batch(l_images, l_reconstructions, eval_axis=0, normalize=False, downsample_steps=None, conv_interpol=False,
                            data_range=1.0, device="cuda"):
     """Mean SSIM over the slices of a volume (original slices skipped when ``downsample_steps`` is given), evaluate/metrics.py:111-154."""
     _check_axis(eval_axis)
+    if eval_axis != 0 and not _is_single_image(l_images):
+        scores, keep = long_axis_slice_scores("ssim", l_images, l_reconstructions, eval_axis, normalize, downsample_steps, conv_interpol,
+                                              data_range=data_range, device=device)
+        return _mean_or_nan(scores[keep])
     a, b = _as_volume(l_images, device), _as_volume(l_reconstructions, device)
     if normalize:
         b = rescale_intensities(b, percs=(0, 100))
@@ -159,6 +246,10 @@ def compute_psnr_for_batch(l_images, l_reconstructions, eval_axis=0, normalize=F
                            data_range=1.0, device="cuda"):
     """Mean PSNR over the slices (nan / inf slices dropped as in the reference), evaluate/metrics.py:157-194."""
     _check_axis(eval_axis)
+    if eval_axis != 0 and not _is_single_image(l_images):
+        scores, keep = long_axis_slice_scores("psnr", l_images, l_reconstructions, eval_axis, normalize, downsample_steps, conv_interpol,
+                                              data_range=data_range, device=device)
+        return _mean_or_nan(scores[keep])
     a, b = _as_volume(l_images, device), _as_volume(l_reconstructions, device)
     if normalize:
         b = rescale_intensities(b, percs=(0, 100))
@@ -176,15 +267,28 @@ def compute_lpips_for_batch(l_images, l_reconstructions, eval_axis=0, normalize=
     """Mean LPIPS distance over the slices of a volume (original slices skipped when ``downsample_steps`` is given), reference
     evaluate/metrics.py:210-243.  ``criterion``: a ``PerceptualLoss`` (built with the reference's arguments when omitted)."""
     _check_axis(eval_axis)
-    if criterion is None:
-        from ..lpips.perceptual import PerceptualLoss
-        criterion = PerceptualLoss(model="net-lin", net="vgg", use_gpu=True, gpu_ids=[0], device=device)
     a, b = _as_volume(l_images, device), _as_volume(l_reconstructions, device)
     if normalize:
         b = rescale_intensities(b, percs=(0, 100))
-    keep = np.ones(a.shape[0], dtype=bool)
-    if downsample_steps is not None and a.shape[0] > 1:
-        keep[determine_original_sliceids(a, downsample_steps, conv_interpol)] = False
+    if eval_axis != 0 and not _is_single_image(l_images):
+        # evaluate/metrics.py:227-241: original-slice ids from the shape before the swap, every other swapped slice is scored, black or not
+        ids = determine_original_sliceids(a, downsample_steps, conv_interpol) if downsample_steps is not None else np.zeros(0, dtype=np.int64)
+        sides = (a.shape[0], a.shape[2]) if eval_axis == 1 else (a.shape[1], a.shape[0])
+        if min(sides) < 16:
+            raise ValueError("LPIPS needs slices of at least 16 x 16 pixels (the VGG stack pools four times); the eval_axis=%d slices of a "
+                             "%s volume are %s" % (eval_axis, tuple(a.shape), sides))
+        a, b, _ = long_axis_views(a, b, eval_axis, device=device)
+        keep = np.ones(a.shape[0], dtype=bool)
+        keep[ids[ids < keep.shape[0]]] = False
+        if not keep.any():
+            return float("nan")
+    else:
+        keep = np.ones(a.shape[0], dtype=bool)
+        if downsample_steps is not None and a.shape[0] > 1:
+            keep[determine_original_sliceids(a, downsample_steps, conv_interpol)] = False
+    if criterion is None:
+        from ..lpips.perceptual import PerceptualLoss
+        criterion = PerceptualLoss(model="net-lin", net="vgg", use_gpu=True, gpu_ids=[0], device=device)
     idx = torch.from_numpy(np.nonzero(keep)[0]).to(a.device)
     with torch.no_grad():
         d = criterion(a[idx][:, None].contiguous(), b[idx][:, None].contiguous(), normalize=True)
