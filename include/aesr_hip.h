@@ -13,7 +13,17 @@
  *     calling thread's last error is aesr_last_error_string();
  *   - activation codes: 0 none, 1 LeakyReLU(slope), 2 ReLU, 3 sigmoid;
  *   - BatchNorm "groups": a batch may consist of up to 4 consecutive sub-batches with independent batch
- *     statistics; group g covers images [nstart[g], nstart[g+1]) (nstart has G+1 entries).
+ *     statistics; group g covers images [nstart[g], nstart[g+1]) (nstart has G+1 entries);
+ *   - pointer alignment: a device pointer needs the alignment of its ELEMENT type only -- 4 bytes for float and 32-bit words, 8 bytes
+ *     for double and int64_t -- for every argument of every entry point: parameters, gradients and optimizer moments that are slices
+ *     of one flat buffer at any float offset (the shipped optimizer), two parts of one tensor (aesr_mse3_fwd / _bwd), activations,
+ *     images and workspaces alike.  The kernels' 16-byte vector and global-to-LDS accesses tolerate such addresses on gfx950; results
+ *     are bit-identical to those at 16-byte-aligned addresses.  (Byte arrays -- `black`, and the VIF workspace, which its own note asks
+ *     to be 8-byte aligned -- are covered at 4-byte boundaries, with the same results.)  No entry point refuses a pointer for its alignment.  tests/test_gpu_memguard.py holds every launch entry point to
+ *     this at offsets of 4, 8 and 12 bytes from a 16-byte boundary, and to writing nothing outside the buffers it is given: outputs at
+ *     exactly their shape, workspaces at exactly the size the matching *_workspace_* query or documented constant states.  Workspaces
+ *     and outputs may hold anything on entry (nothing is read before it is written) except the three buffers documented as zeroed
+ *     once by the caller: the aesr_mse3_fwd workspace, the Adam state (aesr_adam_state_init) and the aesr_bn_fused1_* barrier words.
  */
 #ifndef AESR_HIP_H
 #define AESR_HIP_H
