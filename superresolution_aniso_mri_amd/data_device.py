@@ -37,21 +37,39 @@ def rescale_intensities(vol, percs=(1, 99)):
     return ((vol.astype(np.float32) - lo) / (hi - lo)).clip(0, 1)
 
 
-def load_volume_dir(path):
+NEW_SPACING = (1.4, 1.4)      # CardiacImage.new_spacing[1:] of the reference (datasets/cardiac_image.py:49): the in-plane training spacing
+
+
+def _resample_to(arr, spacing_zyx, new_spacing, f):
+    """``CardiacImage(resample=True)`` (datasets/cardiac_image.py:80-82, 102-104): in-plane resampling of a [Z,H,W] / [T,Z,H,W] array to
+    ``new_spacing`` on the device (datasets/common.py; all slices in one launch), BEFORE the intensities are rescaled."""
+    from .datasets.common import apply_2d_zoom_3d, apply_2d_zoom_4d
+    if spacing_zyx is None:
+        raise ValueError("%s: resample=True needs the volume's spacing, and a .npy file carries none (use .nii / .mha)" % f)
+    fn = apply_2d_zoom_3d if arr.ndim == 3 else apply_2d_zoom_4d
+    return fn(np.asarray(arr, dtype=np.float32), spacing_zyx, NEW_SPACING if new_spacing is None else new_spacing)
+
+
+def load_volume_dir(path, resample=False, new_spacing=None):
     """All volumes of a directory (.npy, .nii, .nii.gz, .mha, .mhd; 3-D [Z,H,W] or 4-D [T,Z,H,W] -> one volume per frame),
-    each rescaled to [0,1] by its 1st / 99th percentile when it is not already in that range."""
+    each rescaled to [0,1] by its 1st / 99th percentile when it is not already in that range.  ``resample``: every volume is first
+    resampled in-plane from its header's spacing to ``new_spacing`` (y, x; default 1.4 x 1.4 mm), as the reference's readers do."""
     import os
     from . import volume_io
     vols = []
     for name in sorted(os.listdir(path)):
         f = os.path.join(path, name)
         low = name.lower()
+        spacing = None
         if low.endswith(".npy"):
             arr = np.load(f)
         elif low.endswith((".nii", ".nii.gz", ".mha", ".mhd")):
-            arr = volume_io.read_volume(f).array
+            v = volume_io.read_volume(f)
+            arr, spacing = v.array, tuple(v.spacing[:3][::-1])
         else:
             continue
+        if resample:
+            arr = _resample_to(arr, spacing, new_spacing, f)
         frames = [arr] if arr.ndim == 3 else list(arr)
         for v in frames:
             v = np.asarray(v, dtype=np.float32)
@@ -63,10 +81,15 @@ def load_volume_dir(path):
     return vols
 
 
-def load_image_dict(path, max_patients=2):
+load_volumes = load_volume_dir
+
+
+def load_image_dict(path, max_patients=2, resample=False, new_spacing=None):
     """The in-memory validation images ``validate(image_dict=...)`` previews (train_cardiac_aesr.py:49-53 of the reference: two 4-D
     patients): {p_id: {'image': [t,z,y,x] float32 in [0,1], 'patient_id': 'patientNNN', 'spacing': (z,y,x)}} from the first
-    ``max_patients`` volumes of a directory (a 3-D volume counts as one frame).  p_id: the digits in the file name, else its rank."""
+    ``max_patients`` volumes of a directory (a 3-D volume counts as one frame).  p_id: the digits in the file name, else its rank.
+    ``resample``: resample in-plane to ``new_spacing`` (default 1.4 x 1.4 mm) before the intensities are rescaled; 'spacing' then
+    reports [z, new_y, new_x] and 'original_spacing' keeps the file's own, as the reference's ``preprocessed4d`` does."""
     import os
     import re
     from . import volume_io
@@ -80,6 +103,11 @@ def load_image_dict(path, max_patients=2):
             arr, spacing = v.array, tuple(v.spacing[:3][::-1])
         else:
             continue
+        original_spacing = spacing
+        if resample:
+            arr = _resample_to(arr, None if low.endswith(".npy") else spacing, new_spacing, f)
+            ns = NEW_SPACING if new_spacing is None else tuple(new_spacing)[-2:]
+            spacing = (spacing[0], float(ns[0]), float(ns[1]))
         arr = np.asarray(arr, dtype=np.float32)
         arr = arr[None] if arr.ndim == 3 else arr
         if arr.ndim != 4:
@@ -89,6 +117,8 @@ def load_image_dict(path, max_patients=2):
         digits = re.findall(r"\d+", name)
         p_id = int(digits[0]) if digits and int(digits[0]) not in out else 1000 + rank
         out[p_id] = {"image": arr, "patient_id": "patient{:03d}".format(p_id), "spacing": np.asarray(spacing, dtype=np.float64)}
+        if resample:
+            out[p_id]["original_spacing"] = np.asarray(original_spacing, dtype=np.float64)
         if len(out) >= int(max_patients):
             break
     if not out:

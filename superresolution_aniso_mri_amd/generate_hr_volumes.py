@@ -8,7 +8,13 @@ output for a latent mix is the mix of its outputs), all (z-1)*n mixes are formed
 of the decoder runs on them as ONE batch, the interleave and clamp happen on the device and there is a single device-to-host copy
 at the end.
 Conventions kept: ``alpha*enc(later slice) + (1-alpha)*enc(earlier slice)``, alphas = linspace(0,1,n+2)[1:-1],
-output order [orig_0, interp_0(a_1..a_n), orig_1, ...], clamp to [0,1], new z-spacing = old/(n+1)."""
+output order [orig_0, interp_0(a_1..a_n), orig_1, ...], clamp to [0,1], new z-spacing = old/(n+1).
+
+``--resample`` (the reference's ``CardiacImage(resample=True)`` on the way in, datasets/cardiac_image.py:80-88, and
+``save_3d_volume(..., resample=True)`` on the way out, evaluate/create_HR_images.py:83-87): the volume is resampled in-plane to the
+training spacing (``--new_spacing``, default 1.4 x 1.4 mm) BEFORE the percentile normalisation, synthesised, and resampled back to the
+file's own in-plane spacing before it is written -- both resamplings on the device (datasets/common.py, csrc/inplane.hip), so the
+volume crosses PCIe once each way.  Without the flag nothing changes."""
 import argparse
 import os
 from pathlib import Path
@@ -123,8 +129,62 @@ def upsample_volume(trainer, vol_np, num_interpolations):
     return np.stack([upsample_volume(trainer, v, num_interpolations) for v in vol_np])
 
 
+def normalize_on_device(x, perc=(1, 99)):
+    """``array_to_torch``'s intensity rule on a device tensor: values outside [0, 1] -> the 1st..99th percentile window mapped to [0, 1]
+    and clipped (percentiles with numpy's linear interpolation between the two nearest sorted values)."""
+    if not (float(x.max()) > 1 or float(x.min()) < 0):
+        return x
+    v = x.flatten().sort().values
+    n = v.numel()
+
+    def q(p):
+        pos = p / 100.0 * (n - 1)
+        i = int(np.floor(pos))
+        return v[i] + (v[min(i + 1, n - 1)] - v[i]) * float(pos - i)
+    lo, hi = q(perc[0]), q(perc[1])
+    return ((x - lo) / (hi - lo)).clamp_(0, 1)
+
+
+def upsample_volume_resampled(trainer, vol_np, num_interpolations, spacing, new_spacing=(1.4, 1.4), clamp_edges=False):
+    """``upsample_volume`` for a volume whose in-plane ``spacing`` (y, x) is not the training spacing: one upload, resample to
+    ``new_spacing`` (one launch for all frames and slices), per frame normalise and synthesise (zero-padded to the network's stride where
+    the resampled size needs it), resample back to ``spacing`` (one launch), one download.  [z,y,x] or [t,z,y,x] numpy -> numpy with the same leading layout; the in-plane shape is what the round trip of
+    ``int(round(n * zoom))`` gives (the input's own for the usual sizes), as in the reference."""
+    from .datasets.common import apply_2d_zoom_3d, apply_2d_zoom_4d
+    alpha_range = np.linspace(0, 1, num_interpolations + 2, endpoint=True)[1:-1]
+    zoom = apply_2d_zoom_3d if vol_np.ndim == 3 else apply_2d_zoom_4d
+    vol = torch.from_numpy(np.ascontiguousarray(vol_np, dtype=np.float32)).to(trainer.args["device"])
+    vol = zoom(vol, spacing, new_spacing, clamp_edges=clamp_edges)
+    # the resampled size is whatever the spacing gives (216 x 256 at 1.5625 mm -> 241 x 286): the network halves the image width /
+    # latent_width times over, so each frame is zero-padded at the bottom / right to the next multiple of that for the synthesis (after
+    # the normalisation, so the percentiles are the image's own) and cropped again before it is resampled back
+    m = max(1, int(trainer.args["width"]) // int(trainer.args["latent_width"]))
+    H, W = vol.shape[-2:]
+    pad = ((-W) % m, (-H) % m)
+    frames = [vol] if vol.dim() == 3 else list(vol)
+    hr = []
+    for f in frames:
+        f = normalize_on_device(f)
+        if pad != (0, 0):
+            f = torch.nn.functional.pad(f, (0, pad[0], 0, pad[1]))
+        up = create_super_volume(trainer, f.unsqueeze(1), alpha_range, use_original=True, to_cpu=False)["upsampled_image"]
+        hr.append(up[:, :H, :W].contiguous() if pad != (0, 0) else up)
+    hr = hr[0] if vol.dim() == 3 else torch.stack(hr)
+    out = zoom(hr, new_spacing, spacing, clamp_edges=clamp_edges).cpu().numpy()
+    _hip.check_device_watchdogs("upsample_volume_resampled")
+    return out
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="Generate through-plane super-resolved volumes")
+    p.add_argument("--resample", action="store_true",
+                   help="resample in-plane to --new_spacing before the synthesis and back to the file's own spacing before writing")
+    p.add_argument("--new_spacing", type=float, nargs=2, default=[1.4, 1.4], metavar=("Y", "X"),
+                   help="in-plane spacing the model was trained at (mm)")
+    p.add_argument("--spacing", type=float, nargs=2, default=None, metavar=("Y", "X"),
+                   help="in-plane spacing of .npy volumes (they carry none); required for them with --resample")
+    p.add_argument("--clamp_edges", action="store_true",
+                   help="with --resample: repeat the edge where scipy (and the reference) leave an all-zero last row / column")
     p.add_argument("--exper_dir", type=str, default=None)
     p.add_argument("--model_nbr", type=int, default=None)
     p.add_argument("--num_interpolations", type=int, default=6)
@@ -137,26 +197,34 @@ def main(argv=None):
     out_dir.mkdir(parents=True, exist_ok=True)
     images = load_images(Path(args.data_input_dir))
     print("INFO - Found {} files to process in {}".format(len(images), args.data_input_dir))
+    if args.resample and args.spacing is None and any(isinstance(img, np.ndarray) for _, img in images):
+        p.error("--resample: .npy volumes carry no spacing; give their in-plane spacing with --spacing Y X")
     trainer, _ = get_trainer_dynamic(src_path=args.exper_dir, model_nbr=args.model_nbr, model_nbr_sr=None, eval_mode=True)
     sitk = _sitk()
     results = []
     from . import volume_io
+
+    def upsample(arr, spacing_yx):
+        if not args.resample:
+            return upsample_volume(trainer, arr, args.num_interpolations)
+        return upsample_volume_resampled(trainer, arr, args.num_interpolations, spacing_yx, args.new_spacing, clamp_edges=args.clamp_edges)
+
     for fname, img in images:
         if isinstance(img, volume_io.Volume):
-            hr = upsample_volume(trainer, img.array, args.num_interpolations)
+            hr = upsample(img.array, (img.spacing[1], img.spacing[0]))
             spacing = list(img.spacing)
             spacing[2] = spacing[2] / (args.num_interpolations + 1)
             results.append((out_dir / fname.name, hr))
             if args.save:
                 volume_io.write_volume(out_dir / fname.name, img, hr.astype(np.float32), spacing)
         elif isinstance(img, np.ndarray):
-            hr = upsample_volume(trainer, img, args.num_interpolations)
+            hr = upsample(img, args.spacing)
             results.append((out_dir / fname.name, hr))
             if args.save:
                 np.save(str(out_dir / fname.name), hr)
         else:
             arr = sitk.GetArrayFromImage(img)
-            hr = upsample_volume(trainer, arr, args.num_interpolations)
+            hr = upsample(arr, (img.GetSpacing()[1], img.GetSpacing()[0]))
             spacing = list(img.GetSpacing())
             zi = 2 if arr.ndim == 3 else 2
             spacing[zi] = spacing[zi] / (args.num_interpolations + 1)

@@ -55,6 +55,11 @@ def build_parser():
                                                   "directory: device-resident cache + on-device triplet assembly / augmentation")
     a("--val_volumes_dir", type=str, default=None, help="4-D (or 3-D) validation images of this directory become the in-memory image_dict "
                                                       "that validate() previews as val_image_e###_p###.png (at most --val_patients of them)")
+    a("--resample", action="store_true", help="with --volumes_dir / --val_volumes_dir: resample every volume in-plane from its header's "
+                                              "spacing to --new_spacing on the device before the intensities are rescaled (the "
+                                              "reference's CardiacImage(resample=True))")
+    a("--new_spacing", type=float, nargs=2, default=None, metavar=("Y", "X"), help="in-plane training spacing in mm for --resample "
+                                                                                   "(default 1.4 1.4)")
     a("--val_patients", type=int, default=2, help="validation patients kept for the whole-volume previews (the reference loads 2)")
     a("--iters_per_epoch", type=int, default=50, help="iterations per epoch with --synthetic")
     a("--vgg_weights", type=str, default=None, help="local torchvision vgg16 state_dict for LPIPS (offline)")

@@ -82,7 +82,8 @@ def main(argv=None, brain=False):
         # device-resident volume cache + ONE kernel per batch (data_device.py); every rank draws the same global batch from
         # the same RandomState and keeps its own triplets, so the step sees the batch a single process would see
         from .data_device import TripletAugmenter, load_volume_dir
-        augmenter = TripletAugmenter(load_volume_dir(args_dict["volumes_dir"]), args_dict["width"],
+        augmenter = TripletAugmenter(load_volume_dir(args_dict["volumes_dir"], resample=bool(args_dict.get("resample")),
+                                                     new_spacing=args_dict.get("new_spacing")), args_dict["width"],
                                      args_dict.get("aug_patch_size") or args_dict["width"],
                                      rs=np.random.RandomState(args_dict["seed"]), device=args_dict["device"])
         step = max(2, int(args_dict.get("slice_step") or 2))
@@ -123,7 +124,8 @@ def main(argv=None, brain=False):
     image_dict_val = None       # train_cardiac_aesr.py:49-53,183: a few in-memory 4-D patients, previewed as whole volumes at every validation
     if args_dict.get("val_volumes_dir"):
         from .data_device import load_image_dict
-        image_dict_val = load_image_dict(args_dict["val_volumes_dir"], args_dict.get("val_patients") or 2)
+        image_dict_val = load_image_dict(args_dict["val_volumes_dir"], args_dict.get("val_patients") or 2,
+                                         resample=bool(args_dict.get("resample")), new_spacing=args_dict.get("new_spacing"))
     num_it_per_epoch = args_dict["iters_per_epoch"]
     args.num_it_per_epoch = num_it_per_epoch
     if dp.rank == 0:
