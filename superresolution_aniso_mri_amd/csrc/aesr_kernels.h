@@ -232,6 +232,7 @@ int aesr_launch_long_axis_views(const float* ref, const float* rec, float* ref_v
 struct TripletDesc { long long vol_off; int H, W, z_from, z_to, z_between, oy, ox, k; float gain, cutoff; };
 struct TripletTable { TripletDesc d[TRIPLET_MAX]; };
 int aesr_launch_triplet_assemble(const float* vol, const TripletTable& t, int B, int W, float* image, float* between, hipStream_t st);
+int aesr_launch_triplet_assemble_raw(const float* vol, const TripletTable& t, int B, int W, float* image, float* between, hipStream_t st);
 int aesr_launch_s2d(const float* x, float* out, int N, int H, int W, int C, int inverse, hipStream_t st);
 
 // ---- Laplacian-pyramid loss (lap.hip) ----

@@ -6,8 +6,11 @@
 // src = 0 outside the slice (the zero padding of AdjustToPatchSize goes through the intensity curve like in the reference),
 // s = from / to / between;  `image` receives all "from" slices then all "to" slices ([2B,1,W,W]), `between` [B,1,W,W].
 // The random numbers (crop origin, gain, cutoff, k) are drawn on the host in the reference's order and travel as a by-value table.
+// RAW (aesr_triplet_assemble_raw, include/aesr_hip_dataprep.h): the same gather, padding, rotation and layout without the intensity
+// curve -- the values are copied unchanged (the brain test transform of datasets/common_brains.py: AdjustToPatchSize + ToTensor only).
 #include "aesr_kernels.h"
 
+template <bool RAW>
 __global__ __launch_bounds__(256) void triplet_assemble_kernel(const float* __restrict__ vol, TripletTable t, int B, int W,
                                                                float* __restrict__ image, float* __restrict__ between) {
     const int b = blockIdx.z, s = blockIdx.y;
@@ -25,7 +28,7 @@ __global__ __launch_bounds__(256) void triplet_assemble_kernel(const float* __re
         const int y = d.oy + u, x = d.ox + v;
         float val = 0.f;
         if (y >= 0 && y < d.H && x >= 0 && x < d.W) val = src[(size_t)y * d.W + x];
-        dst[p] = 1.f / (1.f + expf(d.gain * (d.cutoff - val)));
+        dst[p] = RAW ? val : 1.f / (1.f + expf(d.gain * (d.cutoff - val)));
     }
 }
 
@@ -33,7 +36,16 @@ int aesr_launch_triplet_assemble(const float* vol, const TripletTable& t, int B,
                                  hipStream_t st) {
     int gx = ceil_div(W * W, 256);
     if (gx > 64) gx = 64;
-    hipLaunchKernelGGL(triplet_assemble_kernel, dim3(gx, 3, B), dim3(256), 0, st, vol, t, B, W, image, between);
+    hipLaunchKernelGGL(triplet_assemble_kernel<false>, dim3(gx, 3, B), dim3(256), 0, st, vol, t, B, W, image, between);
     AESR_LAUNCH_CHECK("triplet_assemble");
+    return AESR_OK;
+}
+
+int aesr_launch_triplet_assemble_raw(const float* vol, const TripletTable& t, int B, int W, float* image, float* between,
+                                     hipStream_t st) {
+    int gx = ceil_div(W * W, 256);
+    if (gx > 64) gx = 64;
+    hipLaunchKernelGGL(triplet_assemble_kernel<true>, dim3(gx, 3, B), dim3(256), 0, st, vol, t, B, W, image, between);
+    AESR_LAUNCH_CHECK("triplet_assemble_raw");
     return AESR_OK;
 }

@@ -50,12 +50,32 @@ def _resample_to(arr, spacing_zyx, new_spacing, f):
     return fn(np.asarray(arr, dtype=np.float32), spacing_zyx, NEW_SPACING if new_spacing is None else new_spacing)
 
 
-def load_volume_dir(path, resample=False, new_spacing=None):
+def _check_brain_options(thick_slices, downsample_steps, resample):
+    if thick_slices is None and downsample_steps is None:
+        return False
+    if downsample_steps is None or int(downsample_steps) < 1:
+        raise ValueError("thick_slices / downsample_steps: downsample_steps=%r must be a positive integer" % (downsample_steps,))
+    if thick_slices is not None and not float(thick_slices) > 0:
+        raise ValueError("thick_slices=%r must be a positive thickness (None for volumes that are blurred already)" % (thick_slices,))
+    if resample:
+        raise ValueError("resample (the cardiac in-plane step) and thick_slices / downsample_steps (the brain through-plane step) exclude each other")
+    return True
+
+
+def load_volume_dir(path, resample=False, new_spacing=None, thick_slices=None, downsample_steps=None, percs=(0, 100), device="cuda"):
     """All volumes of a directory (.npy, .nii, .nii.gz, .mha, .mhd; 3-D [Z,H,W] or 4-D [T,Z,H,W] -> one volume per frame),
     each rescaled to [0,1] by its 1st / 99th percentile when it is not already in that range.  ``resample``: every volume is first
-    resampled in-plane from its header's spacing to ``new_spacing`` (y, x; default 1.4 x 1.4 mm), as the reference's readers do."""
+    resampled in-plane from its header's spacing to ``new_spacing`` (y, x; default 1.4 x 1.4 mm), as the reference's readers do.
+
+    Brain volumes (``downsample_steps=K``, optionally ``thick_slices=MM``): what the reference loads from its blurred files
+    (datasets/common_brains.py:136-144, 206-208) made on the device -- one upload, one ``aesr_thick_slices(z_step=K)`` (skipped when
+    ``thick_slices`` is None: the files are blurred already, only ``[::K]`` applies) and one min / max rescale (``percs`` must be
+    (0, 100)).  The result is a list of CUDA tensors [ceil(Z / K), H, W], which ``BrainTripletAugmenter`` uses as its cache as they are."""
     import os
     from . import volume_io
+    brain = _check_brain_options(thick_slices, downsample_steps, resample)
+    if brain and tuple(percs) != (0, 100):
+        raise NotImplementedError("percs=%r: only the brain loaders' default window (0, 100), i.e. min / max, is built on the device" % (percs,))
     vols = []
     for name in sorted(os.listdir(path)):
         f = os.path.join(path, name)
@@ -75,6 +95,10 @@ def load_volume_dir(path, resample=False, new_spacing=None):
             v = np.asarray(v, dtype=np.float32)
             if v.ndim != 3:
                 raise ValueError("%s: expected a 3-D or 4-D volume, got shape %s" % (f, arr.shape))
+            if brain:
+                from .datasets.common_brains import lr_volume_on_device
+                vols.append(lr_volume_on_device(v, thick_slices, downsample_steps, device=device))
+                continue
             vols.append(v if (v.min() >= 0 and v.max() <= 1) else rescale_intensities(v))
     if not vols:
         raise FileNotFoundError("no .npy / .nii / .mha / .mhd volumes in %s" % path)
@@ -84,15 +108,23 @@ def load_volume_dir(path, resample=False, new_spacing=None):
 load_volumes = load_volume_dir
 
 
-def load_image_dict(path, max_patients=2, resample=False, new_spacing=None):
+def load_image_dict(path, max_patients=2, resample=False, new_spacing=None, thick_slices=None, downsample_steps=None, include_hr=True,
+                    device="cuda"):
     """The in-memory validation images ``validate(image_dict=...)`` previews (train_cardiac_aesr.py:49-53 of the reference: two 4-D
     patients): {p_id: {'image': [t,z,y,x] float32 in [0,1], 'patient_id': 'patientNNN', 'spacing': (z,y,x)}} from the first
     ``max_patients`` volumes of a directory (a 3-D volume counts as one frame).  p_id: the digits in the file name, else its rank.
     ``resample``: resample in-plane to ``new_spacing`` (default 1.4 x 1.4 mm) before the intensities are rescaled; 'spacing' then
-    reports [z, new_y, new_x] and 'original_spacing' keeps the file's own, as the reference's ``preprocessed4d`` does."""
+    reports [z, new_y, new_x] and 'original_spacing' keeps the file's own, as the reference's ``preprocessed4d`` does.
+
+    Brain volumes (``downsample_steps=K``, optionally ``thick_slices=MM``; 3-D files only): the LR / HR evaluation pair of the
+    reference's ``get_images(..., do_downsample=True, include_hr_images=True)``.  'image' is [ceil(Z / K), y, x]: the volume blurred on
+    the device (skipped when ``thick_slices`` is None), sub-sampled and rescaled to [0, 1] by its min / max; 'image_hr' (with
+    ``include_hr``) is the file's own array as float32, untouched, which ``evaluate`` scores against; 'spacing' is the file's, and
+    'num_slices' counts the slices of 'image'."""
     import os
     import re
     from . import volume_io
+    brain = _check_brain_options(thick_slices, downsample_steps, resample)
     out = {}
     for rank, name in enumerate(sorted(os.listdir(path))):
         f, low = os.path.join(path, name), name.lower()
@@ -104,6 +136,19 @@ def load_image_dict(path, max_patients=2, resample=False, new_spacing=None):
         else:
             continue
         original_spacing = spacing
+        if brain:
+            from .datasets.common_brains import lr_volume_on_device
+            hr = np.asarray(arr, dtype=np.float32)
+            if hr.ndim != 3:
+                raise ValueError("%s: a brain volume is 3-D [z, y, x], got shape %s" % (f, hr.shape))
+            lr = lr_volume_on_device(hr, thick_slices, downsample_steps, device=device).cpu().numpy()
+            digits = re.findall(r"\d+", name)
+            p_id = int(digits[0]) if digits and int(digits[0]) not in out else 1000 + rank
+            out[p_id] = {"image": lr, "image_hr": hr if include_hr else None, "patient_id": "patient{:03d}".format(p_id),
+                         "spacing": np.asarray(spacing, dtype=np.float64), "num_slices": lr.shape[0]}
+            if len(out) >= int(max_patients):
+                break
+            continue
         if resample:
             arr = _resample_to(arr, None if low.endswith(".npy") else spacing, new_spacing, f)
             ns = NEW_SPACING if new_spacing is None else tuple(new_spacing)[-2:]
@@ -249,3 +294,234 @@ class TripletAugmenter:
         transforms = [self.draw_transform(t[0]) for t in trips]         # the order assemble() draws them in
         lo, hi = (B * rank) // world, (B * (rank + 1)) // world
         return self.assemble(trips[lo:hi], transforms[lo:hi], reuse_output=reuse_output)
+
+
+# ---- brain volumes (datasets/common_brains.py, OASIS/dataset.py, dHCP/dataset.py of the reference) ---------------------------------
+class BrainSampler:
+    """The random draws of the reference's ``BrainDataset.__getitem__`` (datasets/common_brains.py:241-283), host only: from one
+    (slice id, number of slices) the neighbour ``slice step`` away, the slice in between, the from / to order and the mixing
+    coefficients, drawn from this sampler's own ``RandomState`` with the reference's calls in the reference's order.
+
+    ``dataset``: 'OASIS' always regularises on neighbours 2 apart (OASIS/dataset.py:95-101: ``adjacent_plus`` -> 2, ``mix`` ->
+    ``rs.choice([1, 2])``); every other brain dataset (dHCP, ADNI: the base class) uses ``downsample_steps``.
+
+    ``adjacent``, and ``mix`` whenever it draws step 1, make the reference call ``rs.choice`` on the empty range between two
+    neighbouring slices, which raises there; here that is a ``ValueError`` that says so."""
+
+    def __init__(self, dataset, slice_selection="adjacent_plus", downsample_steps=1, rs=None):
+        if slice_selection not in ("adjacent", "adjacent_plus", "mix"):
+            raise ValueError("slice_selection=%r: one of 'adjacent', 'adjacent_plus', 'mix'" % (slice_selection,))
+        self.dataset, self.slice_selection, self.downsample_steps = dataset, slice_selection, int(downsample_steps)
+        self.rs = rs if rs is not None else np.random.RandomState(1234)
+
+    def slice_step(self):
+        plus = 2 if self.dataset == "OASIS" else self.downsample_steps
+        if self.slice_selection == "adjacent":
+            return 1
+        if self.slice_selection == "adjacent_plus":
+            return plus
+        return int(self.rs.choice([1, plus]))
+
+    def draw(self, slice_id, num_slices):
+        """-> (slice_from, slice_to, slice_between, alpha_from, alpha_to); the alphas are float32, as the dataset stores them."""
+        from .datasets.common_brains import determine_interpol_coefficients
+        slice_id, num_slices = int(slice_id), int(num_slices)
+        step = self.slice_step()
+        last = num_slices - 1
+        if slice_id + step > last:                      # datasets/common.py:34-43, with its rs.choice
+            other = slice_id - step
+        elif slice_id == 0:
+            other = step
+        elif slice_id - step < 0:
+            other = slice_id + step
+        else:
+            other = int(self.rs.choice([slice_id - step, slice_id + step]))
+        if not 0 <= other <= last:
+            # fewer than 2 * step slices: the reference's rule leaves the volume here (and numpy wraps its -1 to the last slice)
+            raise ValueError("slice %d of a volume of %d slices has no neighbour %d slices away (the volume needs at least %d slices)"
+                             % (slice_id, num_slices, step, 2 * step))
+        lo, hi = min(slice_id, other), max(slice_id, other)
+        if hi - lo < 2:
+            raise ValueError("slice_selection=%r drew slice step %d: there is no slice between %d and %d, and the reference raises here "
+                             "too (rs.choice of an empty range, datasets/common_brains.py:281); use 'adjacent_plus'"
+                             % (self.slice_selection, step, lo, hi))
+        between = int(self.rs.choice(np.arange(lo + 1, hi)))
+        if self.rs.choice([0, 1]) == 0:
+            s_from, s_to = slice_id, other
+        else:
+            s_from, s_to = other, slice_id
+        a_from, a_to = determine_interpol_coefficients(s_from, s_to, between)
+        return s_from, s_to, between, np.float32(a_from), np.float32(a_to)
+
+
+class BrainTripletAugmenter:
+    """``TripletAugmenter`` for brain volumes: the batches of the reference's ``BrainDataset`` + ``get_transforms_brain`` +
+    ``prepare_batch_pairs`` from a device-resident cache, one launch per batch.
+
+    ``volumes``: [Z,H,W] float32 arrays or CUDA tensors in [0, 1] (``load_volume_dir(..., downsample_steps=K)`` returns such tensors;
+    they are used as they are).  Differences from the cardiac class, all the reference's:
+      - slices and coefficients come from a ``BrainSampler`` (``rs``); ``alpha_from`` / ``alpha_to`` vary per sample;
+      - the transform numbers come from a SECOND ``RandomState`` (``rs_transform``: the reference's dataset and transforms hold two
+        distinct default objects) in the brain order: crop top / left (only when a crop happens), then ``k``, then ``gain``, ``cutoff``;
+      - geometry (datasets/common_brains.py:47-100): with ``width < aug_patch_size`` (the reference's 220 for OASIS, 256 for dHCP / ADNI)
+        OASIS / ADNI slices are zero-padded up to ``aug_patch_size`` (``AdjustToPatchSize`` only pads) and a ``width`` window is cropped at
+        random; dHCP slices are not padded.  A slice that is ``width`` x ``width`` already is not cropped and draws nothing.  Otherwise
+        (no crop) OASIS / ADNI slices are padded up to ``width``, dHCP slices stay.  There is no centre crop: a slice that cannot be
+        cropped, is larger than the patch without a crop, or is not ``width`` x ``width`` in the end is refused with a ``ValueError``;
+      - ``raw=True``: the test transform (padding only, no rotation, no intensity curve) through ``aesr_triplet_assemble_raw``."""
+
+    def __init__(self, volumes, width, aug_patch_size=None, dataset="OASIS", slice_selection="adjacent_plus", downsample_steps=1, rs=None,
+                 rs_transform=None, device="cuda"):
+        self.width = int(width)
+        self.aug = int(aug_patch_size) if aug_patch_size else self.width
+        self.dataset, self.device = dataset, device
+        self.rs = rs if rs is not None else np.random.RandomState(1234)
+        self.rs_transform = rs_transform if rs_transform is not None else np.random.RandomState(1234)
+        self.sampler = BrainSampler(dataset, slice_selection, downsample_steps, self.rs)
+        self.pads = dataset != "dHCP"
+        self.crops = self.width < self.aug
+        offs, flat, self.shapes = [], [], []
+        n = 0
+        for v in volumes:
+            v = v.to(device=device, dtype=torch.float32) if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(device)
+            if v.dim() != 3:
+                raise ValueError("every volume must be [Z,H,W], got %s" % (tuple(v.shape),))
+            offs.append(n)
+            self.shapes.append(tuple(int(s) for s in v.shape))
+            flat.append(v.reshape(-1))
+            n += v.numel()
+        self.offsets = offs
+        step = 2 if dataset == "OASIS" else int(downsample_steps)
+        short = [i for i, sh in enumerate(self.shapes) if sh[0] < 2 * step]
+        if slice_selection != "adjacent" and short:
+            raise ValueError("volume %d has %d slices: neighbours %d slices apart need at least %d (below that the reference's neighbour rule "
+                             "leaves the volume)" % (short[0], self.shapes[short[0]][0], step, 2 * step))
+        self.cache = flat[0].contiguous() if len(flat) == 1 else torch.cat(flat)        # the device-resident volume cache
+        self._out = {}          # B -> (joined [3B,1,W,W] output buffer, alpha_from [B,1], alpha_to [B,1]): reused by every batch of that size
+        self._host_alphas = {}  # B -> (pinned [2,B,1] staging of the coefficients, event recorded after its copy)
+
+    # ---- host side ------------------------------------------------------------------------------------------------------------------
+    def _padded(self, vol_id, target, pads=None):
+        """(pad_top, pad_left, height, width) of a slice after ``AdjustToPatchSize((target, target))`` (shared_transforms.py:389-447)."""
+        _, H, W = self.shapes[vol_id]
+        if not (self.pads if pads is None else pads):
+            return 0, 0, H, W
+        return max(0, target - H) // 2, max(0, target - W) // 2, max(H, target), max(W, target)
+
+    def draw_transform(self, vol_id):
+        """(oy, ox, gain, cutoff, k), drawn from ``rs_transform``: [top, left] (only when a crop happens), k, gain, cutoff."""
+        rs, wd = self.rs_transform, self.width
+        pt, pl, h, w = self._padded(vol_id, self.aug if self.crops else wd)
+        top = left = 0
+        if self.crops and not (h == wd and w == wd):
+            if h <= wd or w <= wd:
+                raise ValueError("volume %d: a %d x %d slice cannot be cropped to %d x %d (RandomCrop draws from an empty range)"
+                                 % (vol_id, h, w, wd, wd))
+            top = int(rs.randint(0, h - wd))
+            left = int(rs.randint(0, w - wd))
+        elif not (h == wd and w == wd):
+            raise ValueError("volume %d: slices are %d x %d after padding, not %d x %d, and no crop is configured (width < aug_patch_size)"
+                             % (vol_id, h, w, wd, wd))
+        k = int(rs.randint(0, 4))
+        gain = float(rs.uniform(2.5, 7.5))
+        cutoff = float(rs.uniform(0.25, 0.75))
+        return top - pt, left - pl, gain, cutoff, k
+
+    def test_transform(self, vol_id, size=None):
+        """The test transform: padding up to ``width`` (OASIS / ADNI) or nothing (dHCP); no draw.  ``size``: every dataset's slices are
+        padded up to size x size instead (``eval_size``)."""
+        wd = self.width if size is None else int(size)
+        pt, pl, h, w = self._padded(vol_id, wd, pads=None if size is None else True)
+        if not (h == wd and w == wd):
+            raise ValueError("volume %d: slices are %d x %d after padding, not %d x %d: the test transform does not crop"
+                             % (vol_id, h, w, wd, wd))
+        return -pt, -pl, 0.0, 0.0, 0
+
+    def eval_size(self, multiple=1):
+        """The smallest square the test transform can pad EVERY volume's slices to: >= ``width`` and every H, W, a multiple of
+        ``multiple`` (the network's stride).  The reference's test transform leaves slices larger than the patch as they are (the
+        network is convolutional) and its loader needs them equal-sized; one padded square serves volumes of unequal size."""
+        s = max([self.width] + [max(H, W) for _, H, W in self.shapes])
+        m = max(1, int(multiple))
+        return (s + m - 1) // m * m
+
+    # ---- device side ----------------------------------------------------------------------------------------------------------------
+    def assemble(self, triplets, alphas, transforms=None, reuse_output=False, raw=False, size=None):
+        """triplets: list of (vol_id, z_from, z_to, z_between); alphas: list of (alpha_from, alpha_to); transforms: list of
+        (oy, ox, gain, cutoff, k) or None (drawn now, one sample after the other; ``raw``: the test transform, nothing drawn).
+        Returns {'image': [2B,1,W,W], 'slice_between': [B,1,W,W], 'alpha_from': [B,1], 'alpha_to': [B,1]}.  ``reuse_output``: all four
+        are this augmenter's persistent tensors of that batch size, written in place -- the coefficients too, so that a captured step
+        reads the new ones.  ``size`` (with ``raw`` only): the slices are padded up to size x size instead of ``width``."""
+        B, Wd = len(triplets), self.width
+        if size is not None:
+            if not raw or reuse_output:
+                raise ValueError("size= goes with raw=True (the test transform) and tensors of its own")
+            Wd = int(size)
+        if len(alphas) != B:
+            raise ValueError("%d triplets but %d coefficient pairs" % (B, len(alphas)))
+        if transforms is None:
+            transforms = [self.test_transform(t[0], size) if raw else self.draw_transform(t[0]) for t in triplets]
+        if reuse_output:
+            if B not in self._out:
+                both = torch.empty((3 * B, 1, Wd, Wd), device=self.device, dtype=torch.float32)
+                ab = torch.empty((2, B, 1), device=self.device, dtype=torch.float32)
+                self._out[B] = (both, ab)
+                self._host_alphas[B] = (torch.empty((2, B, 1), dtype=torch.float32).pin_memory(), torch.cuda.Event())
+            both, ab = self._out[B]
+            image, between = both[:2 * B], both[2 * B:]
+            host, copied = self._host_alphas[B]
+            copied.synchronize()            # the previous batch's copy has read the staging buffer (long done: no wait in practice)
+        else:
+            image = torch.empty((2 * B, 1, Wd, Wd), device=self.device, dtype=torch.float32)
+            between = torch.empty((B, 1, Wd, Wd), device=self.device, dtype=torch.float32)
+            ab = torch.empty((2, B, 1), device=self.device, dtype=torch.float32)
+            host, copied = torch.empty((2, B, 1), dtype=torch.float32), None
+        host[:, :, 0] = torch.from_numpy(np.asarray(alphas, dtype=np.float32).reshape(B, 2).T.copy())
+        ab.copy_(host, non_blocking=copied is not None)
+        if copied is not None:
+            copied.record()
+        launch = lib.aesr_triplet_assemble_raw if raw else lib.aesr_triplet_assemble
+        _hip.require_gpu_tensor(self.cache, "volume cache")
+        for b0 in range(0, B, 64):
+            n = min(64, B - b0)
+            descs = (_hip.TripletDesc * n)()
+            for i in range(n):
+                vid, zf, zt, zb = triplets[b0 + i]
+                oy, ox, gain, cutoff, k = transforms[b0 + i]
+                Z, H, W = self.shapes[vid]
+                if not (0 <= zf < Z and 0 <= zt < Z and 0 <= zb < Z):
+                    raise ValueError("slice index outside volume %d (Z=%d)" % (vid, Z))
+                descs[i] = _hip.TripletDesc(self.offsets[vid], H, W, zf, zt, zb, oy, ox, k, gain, cutoff)
+            if B <= 64:
+                img_dst, btw_dst = image, between
+            else:       # more than one launch: each launch owns a contiguous [from | to] pair block -> assemble then scatter
+                img_dst = torch.empty((2 * n, 1, Wd, Wd), device=self.device, dtype=torch.float32)
+                btw_dst = between[b0:b0 + n]
+            check(launch(ptr(self.cache), descs, n, Wd, ptr(img_dst), ptr(btw_dst), stream()),
+                  "aesr_triplet_assemble_raw" if raw else "aesr_triplet_assemble")
+            if B > 64:
+                image[b0:b0 + n] = img_dst[:n]
+                image[B + b0:B + b0 + n] = img_dst[n:]
+        out = {"image": image, "slice_between": between, "alpha_from": ab[0], "alpha_to": ab[1]}
+        if reuse_output:
+            out["_persistent"] = True
+        return out
+
+    def next_batch(self, B, reuse_output=False, shard=None, raw=False, size=None):
+        """A random batch: B random (volume, slice) pairs, each completed by the sampler.  ``reuse_output`` and ``shard`` = (rank, world)
+        as in ``TripletAugmenter.next_batch``: every rank draws the whole global batch (slices from ``rs``, then transforms from
+        ``rs_transform``) and assembles its own triplets [B r / W, B (r + 1) / W)."""
+        trips, alphas = [], []
+        for _ in range(B):
+            vid = int(self.rs.randint(0, len(self.shapes)))
+            Z = self.shapes[vid][0]
+            sid = int(self.rs.randint(0, Z))
+            zf, zt, zb, af, at = self.sampler.draw(sid, Z)
+            trips.append((vid, zf, zt, zb))
+            alphas.append((af, at))
+        transforms = [self.test_transform(t[0], size) if raw else self.draw_transform(t[0]) for t in trips]
+        lo, hi = 0, B
+        if shard is not None:
+            rank, world = int(shard[0]), int(shard[1])
+            lo, hi = (B * rank) // world, (B * (rank + 1)) // world
+        return self.assemble(trips[lo:hi], alphas[lo:hi], transforms[lo:hi], reuse_output=reuse_output, raw=raw, size=size)

@@ -60,6 +60,12 @@ def build_parser():
                                               "reference's CardiacImage(resample=True))")
     a("--new_spacing", type=float, nargs=2, default=None, metavar=("Y", "X"), help="in-plane training spacing in mm for --resample "
                                                                                    "(default 1.4 1.4)")
+    a("--thick_slices", type=float, default=None, metavar="MM", help="brain datasets with --volumes_dir / --val_volumes_dir: simulate slices "
+                                                                     "of this thickness on the device (Gaussian profile along z, FWHM = MM voxels) "
+                                                                     "before every --downsample_steps-th slice is kept; default: downsample_steps "
+                                                                     "(OASIS, ADNI) or downsample_steps / 2 (dHCP), as the reference's dataset creators")
+    a("--no_thick_slices", action="store_true", help="the volumes are blurred already (files a create_lr_dataset run wrote): only keep every "
+                                                     "--downsample_steps-th slice")
     a("--val_patients", type=int, default=2, help="validation patients kept for the whole-volume previews (the reference loads 2)")
     a("--iters_per_epoch", type=int, default=50, help="iterations per epoch with --synthetic")
     a("--vgg_weights", type=str, default=None, help="local torchvision vgg16 state_dict for LPIPS (offline)")
@@ -85,6 +91,10 @@ def finalize_args(args):
         args.vae_beta, args.lamb = 0, 0
     if args.downsample_steps is None:
         raise ValueError("Error - arguments - downsample_steps cannot be None")
+    if args.no_thick_slices and args.thick_slices is not None:
+        raise ValueError("Error - arguments - --thick_slices and --no_thick_slices exclude each other")
+    if args.dataset in ("OASIS", "ADNI", "dHCP") and args.thick_slices is None and not args.no_thick_slices:
+        args.thick_slices = args.downsample_steps / 2 if args.dataset == "dHCP" else float(args.downsample_steps)
     forced = {"OASIS": 220, "dHCP": 256}
     if args.dataset in forced and args.aug_patch_size is None and args.width < forced[args.dataset]:
         args.aug_patch_size = forced[args.dataset]

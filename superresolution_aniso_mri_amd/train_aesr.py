@@ -3,7 +3,9 @@ train_brain_aesr.py:137-206) for the MI355X build: same flags, output layout (se
 log_images/, loss*.npz) and epoch bookkeeping (iters starts at 1, validate when (iters+1) % num_it_per_epoch == 0).
 
 Data: the reference's SimpleITK/NIfTI dataset readers and numpy augmentations are host-side I/O outside this build's
-hot path; ``--synthetic`` feeds device-resident synthetic triplets in the same batch layout.  Launch under
+hot path; ``--synthetic`` feeds device-resident synthetic triplets in the same batch layout, ``--volumes_dir``
+feeds the volumes of a directory through the on-device augmenters of data_device.py (cardiac datasets: ``TripletAugmenter``; OASIS /
+dHCP / ADNI: thick slices simulated on the device, then ``BrainTripletAugmenter``).  Launch under
 ``python -m torch.distributed.run --nproc-per-node N`` for data parallel training (one process per GPU, RCCL)."""
 import os
 from shutil import rmtree
@@ -78,7 +80,23 @@ def main(argv=None, brain=False):
     B = args_dict["batch_size"]
 
     augmenter = None
-    if args_dict.get("volumes_dir"):
+    brain_volumes = bool(args_dict.get("volumes_dir")) and args_dict["dataset"] in ("OASIS", "dHCP", "ADNI")
+    # brain volumes: thick slices simulated on the device, every downsample_steps-th slice kept (datasets/common_brains.py); None: blurred already
+    brain_opts = dict(thick_slices=None if args_dict.get("no_thick_slices") else args_dict.get("thick_slices"),
+                      downsample_steps=args_dict["downsample_steps"])
+    if brain_volumes:
+        # the reference's BrainDataset: slice distances decide the neighbour, the slice in between and the mixing coefficients; the
+        # dataset and the transforms draw from two RandomStates (data_device.BrainTripletAugmenter)
+        from .data_device import BrainTripletAugmenter, load_volume_dir
+        # ADNI: get_transforms_brain pads to its constant 256 and crops below it (datasets/common_brains.py:59-71); the reference's
+        # arguments force aug_patch_size for OASIS and dHCP only, so that constant is supplied here
+        brain_canvas = 256 if args_dict["dataset"] == "ADNI" and args_dict["width"] < 256 else args_dict["width"]
+        augmenter = BrainTripletAugmenter(load_volume_dir(args_dict["volumes_dir"], device=args_dict["device"], **brain_opts), args_dict["width"],
+                                          args_dict.get("aug_patch_size") or brain_canvas, dataset=args_dict["dataset"],
+                                          slice_selection=args_dict["slice_selection"], downsample_steps=args_dict["downsample_steps"],
+                                          rs=np.random.RandomState(args_dict["seed"]), rs_transform=np.random.RandomState(args_dict["seed"] + 1),
+                                          device=args_dict["device"])
+    elif args_dict.get("volumes_dir"):
         # device-resident volume cache + ONE kernel per batch (data_device.py); every rank draws the same global batch from
         # the same RandomState and keeps its own triplets, so the step sees the batch a single process would see
         from .data_device import TripletAugmenter, load_volume_dir
@@ -91,6 +109,12 @@ def main(argv=None, brain=False):
     synth_pool = {}       # --synthetic: a small pool of device-resident batches made BEFORE the loop (rendering one on the host costs tens of ms)
 
     def make_batch(seed, n, training=True):
+        if brain_volumes:
+            # as below; the validation batch goes through the brain TEST transform (padding only, no intensity curve: raw=True), padded
+            # to one square that holds every volume's slices and suits the network's stride
+            stride = max(1, args_dict["width"] // max(1, args_dict["latent_width"]))
+            return augmenter.next_batch(n, reuse_output=training, shard=(dp.rank, dp.world) if dp.active else None, raw=not training,
+                                        size=None if training else augmenter.eval_size(stride))
         if augmenter is not None:
             # training batches go into the augmenter's persistent output buffer, which the captured step reads directly (data parallel: the
             # rank's own triplets only -- every rank draws the whole global batch's random numbers); the validation batch is kept for the
@@ -124,8 +148,14 @@ def main(argv=None, brain=False):
     image_dict_val = None       # train_cardiac_aesr.py:49-53,183: a few in-memory 4-D patients, previewed as whole volumes at every validation
     if args_dict.get("val_volumes_dir"):
         from .data_device import load_image_dict
-        image_dict_val = load_image_dict(args_dict["val_volumes_dir"], args_dict.get("val_patients") or 2,
-                                         resample=bool(args_dict.get("resample")), new_spacing=args_dict.get("new_spacing"))
+        if brain_volumes:
+            image_dict_val = load_image_dict(args_dict["val_volumes_dir"], args_dict.get("val_patients") or 2, device=args_dict["device"],
+                                             **brain_opts)
+            for data in image_dict_val.values():
+                data["image"] = data["image"][None]           # the whole-volume preview walks [t,z,y,x]: a brain volume is one frame
+        else:
+            image_dict_val = load_image_dict(args_dict["val_volumes_dir"], args_dict.get("val_patients") or 2,
+                                             resample=bool(args_dict.get("resample")), new_spacing=args_dict.get("new_spacing"))
     num_it_per_epoch = args_dict["iters_per_epoch"]
     args.num_it_per_epoch = num_it_per_epoch
     if dp.rank == 0:
