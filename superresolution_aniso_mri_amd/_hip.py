@@ -1,4 +1,4 @@
-"""ctypes binding of libaesr_hip.so (C ABI: include/aesr_hip.h, include/aesr_hip_preproc.h and include/aesr_hip_dataprep.h).
+"""ctypes binding of libaesr_hip.so (C ABI: include/aesr_hip.h, include/aesr_hip_preproc.h, include/aesr_hip_dataprep.h and include/aesr_hip_train.h).
 
 There is NO fallback: if the shared library is missing or an entry point is absent this module raises at
 import time, and every wrapper raises RuntimeError with the library's own message when a call fails.
@@ -181,6 +181,11 @@ SIGNATURES_DATAPREP = {
     "aesr_thick_slices": (c_int, [P, P, c_int, c_int, c_int, c_int, DP, c_int, P]),
     "aesr_triplet_assemble_raw": (c_int, [P, ctypes.POINTER(TripletDesc), c_int, c_int, P, P, P]),
 }
+# the fused training-step ABI (include/aesr_hip_train.h, same library): must list every symbol that header declares (checked by tests)
+SIGNATURES_TRAIN = {
+    "aesr_conv2d_cout1_bwd_workspace_floats": (c_size_t, [c_int]),
+    "aesr_conv2d_cout1_bwd": (c_int, [P] * 8 + [c_int] * 5 + [c_float, c_int, c_float, P]),
+}
 P2P_HANDLE_BYTES, P2P_SLOTS = 64, 32
 COMM_ID_BYTES = 128
 COMM_F32, COMM_F64, COMM_SUM, COMM_MAX = 0, 1, 0, 1
@@ -201,7 +206,8 @@ def _load():
             "libaesr_hip.so not found at %s -- build it with `python __graft_entry__.py` (or `make -C "
             "superresolution_aniso_mri_amd/csrc`). The HIP extension is mandatory: there is no CPU/eager fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_PREPROC.items()) + list(SIGNATURES_DATAPREP.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_PREPROC.items()) + list(SIGNATURES_DATAPREP.items())
+                                   + list(SIGNATURES_TRAIN.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             raise RuntimeError("libaesr_hip.so does not export %s (stale build?)" % name)

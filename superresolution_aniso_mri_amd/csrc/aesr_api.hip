@@ -10,6 +10,7 @@
 
 #include "../../include/aesr_hip.h"
 #include "../../include/aesr_hip_dataprep.h"
+#include "../../include/aesr_hip_train.h"
 #include "aesr_kernels.h"
 
 // ---- error string ------------------------------------------------------------------------------------------
@@ -829,6 +830,30 @@ int aesr_conv2d_cout1_dgrad_pre(const float* dy, const float* w_flipped, const f
     a.N = N; a.Hs = H; a.Ws = W; a.Ho = H; a.Wo = W; a.C = Cin; a.ps = 0;
     a.act = ACT_NONE; a.mask_act = y_saved ? mask_act : ACT_NONE; a.slope = slope;
     return aesr_launch_thin_expand(a, (hipStream_t)stream);
+}
+
+// ---- include/aesr_hip_train.h: the Cout == 1 convolution's backward in one pass over its saved input --------------------------------
+size_t aesr_conv2d_cout1_bwd_workspace_floats(int Cin) { return Cin > 0 ? (size_t)(THIN_NWG + 1) * 10 * Cin : 0; }
+
+int aesr_conv2d_cout1_bwd(const float* x, const float* dout, const float* out, const float* w_flipped, float* dw, float* db, float* dx,
+                          float* workspace, int N, int H, int W, int Cin, int act, float slope, int mask_act, float mask_slope,
+                          void* stream) {
+    AESR_CHECK_ARG(x && dout && w_flipped && dw && db && dx && workspace, "aesr_conv2d_cout1_bwd: null pointer");
+    AESR_CHECK_ARG(N > 0 && H > 0 && W > 0, "aesr_conv2d_cout1_bwd: empty shape");
+    AESR_CHECK_ARG(thin_channels_ok(Cin), "aesr_conv2d_cout1_bwd: Cin=%d must be 4 times a power of two (4..256)", Cin);
+    AESR_CHECK_ARG(act >= ACT_NONE && act <= ACT_SIGMOID && mask_act >= ACT_NONE && mask_act <= ACT_SIGMOID,
+                   "aesr_conv2d_cout1_bwd: unknown activation (act=%d, mask_act=%d)", act, mask_act);
+    AESR_CHECK_ARG(out || act == ACT_NONE, "aesr_conv2d_cout1_bwd: out (the saved output) is needed for act=%d", act);
+    // weight gradient = thin reduce of x against dpre = dout * act'(out), taps flipped (aesr_conv2d_cout1_wgrad); data gradient = the
+    // expand of dpre with the flipped filter, masked by the derivative of the activation that produced x (aesr_conv2d_cout1_dgrad_pre):
+    // both from the one read of x
+    ThinArgs a;
+    memset(&a, 0, sizeof(a));
+    a.s = dout; a.sout = act == ACT_NONE ? nullptr : out; a.t = x; a.partial = workspace; a.w = w_flipped; a.out = dx;
+    a.N = N; a.Hs = H; a.Ws = W; a.Ho = H; a.Wo = W; a.C = Cin; a.ps = 0; a.with_be = 0;
+    a.act = act; a.slope = slope; a.mask_act = mask_act; a.mask_slope = mask_slope;
+    if (int e = aesr_launch_thin_reduce_dx(a, THIN_NWG, (hipStream_t)stream)) return e;
+    return aesr_launch_thin_cout1_finish_sum(workspace, THIN_NWG, dw, db, Cin, (hipStream_t)stream);
 }
 
 size_t aesr_stemconv_folded_floats(int C1) { return (size_t)2 * 9 * C1; }

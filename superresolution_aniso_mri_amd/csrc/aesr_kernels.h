@@ -138,9 +138,13 @@ struct ThinArgs {
     float slope;
     int with_be;
     int tiles_y, tiles_x, ntiles;
+    // reduce with the data gradient (aesr_launch_thin_reduce_dx): w = the flipped filter, out = dx, mask_act = the activation that produced t
+    const float* sout;     // saved output [N,Hs,Ws] of the convolution's own activation `act`: s is staged as s * act'(sout); or nullptr
+    float mask_slope;      // slope of mask_act (slope is that of act)
 };
 int aesr_launch_thin_expand(ThinArgs a, hipStream_t st);
 int aesr_launch_thin_reduce(ThinArgs a, int nwg, hipStream_t st);
+int aesr_launch_thin_reduce_dx(ThinArgs a, int nwg, hipStream_t st);
 int aesr_launch_thin_collapse(const float* x, const float* w, const float* bias, float* out, int N, int H, int W, int C, int act,
                               float slope, hipStream_t st);
 int aesr_launch_thin_stem_fold(const float* ws, const float* bs, const float* w1, float* folded, int Cs, int C1, hipStream_t st);
@@ -148,6 +152,7 @@ int aesr_launch_thin_stem_finish(const float* R, const float* ws, const float* b
                                  float* dw1, float* db1, int Cs, int C1, hipStream_t st);
 int aesr_launch_thin_cout1_flip(const float* w, float* wexp, int Cin, hipStream_t st);
 int aesr_launch_thin_cout1_finish(const float* R, float* dw, float* db, int Cin, hipStream_t st);
+int aesr_launch_thin_cout1_finish_sum(const float* partial, int np, float* dw, float* db, int Cin, hipStream_t st);
 
 struct BnGroups { int G; int nstart[5]; };
 struct BnApplyArgs {

@@ -43,6 +43,38 @@ __device__ __forceinline__ void thin_stage(const ThinArgs& a, float (*xs)[THIN_X
     }
 }
 
+// The same patch for an 8-row tile with s standing behind an activation whose saved output is a.sout: the patch holds s * act'(sout) (what
+// act_bwd_kernel would have written; halo pixels are recomputed by the neighbouring tile, values outside the image stay 0).  Straight-line
+// code, loads first: the caller has other loads in flight, and a loop that waits for its own loads makes the compiler drain those in front of it.
+#define THIN_NPV (((THIN_TH + 2) * 66 + 255) / 256)            // patch values per thread (TW <= 64)
+__device__ __forceinline__ void thin_stage_act(const ThinArgs& a, float (*xs)[THIN_XS], int n, int y0, int x0, int TW) {
+    const int PW = TW + 2;
+    const float* so = a.sout ? a.sout : a.s;
+    float pv[THIN_NPV], po[THIN_NPV];
+    bool in[THIN_NPV];
+    // branch-free: every lane loads from a clamped (always valid) element and the value is dropped afterwards, so all loads go out back to back
+#pragma unroll
+    for (int j = 0; j < THIN_NPV; ++j) {
+        const int q = threadIdx.x + j * 256;
+        const int r = q / PW, c = q - r * PW;
+        const int sy = y0 + r - 1 - a.ps, sx = x0 + c - 1 - a.ps;
+        in[j] = q < (THIN_TH + 2) * PW && sy >= 0 && sy < a.Hs && sx >= 0 && sx < a.Ws;
+        const size_t i = in[j] ? ((size_t)n * a.Hs + sy) * a.Ws + sx : 0;
+        pv[j] = a.s[i];
+        po[j] = so[i];
+    }
+#pragma unroll
+    for (int j = 0; j < THIN_NPV; ++j) {
+        const int q = threadIdx.x + j * 256;
+        const int r = q / PW, c = q - r * PW;
+        if (q < (THIN_TH + 2) * PW) {
+            float v = in[j] ? pv[j] : 0.f;
+            if (in[j] && a.sout) v = v * act_grad_from_output(po[j], a.act, a.slope);
+            xs[r][c] = v;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void thin_expand_kernel(ThinArgs a) {
     __shared__ float xs[THIN_ETH + 2][THIN_XS];
     const int C4 = a.C >> 2, TW = thin_tw(C4);
@@ -107,7 +139,11 @@ __global__ __launch_bounds__(256) void thin_expand_kernel(ThinArgs a) {
 }
 
 // partial[wg][row][c]: rows 0..8 = r, (WITH_BE: rows 9..17 = rb), last row: column 0 = ssum, other columns 0
-template <bool WITH_BE>
+// WITH_DX (the Cout == 1 convolution's whole backward in one pass over T): s is staged behind its own activation's derivative, and the
+// pixel whose 16 bytes of T a thread holds also gets its data gradient  out = mask(T) * sum_t w[t][c] * s[p - t]  -- thin_expand_kernel's
+// arithmetic in thin_expand_kernel's order; the mask tensor IS T (the saved input of the convolution is the output of the activation
+// in front of it), so T is read once for both gradients.
+template <bool WITH_BE, bool WITH_DX = false>
 __global__ __launch_bounds__(256) void thin_reduce_kernel(ThinArgs a) {
     __shared__ float xs[THIN_TH + 2][THIN_XS];
     extern __shared__ __attribute__((aligned(16))) float red[];      // [4 waves][NROW][C]
@@ -122,6 +158,14 @@ __global__ __launch_bounds__(256) void thin_reduce_kernel(ThinArgs a) {
         accW[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
         accB[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
+    f32x4 w[WITH_DX ? 9 : 1];
+    if constexpr (WITH_DX) {
+#pragma unroll
+        for (int t = 0; t < 9; ++t) w[t] = *(const f32x4*)(a.w + t * a.C + c4 * 4);
+    }
+    // WITH_DX: act_grad_from_output(T, mask_act, mask_slope) with its case distinction taken out of the pixel loop (the same values)
+    const bool msig = WITH_DX && a.mask_act == ACT_SIGMOID;
+    const float mneg = (WITH_DX && a.mask_act == ACT_LRELU) ? a.mask_slope : 0.f;
     const int tpi = a.tiles_y * a.tiles_x;
     for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
         const int n = tile / tpi;
@@ -129,7 +173,7 @@ __global__ __launch_bounds__(256) void thin_reduce_kernel(ThinArgs a) {
         const int ty = trem / a.tiles_x, tx = trem - ty * a.tiles_x;
         const int y0 = ty * THIN_TH, x0 = tx * TW;
         __syncthreads();
-        thin_stage(a, xs, n, y0, x0, TW);
+        if constexpr (!WITH_DX) thin_stage(a, xs, n, y0, x0, TW);
         const int ox = x0 + pl;
         const bool xin = pl < TW && ox < a.Wo;
         const int plr = pl < TW ? pl : 0;               // idle threads (C < 16) read a valid LDS column, their g is 0
@@ -140,6 +184,9 @@ __global__ __launch_bounds__(256) void thin_reduce_kernel(ThinArgs a) {
             g[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
             if (xin && oy < a.Ho) g[r] = *(const f32x4*)(a.t + (((size_t)n * a.Ho + oy) * a.Wo + ox) * a.C + c4 * 4);
         }
+        // behind the loads of T, so that patch and T arrive in ONE memory latency: with 512 workgroups (two waves per SIMD) a tile's
+        // latencies are not hidden by other workgroups, and the wait for the patch also drains the stores of the previous tile
+        if constexpr (WITH_DX) thin_stage_act(a, xs, n, y0, x0, TW);
         float mxf[3];
         mxf[0] = (ox - 1 >= 0) ? 1.f : 0.f;
         mxf[1] = 1.f;
@@ -148,11 +195,26 @@ __global__ __launch_bounds__(256) void thin_reduce_kernel(ThinArgs a) {
 #pragma unroll
         for (int r = 0; r < THIN_TH; ++r) {
             const int oy = y0 + r;
+            f32x4 dx = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 const float v = xs[r + t / 3][plr + t % 3];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) accW[t][e] = fmaf(g[r][e], v, accW[t][e]);
+                if constexpr (WITH_DX) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dx[e] = fmaf(w[t][e], v, dx[e]);
+                }
+            }
+            if constexpr (WITH_DX) {
+                if (msig) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dx[e] *= g[r][e] * (1.f - g[r][e]);
+                } else if (a.mask_act != ACT_NONE) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dx[e] *= g[r][e] > 0.f ? 1.f : mneg;
+                }
+                if (xin && oy < a.Ho) *(f32x4*)(a.out + (((size_t)n * a.Ho + oy) * a.Wo + ox) * a.C + c4 * 4) = dx;
             }
             if (WITH_BE) {
 #pragma unroll
@@ -336,6 +398,45 @@ __global__ __launch_bounds__(256) void thin_cout1_flip_kernel(const float* __res
 }
 
 // Cout == 1 conv: dw[ci*9+k] = R[8-k][ci], db = R[9][0]
+// Overload for the one-pass backward: R is summed here from the np partial rows [np][10][Cin] of thin_reduce_kernel and goes straight to
+// dw / db.  The summation tree is sum_partials_kernel's (conv_small.hip), kept operation for operation so that both paths give the same
+// bits: block = 64 columns x 16 row-lanes, four double accumulators striding 64 rows, (s0 + s1) + (s2 + s3), then the 16 lanes in order.
+__global__ __launch_bounds__(1024) void thin_cout1_finish_kernel(const float* __restrict__ partial, int np, float* __restrict__ dw,
+                                                                 float* __restrict__ db, int Cin) {
+    __shared__ double red[16][64];
+    const int n = 10 * Cin, nuse = 9 * Cin + 1;          // the rest of row 9 is zero and goes nowhere
+    const int col = threadIdx.x & 63, rl = threadIdx.x >> 6;
+    const int o = blockIdx.x * 64 + col;
+    double s = 0.0;
+    if (o < nuse) {
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        int p = rl;
+        for (; p + 48 < np; p += 64) {
+            const float v0 = partial[(size_t)p * n + o], v1 = partial[(size_t)(p + 16) * n + o];
+            const float v2 = partial[(size_t)(p + 32) * n + o], v3 = partial[(size_t)(p + 48) * n + o];
+            s0 += (double)v0;
+            s1 += (double)v1;
+            s2 += (double)v2;
+            s3 += (double)v3;
+        }
+        for (; p < np; p += 16) s0 += (double)partial[(size_t)p * n + o];
+        s = (s0 + s1) + (s2 + s3);
+    }
+    red[rl][col] = s;
+    __syncthreads();
+    if (rl == 0 && o < nuse) {
+        s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) s += red[k][col];
+        if (o < 9 * Cin) {
+            const int t = o / Cin, ci = o - t * Cin;
+            dw[ci * 9 + 8 - t] = (float)s;
+        } else {
+            db[0] = (float)s;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void thin_cout1_finish_kernel(const float* __restrict__ R, float* __restrict__ dw,
                                                                 float* __restrict__ db, int Cin) {
     for (int o = blockIdx.x * 256 + threadIdx.x; o < 9 * Cin; o += gridDim.x * 256) {
@@ -385,6 +486,21 @@ int aesr_launch_thin_reduce(ThinArgs a, int nwg, hipStream_t st) {
     return AESR_OK;
 }
 
+int aesr_launch_thin_reduce_dx(ThinArgs a, int nwg, hipStream_t st) {
+    if (!thin_shape_ok(a)) {
+        aesr_set_error("thin conv: C=%d must be 4 times a power of two (4..256)", a.C);
+        return AESR_ERR_ARG;
+    }
+    const int TW = thin_tw(a.C / 4);
+    a.tiles_y = ceil_div(a.Ho, THIN_TH);
+    a.tiles_x = ceil_div(a.Wo, TW);
+    a.ntiles = a.N * a.tiles_y * a.tiles_x;
+    const size_t shmem = (size_t)4 * 10 * a.C * sizeof(float);
+    hipLaunchKernelGGL((thin_reduce_kernel<false, true>), dim3(nwg), dim3(256), shmem, st, a);
+    AESR_LAUNCH_CHECK("thin_reduce_dx");
+    return AESR_OK;
+}
+
 int aesr_launch_thin_collapse(const float* x, const float* w, const float* bias, float* out, int N, int H, int W, int C, int act,
                               float slope, hipStream_t st) {
     const int C4 = C / 4;
@@ -424,5 +540,11 @@ int aesr_launch_thin_cout1_flip(const float* w, float* wexp, int Cin, hipStream_
 int aesr_launch_thin_cout1_finish(const float* R, float* dw, float* db, int Cin, hipStream_t st) {
     hipLaunchKernelGGL(thin_cout1_finish_kernel, dim3(ceil_div(9 * Cin, 256)), dim3(256), 0, st, R, dw, db, Cin);
     AESR_LAUNCH_CHECK("thin_cout1_finish");
+    return AESR_OK;
+}
+
+int aesr_launch_thin_cout1_finish_sum(const float* partial, int np, float* dw, float* db, int Cin, hipStream_t st) {
+    hipLaunchKernelGGL(thin_cout1_finish_kernel, dim3(ceil_div(9 * Cin + 1, 64)), dim3(1024), 0, st, partial, np, dw, db, Cin);
+    AESR_LAUNCH_CHECK("thin_cout1_finish_sum");
     return AESR_OK;
 }

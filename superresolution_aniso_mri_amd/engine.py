@@ -60,6 +60,10 @@ PROFILER = None
 # runs -- the values whose signs ARE the path's LeakyReLU decisions (the backward masks are taken from these very tensors)
 TRACE = None
 FUSE_STEM = os.environ.get("AESR_FUSE_STEM", "1") != "0"      # fold the encoder stem into the first 3x3 conv
+# the Cout == 1 output convolution's backward (activation derivative, weight / bias gradient, data gradient) in one pass over its saved
+# input (aesr_conv2d_cout1_bwd, include/aesr_hip_train.h) instead of aesr_act_bwd + aesr_conv2d_cout1_wgrad + aesr_conv2d_cout1_dgrad_pre:
+# two launches for five, the largest activation of the step read once instead of twice, bit-identical results; =0 keeps the three calls
+FUSE_COUT1_BWD = os.environ.get("AESR_FUSE_COUT1_BWD", "1") != "0"
 # 3x3 / padding-1 convolutions with enough channels run in Winograd F(2x2,3x3) form (csrc/conv_wino.hip: 2.25x fewer MFMA flops,
 # results equal to the implicit GEMM within 2-4e-7); AESR_WINO=0 keeps every layer on the exact-fp32 fma-chain implicit GEMM
 USE_WINO = os.environ.get("AESR_WINO", "1") != "0"
@@ -715,6 +719,24 @@ class SequentialRunner:
                 if s.in_up2:
                     H, W = 2 * H, 2 * W                    # the convolution's size; xin is the half-resolution tensor
                 Ho, Wo = (H, W) if s.s2d else s.out_hw(H, W)
+                if (FUSE_COUT1_BWD and k == len(steps) - 1 and s.cout == 1 and s.ks == 3 and s.pad == 1 and _thin_channels(s.cin)
+                        and not s.s2d and not s.in_up2 and s.mod.bias is not None and (k > 0 or need_input_grad) and s.flipped is not None
+                        and s.packed_epoch == (self.weights_epoch, s.mod.weight._version, s.mod.weight.data_ptr())):
+                    mask_act, mslope = _hip.ACT_NONE, 0.0
+                    if k > 0 and steps[k - 1].kind in ("conv", "stemconv") and steps[k - 1].act != _hip.ACT_NONE:
+                        mask_act, mslope = steps[k - 1].act, steps[k - 1].slope
+                    # the kernel takes the derivative mask from the convolution's own saved input: that must BE the producer's saved output
+                    if mask_act == _hip.ACT_NONE or saved[k - 1][1].data_ptr() == xin.data_ptr():
+                        dw, db = self._grad_dst(s.mod.weight, grads), self._grad_dst(s.mod.bias, grads)
+                        ws = _empty((lib.aesr_conv2d_cout1_bwd_workspace_floats(s.cin),), g)
+                        dx = _empty((N, H, W, s.cin), g)
+                        _pb("thin_reduce", 0.0, 4.0 * (2 * N * H * W * s.cin + 2 * N * H * W))
+                        check(lib.aesr_conv2d_cout1_bwd(ptr(xin), ptr(g), ptr(yout) if s.act != _hip.ACT_NONE else None, ptr(s.flipped), ptr(dw),
+                                                        ptr(db), ptr(dx), ptr(ws), N, H, W, s.cin, s.act, s.slope, mask_act, mslope, stream()),
+                              "aesr_conv2d_cout1_bwd")
+                        _pe()
+                        g = dx
+                        continue
                 if k == len(steps) - 1 and s.act != _hip.ACT_NONE:
                     dpre = torch.empty_like(g)
                     check(lib.aesr_act_bwd(ptr(g), ptr(yout), ptr(dpre), g.numel(), s.act, s.slope, stream()), "aesr_act_bwd")
