@@ -1,4 +1,5 @@
-"""ctypes binding of libaesr_hip.so (C ABI: include/aesr_hip.h, include/aesr_hip_preproc.h, include/aesr_hip_dataprep.h and include/aesr_hip_train.h).
+"""ctypes binding of libaesr_hip.so (C ABI: include/aesr_hip.h, include/aesr_hip_preproc.h, include/aesr_hip_dataprep.h, include/aesr_hip_train.h
+and include/aesr_hip_baselines.h).
 
 There is NO fallback: if the shared library is missing or an entry point is absent this module raises at
 import time, and every wrapper raises RuntimeError with the library's own message when a call fails.
@@ -186,6 +187,17 @@ SIGNATURES_TRAIN = {
     "aesr_conv2d_cout1_bwd_workspace_floats": (c_size_t, [c_int]),
     "aesr_conv2d_cout1_bwd": (c_int, [P] * 8 + [c_int] * 5 + [c_float, c_int, c_float, P]),
 }
+# the conventional through-plane interpolation ABI (include/aesr_hip_baselines.h, same library): must list every symbol that header declares
+# (checked by tests)
+SIGNATURES_BASELINES = {
+    "aesr_z_expand_out_slices": (c_int, [c_int, c_int, c_int]),
+    "aesr_z_expand_store_bytes": (c_int, [c_int, P, P]),
+    "aesr_bspline_coef_bytes": (c_size_t, [c_int] * 4),
+    "aesr_bspline_prefilter_z": (c_int, [P, P] + [c_int] * 4 + [P]),
+    "aesr_z_expand": (c_int, [P, P, P] + [c_int] * 7 + [IP, DP, c_int, c_int, P]),
+}
+ZX_ALIGN_ITK, ZX_ALIGN_GRID, ZX_CLAMP, ZX_MIRROR = 0, 1, 0, 1
+ZX_MAX_FACTOR, ZX_MAX_TAPS = 16, 10          # ZX_MAXF, ZX_MAXT of csrc/z_expand.hip
 P2P_HANDLE_BYTES, P2P_SLOTS = 64, 32
 COMM_ID_BYTES = 128
 COMM_F32, COMM_F64, COMM_SUM, COMM_MAX = 0, 1, 0, 1
@@ -207,7 +219,7 @@ def _load():
             "superresolution_aniso_mri_amd/csrc`). The HIP extension is mandatory: there is no CPU/eager fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_PREPROC.items()) + list(SIGNATURES_DATAPREP.items())
-                                   + list(SIGNATURES_TRAIN.items())):
+                                   + list(SIGNATURES_TRAIN.items()) + list(SIGNATURES_BASELINES.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             raise RuntimeError("libaesr_hip.so does not export %s (stale build?)" % name)

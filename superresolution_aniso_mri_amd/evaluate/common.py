@@ -107,7 +107,49 @@ def create_super_volume(trainer, images, alpha_range=None, use_original=False, h
 
 
 def create_simple_interpolation(images, spacing, new_spacing_z=None, expand_factor=None, interpol_filter=None,
-                                generate_inbetween_slices=False):
-    """The conventional (Lanczos / B-spline / linear) through-plane baseline is SimpleITK's ExpandImageFilter in the reference
-    (:76-118): a comparison method, not part of the synthesis path."""
-    raise NotImplementedError("conventional interpolation baselines (SimpleITK ExpandImageFilter) are outside this build")
+                                generate_inbetween_slices=False, *, align="itk", radius=5):
+    """The conventional through-plane baselines of the reference (:74-118: SimpleITK's ExpandImageFilter along z) on the device
+    (``z_interp.z_expand``, csrc/z_expand.hip).
+
+    :param images: [z, y, x]; a numpy array or CPU tensor (-> numpy ``.array``, through the device) or a CUDA tensor (-> CUDA ``.array``)
+    :param spacing: [z, y, x]
+    :param new_spacing_z: the z spacing wanted; ``expand_factor = ceil(spacing[0] / new_spacing_z)`` when that is not given
+    :param interpol_filter: "nearest", "linear", "bspline" or "lanczos"; None is "lanczos", the reference's default
+    :param generate_inbetween_slices: the evaluation protocol (:86-110): keep every ``expand_factor``-th slice, expand those, cut to the
+        last kept slice and append the ORIGINAL slices that could not be paired -- the result has as many slices as ``images``
+    :param align: "itk" (ExpandImageFilter's grid, half a sample off the input slices) or "grid" (input slices at every f-th slot)
+    :param radius: of the Lanczos window, 3, 4 or 5
+
+    Returns a ``z_interp.ExpandedImage`` (``.array``, ``.spacing``, ``.origin``, ``GetSpacing()``, ``GetOrigin()``).  Nothing is clamped:
+    the caller clips, as create_HR_images.py:328 does."""
+    from . import z_interp
+    if new_spacing_z is None and expand_factor is None:
+        raise ValueError("create_simple_interpolation needs new_spacing_z or expand_factor")
+    method = z_interp.check_method(interpol_filter)
+    l_spacing = np.array(spacing, dtype=np.float64)
+    if l_spacing.shape != (3,):
+        raise ValueError("spacing must be [z, y, x], got %r" % (spacing,))
+    expand_factor = int(np.ceil(l_spacing[0] / new_spacing_z)) if expand_factor is None else int(expand_factor)
+    z_interp._check(expand_factor, align, radius)
+    on_device = torch.is_tensor(images) and images.is_cuda
+    if not torch.is_tensor(images):
+        images = torch.from_numpy(np.ascontiguousarray(np.asarray(images), dtype=np.float32))
+    if images.dim() != 3:
+        raise ValueError("create_simple_interpolation expects a [z, y, x] volume, got shape %s" % (tuple(images.shape),))
+    if not on_device and not torch.cuda.is_available():
+        # a RuntimeError like every "needs the GPU" of the package, of the kind that says what is missing: there is no host implementation
+        raise NotImplementedError("create_simple_interpolation needs the GPU: the interpolators are HIP kernels, there is no CPU fallback")
+    x = images.detach().to(device=images.device if on_device else "cuda", dtype=torch.float32)
+    orig = x
+    if generate_inbetween_slices:
+        x = x[::expand_factor]
+        l_spacing[0] = expand_factor * l_spacing[0]
+    new = z_interp.z_expand(x.contiguous(), expand_factor, method, align=align, radius=radius)
+    if generate_inbetween_slices:
+        last = determine_last_slice(orig.shape[0], expand_factor)
+        remain = (orig.shape[0] - 1) % expand_factor
+        new = new[:last + 1]
+        if remain > 0:
+            new = torch.cat([new, orig[-remain:]])
+    new_spacing, origin = z_interp.expanded_geometry(l_spacing, expand_factor, align)
+    return z_interp.ExpandedImage(new if on_device else new.cpu().numpy(), new_spacing, origin)

@@ -107,10 +107,21 @@ def _as_list(data_generator):
 
 
 def evaluate_interpolation_performance(trainer, myargs, data_generator, transform=None, downsample_steps=None, file_suffix=None,
-                                       patient_id=None, eval_axis=0, compute_percept_loss=False, percept_loss=None):
+                                       patient_id=None, eval_axis=0, compute_percept_loss=False, percept_loss=None, interpol_filter=None,
+                                       align="itk"):
     """evaluate/evaluate_interpolations.py:45-63 -> create_hr_images(generate_inbetween_slices=True, use_original_slice=False,
-    num_interpolations = downsample_steps - 1): result lists per volume.  ``eval_axis`` 1 / 2: the '_synth' / '_recon' lists stay empty."""
+    num_interpolations = downsample_steps - 1): result lists per volume.  ``eval_axis`` 1 / 2: the '_synth' / '_recon' lists stay empty.
+
+    ``interpol_filter`` "nearest" / "linear" / "bspline" / "lanczos" scores that conventional baseline instead of the model
+    (create_HR_images.py:319-329): ``trainer`` may be None, every ``downsample_steps``-th slice is expanded by
+    ``evaluate.common.create_simple_interpolation(expand_factor=downsample_steps, generate_inbetween_slices=True, align=align)``, clipped
+    to [0, 1] and scored by the same ``compute_metrics``.  None (the default) is the model."""
     _metrics._check_axis(eval_axis)
+    if interpol_filter is not None:
+        from . import z_interp
+        z_interp.check_method(interpol_filter)
+    elif trainer is None:
+        raise ValueError("evaluate_interpolation_performance needs a trainer unless interpol_filter names a conventional method")
     alpha_range = np.linspace(0, 1, (downsample_steps - 1) + 2, endpoint=True)[1:-1]
     keys = ("ssim", "psnr", "vif", "ssim_synth", "psnr_synth", "vif_synth", "ssim_recon", "psnr_recon", "vif_recon")
     res = {k: [] for k in keys + ("lpips", "lpips_synth", "lpips_recon")}
@@ -123,9 +134,15 @@ def evaluate_interpolation_performance(trainer, myargs, data_generator, transfor
         images = batch["image"]
         images = torch.from_numpy(np.ascontiguousarray(images)) if isinstance(images, np.ndarray) else images
         ref = batch.get("image_hr")
-        out = _common.create_super_volume(trainer, images, alpha_range=alpha_range, use_original=False,
-                                          downsample_steps=downsample_steps, generate_inbetween_slices=True)
-        m = compute_metrics(images if ref is None else ref, out["upsampled_image"], downsample_steps,
+        if interpol_filter is None:
+            new_images = _common.create_super_volume(trainer, images, alpha_range=alpha_range, use_original=False,
+                                                     downsample_steps=downsample_steps, generate_inbetween_slices=True)["upsampled_image"]
+        else:
+            spacing = batch.get("spacing")
+            new_images = _common.create_simple_interpolation(images.cuda(), np.ones(3) if spacing is None else spacing,
+                                                             expand_factor=downsample_steps, interpol_filter=interpol_filter,
+                                                             generate_inbetween_slices=True, align=align).array.clamp_(0, 1)
+        m = compute_metrics(images if ref is None else ref, new_images, downsample_steps,
                             compute_percept_loss=compute_percept_loss, percept_loss=percept_loss, eval_axis=eval_axis)
         for k in keys:
             if k in m:

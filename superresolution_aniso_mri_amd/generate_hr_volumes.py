@@ -14,7 +14,13 @@ output order [orig_0, interp_0(a_1..a_n), orig_1, ...], clamp to [0,1], new z-sp
 ``save_3d_volume(..., resample=True)`` on the way out, evaluate/create_HR_images.py:83-87): the volume is resampled in-plane to the
 training spacing (``--new_spacing``, default 1.4 x 1.4 mm) BEFORE the percentile normalisation, synthesised, and resampled back to the
 file's own in-plane spacing before it is written -- both resamplings on the device (datasets/common.py, csrc/inplane.hip), so the
-volume crosses PCIe once each way.  Without the flag nothing changes."""
+volume crosses PCIe once each way.  Without the flag nothing changes.
+
+``--method linear|bspline|lanczos|nearest`` writes a conventional through-plane baseline instead (the reference's
+``create_simple_interpolation``, evaluate/common.py:74-118): no model is loaded, the volume is expanded along z by
+``num_interpolations + 1`` on the device (evaluate/z_interp.py, csrc/z_expand.hip) with its intensities as they are, and written with the
+z spacing divided by the same factor.  ``--align itk`` (default) is SimpleITK's ExpandImageFilter grid, ``--align grid`` the layout of the
+model's output."""
 import argparse
 import os
 from pathlib import Path
@@ -175,8 +181,26 @@ def upsample_volume_resampled(trainer, vol_np, num_interpolations, spacing, new_
     return out
 
 
+def expand_volume(vol_np, num_interpolations, method, align="itk", radius=5):
+    """[z,y,x] or [t,z,y,x] numpy -> the conventional baseline ``method`` along z by ``num_interpolations + 1`` (float32 numpy, same
+    leading layout): one upload, one launch for all frames (two for bspline), one download.  Intensities are not normalised or clamped."""
+    from .evaluate import z_interp
+    if vol_np.ndim not in (3, 4):
+        raise ValueError("expected a [z,y,x] or [t,z,y,x] volume, got shape %s" % (vol_np.shape,))
+    if not torch.cuda.is_available():
+        raise RuntimeError("expand_volume needs the GPU: the HIP path has no CPU fallback")
+    x = torch.from_numpy(np.ascontiguousarray(vol_np, dtype=np.float32)).cuda()
+    return z_interp.z_expand(x, num_interpolations + 1, method, align=align, radius=radius).cpu().numpy()
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="Generate through-plane super-resolved volumes")
+    p.add_argument("--method", choices=("ae", "linear", "bspline", "lanczos", "nearest"), default="ae",
+                   help="ae: the trained model (default); otherwise a conventional interpolation along z, no --exper_dir needed")
+    p.add_argument("--align", choices=("itk", "grid"), default="itk",
+                   help="with a conventional --method: itk = SimpleITK's ExpandImageFilter grid (z * (n + 1) slices, half a sample off the "
+                        "input slices), grid = input slices at every (n + 1)-th slot ((z - 1) * (n + 1) + 1 slices)")
+    p.add_argument("--lanczos_radius", type=int, choices=(3, 4, 5), default=5, help="radius of the Lanczos window for --method lanczos")
     p.add_argument("--resample", action="store_true",
                    help="resample in-plane to --new_spacing before the synthesis and back to the file's own spacing before writing")
     p.add_argument("--new_spacing", type=float, nargs=2, default=[1.4, 1.4], metavar=("Y", "X"),
@@ -192,6 +216,12 @@ def main(argv=None):
     p.add_argument("--output_dir", type=str, default=None)
     p.add_argument("--save", action="store_true")
     args = p.parse_args(argv)
+    if args.method != "ae" and args.resample:
+        p.error("--resample belongs to --method ae: a conventional --method interpolates along z only and keeps the in-plane grid")
+    if args.method == "ae" and args.exper_dir is None:
+        p.error("--method ae needs --exper_dir")
+    if args.output_dir is None and args.exper_dir is None:
+        p.error("--output_dir is needed when there is no --exper_dir")
     from .kwatsch.get_trainer import get_trainer_dynamic
     out_dir = Path(args.output_dir if args.output_dir is not None else os.path.join(args.exper_dir, "ni0{}".format(args.num_interpolations)))
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -199,12 +229,16 @@ def main(argv=None):
     print("INFO - Found {} files to process in {}".format(len(images), args.data_input_dir))
     if args.resample and args.spacing is None and any(isinstance(img, np.ndarray) for _, img in images):
         p.error("--resample: .npy volumes carry no spacing; give their in-plane spacing with --spacing Y X")
-    trainer, _ = get_trainer_dynamic(src_path=args.exper_dir, model_nbr=args.model_nbr, model_nbr_sr=None, eval_mode=True)
+    trainer = None
+    if args.method == "ae":
+        trainer, _ = get_trainer_dynamic(src_path=args.exper_dir, model_nbr=args.model_nbr, model_nbr_sr=None, eval_mode=True)
     sitk = _sitk()
     results = []
     from . import volume_io
 
     def upsample(arr, spacing_yx):
+        if args.method != "ae":
+            return expand_volume(arr, args.num_interpolations, args.method, args.align, args.lanczos_radius)
         if not args.resample:
             return upsample_volume(trainer, arr, args.num_interpolations)
         return upsample_volume_resampled(trainer, arr, args.num_interpolations, spacing_yx, args.new_spacing, clamp_edges=args.clamp_edges)
