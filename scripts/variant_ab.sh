@@ -1,5 +1,6 @@
 #!/bin/bash
-# A/B of conv_wino_res_f32 variants (scripts/variants.py) through AESR_LIB: layer times (HIP events, best of 5 x 10 launches) and the C2 step
+# A/B of variant libraries (scripts/variants.py) through AESR_LIB: times of four resident-filter Winograd layers (HIP events, best of 5 x 10
+# launches) and the C2 / C3 step:  variant_ab.sh OUT variant...
 R=$GRAFT_REPO_ROOT
 V=$R/superresolution_aniso_mri_amd/csrc/build/variants
 OUT=$R/gpurun_out/${1:-r05_res_ab}.txt

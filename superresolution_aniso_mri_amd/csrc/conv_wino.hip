@@ -39,6 +39,7 @@
 
 #include "aesr_kernels.h"
 #include "aesr_pack_dev.h"
+#include "conv_wino_tile.h"
 
 constexpr int WN_S = 16;            // LDS floats per patch pixel: 16 channels, no padding (the DMA destination is lane-linear)
 constexpr int WN_NT = 512;          // threads per workgroup
@@ -46,20 +47,7 @@ constexpr int WN_TN = 32;           // output channels per work item (2 MFMA blo
 constexpr int WN_NB = 2;
 constexpr int WN_WFL = 16 * 4 * WN_TN * 4;      // floats of one U chunk in LDS (16 positions x 16 ci x 32 co) = 8192
 constexpr int WN_WP = WN_WFL / 4 / WN_NT;       // 16-byte weight pieces per thread and chunk = 4
-constexpr int WN_OOB = 0x70000000;              // byte offset that every buffer descriptor rejects (see conv_igemm.hip)
 constexpr int WN_PIECE_FL = WN_NT * 4;          // floats one DMA round of the workgroup fills (512 lanes x 16 B = 8 KB)
-
-// global -> LDS without registers: lane l of the wave writes 16 bytes at lds_wave_base + 16 l (lds_wave_base is wave-uniform: M0)
-__device__ __forceinline__ void wn_dma(__amdgpu_buffer_rsrc_t rs, float* lds_wave_base, int byte_off) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_wave_base, 16, byte_off, 0, 0, 0);
-}
-
-__device__ __forceinline__ f32x4 wn_ld(__amdgpu_buffer_rsrc_t rs, int byte_off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off, 0, 0));
-}
-__device__ __forceinline__ void wn_st(__amdgpu_buffer_rsrc_t rs, int byte_off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int, v), rs, byte_off, 0, 0);
-}
 
 // NPP = patch staging pieces (16 B) per thread: patch pixels * 4 <= 512 * NPP
 template <int NPP, bool MASK>
@@ -121,17 +109,14 @@ __global__ __launch_bounds__(WN_NT, 2) void conv_wino_f32(WinoArgs a) {
     if (l_item >= nitems) return;
     int goff[NPP];
 
-    // item -> (image group, region row, region column, cout tile): divisions by launch constants as multiply-high with the
-    // host's magic numbers (x / d == mulhi(x, ceil(2^32 / d)) for x * d < 2^32): a runtime integer division costs ~40 instructions
-    // and three of them sit on every item boundary, where no MFMA overlaps them
-#define WN_DIV(x, m) ((m) ? (int)__umulhi((unsigned)(x), (m)) : (int)(x))          /* m == 0: divisor 1 */
+    // item -> (image group, region row, region column, cout tile); three divisions by launch constants sit on every item boundary
 #define WN_ITEM_ORIGIN(item, n0, ty0, tx0, co0)               \
     {                                                         \
-        int reg_ = WN_DIV(item, a.m_ncot);                    \
+        int reg_ = WINO_DIV(item, a.m_ncot);                    \
         co0 = ((item) - reg_ * ncot) * WN_TN;                 \
-        const int q1_ = WN_DIV(reg_, a.m_regs_x);             \
+        const int q1_ = WINO_DIV(reg_, a.m_regs_x);             \
         const int rx_ = reg_ - q1_ * a.regs_x;                \
-        const int q2_ = WN_DIV(q1_, a.m_regs_y);              \
+        const int q2_ = WINO_DIV(q1_, a.m_regs_y);              \
         const int ry_ = q1_ - q2_ * a.regs_y;                 \
         n0 = q2_ * a.TI;                                      \
         ty0 = ry_ * a.THt;                                    \
@@ -143,12 +128,12 @@ __global__ __launch_bounds__(WN_NT, 2) void conv_wino_f32(WinoArgs a) {
         WN_ITEM_ORIGIN(item, n0_, ty0_, tx0_, co0_)                                                               \
         (void)co0_;                                                                                               \
         _Pragma("unroll") for (int j = 0; j < NPP; ++j) {                                                         \
-            int go = WN_OOB;                                                                                      \
+            int go = WINO_OOB;                                                                                      \
             if (piece[j] >= 0) {                                                                                  \
                 const int n = n0_ + (piece[j] >> 20), gy = 2 * ty0_ + ((piece[j] >> 10) & 1023) - 1;              \
                 const int gx = 2 * tx0_ + (piece[j] & 1023) - 1;                                                  \
                 const int sy = a.in_up2 ? gy >> 1 : gy, sx = a.in_up2 ? gx >> 1 : gx;                             \
-                go = (n < a.N && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) ? (((n * inH + sy) * inW + sx) * a.Cin + part4) * 4 : WN_OOB; \
+                go = (n < a.N && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) ? (((n * inH + sy) * inW + sx) * a.Cin + part4) * 4 : WINO_OOB; \
             }                                                                                                     \
             goff[j] = go;                                                                                         \
         }                                                                                                         \
@@ -156,16 +141,16 @@ __global__ __launch_bounds__(WN_NT, 2) void conv_wino_f32(WinoArgs a) {
     // byte offsets of the load state's chunk: weights of (chunk, cout tile) are one contiguous 32 KB block
 #define WN_CHUNK_OFFS(item, cc, wbase, coff)                                                             \
     const int wbase = (int)(((size_t)(cc) * ncot + ((item) % ncot)) * (WN_WFL * 4));                     \
-    const int coff = ((cc) * 16 + part4 < a.Cin) ? (cc) * 64 : WN_OOB;
+    const int coff = ((cc) * 16 + part4 < a.Cin) ? (cc) * 64 : WINO_OOB;
 
     // one chunk (16 input channels of the patch + the U block of the cout tile) global -> LDS buffer, NPP + 4 DMAs per thread
 #define WN_STAGE(item, cc, pdst, wdst)                                                                         \
     {                                                                                                          \
         WN_CHUNK_OFFS(item, cc, wbase_, coff_)                                                                 \
         _Pragma("unroll") for (int j = 0; j < WN_WP; ++j)                                                      \
-            wn_dma(rs_w, (wdst) + j * WN_PIECE_FL + wave * 256, wbase_ + (tid + WN_NT * j) * 16);              \
+            wino_dma(rs_w, (wdst) + j * WN_PIECE_FL + wave * 256, wbase_ + (tid + WN_NT * j) * 16);              \
         _Pragma("unroll") for (int j = 0; j < NPP; ++j)                                                        \
-            wn_dma(rs_in, (pdst) + j * WN_PIECE_FL + wave * 256, goff[j] + coff_);                             \
+            wino_dma(rs_in, (pdst) + j * WN_PIECE_FL + wave * 256, goff[j] + coff_);                             \
     }
     // ---- prologue: chunk 0 of the first item into buffer 0 -----------------------------------------------------
     WN_COMPUTE_GOFF(l_item)
@@ -186,8 +171,7 @@ __global__ __launch_bounds__(WN_NT, 2) void conv_wino_f32(WinoArgs a) {
     int cn0, cty0, ctx0, co0;
     WN_ITEM_ORIGIN(c_item, cn0, cty0, ctx0, co0)
     f32x4 acc[16][WN_NB];
-    const float mslope = a.mask_act == ACT_LRELU ? a.slope : (a.mask_act == ACT_RELU ? 0.f : 1.f);
-    const float nslope = a.act == ACT_LRELU ? a.slope : (a.act == ACT_RELU ? 0.f : 1.f);      // ACT_NONE / ACT_SIGMOID: identity
+    const float mslope = wino_slope(a.mask_act, a.slope), nslope = wino_slope(a.act, a.slope);
     const bool sigm = a.act == ACT_SIGMOID;
     const bool wave_active = wave * 16 < TP;           // waves whose 16 tile slots are all past the item's tiles skip the arithmetic
 
@@ -233,19 +217,11 @@ __global__ __launch_bounds__(WN_NT, 2) void conv_wino_f32(WinoArgs a) {
             f32x4 wnx[WN_NB];
 #pragma unroll
             for (int nb = 0; nb < WN_NB; ++nb) wnx[nb] = *(const f32x4*)(wb + nb * 64);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f32x4 d0 = t[0][j], d1 = t[1][j], d2 = t[2][j], d3 = t[3][j];
-                t[0][j] = aesr_sub4(d0, d2);
-                t[1][j] = d1 + d2;
-                t[2][j] = aesr_sub4(d2, d1);
-                t[3][j] = aesr_sub4(d1, d3);
-            }
+            WINO_ROW_HALF(t)
             // column half of the transform, one position ahead of the MFMAs that consume it: V[i][j] = (t[i] B)[j]
-#define WN_V(i, j) ((j) == 0 ? aesr_sub4(t[i][0], t[i][2]) : (j) == 1 ? t[i][1] + t[i][2] : (j) == 2 ? aesr_sub4(t[i][2], t[i][1]) : aesr_sub4(t[i][1], t[i][3]))
             // (taking 0 / the bias as the C operand in the first chunk of an item instead of zeroing the accumulators -- what
             // conv_wino_res.hip does -- needs a second copy of this block: 4-17 registers spilled here, where the staging maps live)
-            f32x4 vnx = WN_V(0, 0);
+            f32x4 vnx = WINO_V(t, 0, 0);
             auto positions = [&](auto I0c, auto I1c) {
 #pragma unroll
                 for (int i = decltype(I0c)::value; i < decltype(I1c)::value; ++i) {
@@ -264,7 +240,7 @@ __global__ __launch_bounds__(WN_NT, 2) void conv_wino_f32(WinoArgs a) {
                         if (xi + 1 < 16) {
 #pragma unroll
                             for (int nb = 0; nb < WN_NB; ++nb) wnx[nb] = *(const f32x4*)(wb + (xi + 1) * (4 * WN_TN * 4) + nb * 64);
-                            vnx = WN_V((xi + 1) >> 2, (xi + 1) & 3);
+                            vnx = WINO_V(t, (xi + 1) >> 2, (xi + 1) & 3);
                         }
                         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -280,7 +256,6 @@ __global__ __launch_bounds__(WN_NT, 2) void conv_wino_f32(WinoArgs a) {
             positions(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
             if (do_load && stage_late) WN_STAGE(l_item, l_cc, ldsP0 + (buf ^ 1) * PPS, ldsW0 + (buf ^ 1) * WN_WFL)
             positions(std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{});
-#undef WN_V
         }
         WN_STAMP(0)
         // OUR wait, not the compiler's: the barrier below is what makes the other waves' DMAs (buffer_load ... lds) visible, which holds
@@ -310,62 +285,7 @@ __global__ __launch_bounds__(WN_NT, 2) void conv_wino_f32(WinoArgs a) {
             const bool okt = tpix >= 0;
             const int n = cn0 + (tpix >> 20), y0 = 2 * (cty0 + ((tpix >> 10) & 1023)), x0 = 2 * (ctx0 + (tpix & 1023));
             const bool okn = okt && n < a.N;
-            int ob[2][2];
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                for (int q = 0; q < 2; ++q)
-                    ob[p][q] = (okn && y0 + p < a.H && x0 + q < a.W) ? ((n * a.H + y0 + p) * a.W + x0 + q) * a.Cout * 4 : WN_OOB;
-#pragma unroll
-            for (int nb = 0; nb < WN_NB; ++nb) {
-                const int co = co0 + nb * 16 + 4 * g;
-                const int cob = co < a.Cout ? co * 4 : WN_OOB;
-                f32x4 ys[2][2];
-                if (MASK) {
-#pragma unroll
-                    for (int p = 0; p < 2; ++p)
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) ys[p][q] = wn_ld(rs_ys, ob[p][q] + cob);
-                }
-                f32x4 P[2][4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    P[0][j] = acc[0 + j][nb] + acc[4 + j][nb] + acc[8 + j][nb];
-                    P[1][j] = aesr_sub4(aesr_sub4(acc[4 + j][nb], acc[8 + j][nb]), acc[12 + j][nb]);
-                }
-                if (a.out_sum2) {
-                    // adjoint of the nearest Upsample(x2) in front of this layer's forward: the 2x2 tile collapses to one pixel
-                    // (the sum of A^T M A over its four entries = the corner combination below); no activation, no mask
-                    const f32x4 s = aesr_sub4((P[0][0] + P[1][0]) + 2.f * (P[0][1] + P[1][1]), P[0][3] + P[1][3]);
-                    const int obs = (okn && y0 < a.H && x0 < a.W) ? ((n * outH + (y0 >> 1)) * outW + (x0 >> 1)) * a.Cout * 4 : WN_OOB;
-                    wn_st(rs_out, obs + cob, s);
-                    continue;
-                }
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    f32x4 Y[2];
-                    Y[0] = P[p][0] + P[p][1] + P[p][2];
-                    Y[1] = aesr_sub4(aesr_sub4(P[p][1], P[p][2]), P[p][3]);
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) {
-                        f32x4 o = Y[q];
-                        // none / ReLU / LeakyReLU as ONE branch-free form, max(x, x * slope) for 0 <= slope <= 1; a per-element switch on
-                        // the activation code costs a chain of uniform branches per element (~1000 instructions per item)
-                        const f32x4 os = o * nslope;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], os[e]);
-                        if (sigm) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) o[e] = 1.f / (1.f + expf(-o[e]));
-                        }
-                        if (MASK) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) o[e] *= (ys[p][q][e] > 0.f ? 1.f : mslope);
-                        }
-                        wn_st(rs_out, ob[p][q] + cob, o);
-                    }
-                }
-            }
+            WINO_STORE_TILE(WN_NB, MASK, false, okn, n, y0, x0, co0, g, 0)
         }
         WN_STAMP(2)
         c_item += G;
@@ -384,7 +304,6 @@ __global__ __launch_bounds__(WN_NT, 2) void conv_wino_f32(WinoArgs a) {
 #undef WN_CHUNK_OFFS
 #undef WN_COMPUTE_GOFF
 #undef WN_ITEM_ORIGIN
-#undef WN_DIV
 }
 
 // ---- weight transform + packing: wino_pack_elements lives in aesr_pack_dev.h (shared with prep.hip) ----

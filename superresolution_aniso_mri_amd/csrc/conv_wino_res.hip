@@ -31,51 +31,12 @@
 #include <vector>
 
 #include "aesr_kernels.h"
-
-// experiment switches (scripts/variants.py builds variant libraries with -D...; the shipped build leaves them at their defaults)
-#ifndef WR_EXP_PRIO
-#define WR_EXP_PRIO 0       // s_setprio value OUTSIDE the MFMA runs (patch wait, LDS reads, DMA issue, row transform, epilogue); 0 = never touched
-#endif
-#ifndef WR_EXP_PRIO_MFMA
-#define WR_EXP_PRIO_MFMA 0  // s_setprio value INSIDE the MFMA runs
-#endif
-#ifndef WR_EXP_STAGGER
-#define WR_EXP_STAGGER 0    // wave w starts its items w * WR_EXP_STAGGER * 64 cycles behind the prologue barrier
-#endif
-#ifndef WR_EXP_PAIR
-#define WR_EXP_PAIR 1       // 16-cout workgroups: MFMAs of two positions interleaved (a lone accumulator chain waits 40 cycles per MFMA, not 32)
-#endif
-#ifndef WR_DYN
-#define WR_DYN 0            // 1: items of a workgroup dealt to its waves through an LDS counter (measured: +1 % on the biggest layer, -1 % on small ones, step flat)
-#endif
-#ifndef WR_EXP_HALF
-#define WR_EXP_HALF 0       // 1: only waves 0..3 of a workgroup take items (one active wave per SIMD, the same code): what does the second wave buy?
-#endif
-#ifndef WR_EXP_SALU
-#define WR_EXP_SALU 0       // n > 0: n extra scalar instructions in every patch fetch (two fetches per item): does a scalar instruction cost a wave time?
-#endif
-#ifndef WR_ABL
-#define WR_ABL 0            // timing-only ablations (WRONG results): 1 epilogue without its stores, 2 epilogue stores raw accumulators (no transform / activation)
-#endif
-#ifndef WR_EXP_SPLITPRO
-#define WR_EXP_SPLITPRO 0   // prologue: start on filter chunk 0 + first patch, meet again for the rest of the filter before chunk 1
-#endif
+#include "conv_wino_tile.h"
 
 constexpr int WR_NT = 512;          // threads per workgroup: 8 independent waves, 2 per SIMD
 // TN = output channels of a workgroup: 32 (K side <= 32 channels: <= 64 KB of filter) or 16 (K side <= 64 channels: 64 KB)
 constexpr int WR_RP = 260;          // floats between patch rows: 16 pixel slots x 16 channels + 4 (shifts a row by one 16-byte bank group)
 constexpr int WR_PFL = 10 * WR_RP;  // floats of a wave's patch buffer (10 rows)
-constexpr int WR_OOB = 0x70000000;
-
-__device__ __forceinline__ void wr_dma(__amdgpu_buffer_rsrc_t rs, float* lds_wave_base, int byte_off) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_wave_base, 16, byte_off, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 wr_ld(__amdgpu_buffer_rsrc_t rs, int byte_off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off, 0, 0));
-}
-__device__ __forceinline__ void wr_st(__amdgpu_buffer_rsrc_t rs, int byte_off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int, v), rs, byte_off, 0, 0);
-}
 
 // POST: eval-mode BatchNorm (a per-channel affine behind the activation) and the AvgPool2d(2) that follows it, in the epilogue -- a lane
 // holds one 2 x 2 output tile, which IS one pooling window; an instantiation of its own, so that the training kernels' code is untouched
@@ -111,7 +72,6 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
     float* const ldsW = lds;                                        // [nchunks][16 positions][4][32][4]
     float* const ldsP = lds + nchunks * WR_WFL + wave * WR_PFL;     // this wave's patch: [10 rows][16 pixel slots][16 ch] (+ pitch)
     float* const ldsBias = lds + nchunks * WR_WFL + 8 * WR_PFL;     // [32]
-    int* const ldsNext = (int*)(ldsBias + 32);                      // the workgroup's next undealt item slot (WR_DYN)
 
     const int sh = a.in_up2 ? 1 : 0;
     const int inH = a.H >> sh, inW = a.W >> sh;                                              // stored size of the input tensor
@@ -136,12 +96,10 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
 #pragma unroll
         for (int j = 0; j < WR_WFL / 4 / WR_NT; ++j) {
             const int pc = tid + WR_NT * j;                        // 16-byte piece -> (row of TN couts x 4, piece in the row)
-            wr_dma(rs_w, ldsW + cc * WR_WFL + j * (WR_NT * 4) + wave * 256, wbase + ((pc / WR_TN) * 128 + (pc % WR_TN) * 4) * 4);
+            wino_dma(rs_w, ldsW + cc * WR_WFL + j * (WR_NT * 4) + wave * 256, wbase + ((pc / WR_TN) * 128 + (pc % WR_TN) * 4) * 4);
         }
     };
-    // (WR_EXP_SPLITPRO: only chunk 0 of the filter stands in front of the first patch; the rest is requested behind it and met at a second
-    // barrier in front of the first chunk-1 MFMAs, so the first 128 MFMAs of every wave run while 32 KB of filter are still on their way)
-    for (int cc = 0; cc < (WR_EXP_SPLITPRO ? 1 : nchunks); ++cc) filter_chunk(cc);
+    for (int cc = 0; cc < nchunks; ++cc) filter_chunk(cc);
 
     // ---- per-lane maps ----
     // DMA: lane -> pixel slot lane >> 2 of a patch row, channel quad (lane & 3) ^ ((slot >> 2) & 1)
@@ -153,46 +111,38 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
     const int offB = (2 * ty) * WR_RP + (2 * tx) * 16 + ((g ^ (((2 * tx + 2) >> 2) & 1)) << 2);  // columns j = 2, 3
     const float* wbl = ldsW + (g * WR_TN + l15) * 4;                    // + chunk * WFL + xi * 512 + nb * 64
 
-    const float mslope = a.mask_act == ACT_LRELU ? a.slope : (a.mask_act == ACT_RELU ? 0.f : 1.f);
-    const float nslope = a.act == ACT_LRELU ? a.slope : (a.act == ACT_RELU ? 0.f : 1.f);      // ACT_NONE / ACT_SIGMOID: identity
+    const float mslope = wino_slope(a.mask_act, a.slope), nslope = wino_slope(a.act, a.slope);
     const bool sigm = a.act == ACT_SIGMOID;
 
     // item k of this wave: block wgc + nwgc * (wave + 8 k) of the N x BY x BX blocks of 8 x 8 outputs (a partial last round lands on
     // wave 0 of many workgroups, not on all waves of a few)
-#define WR_DIV(x, m) ((m) ? (int)__umulhi((unsigned)(x), (m)) : (int)(x))          /* m == 0: divisor 1 */
     // XCD map: round k, XCD x = blocks [(8 k + x) * 8 nwgc, + 8 nwgc), wave w of worker s takes block w * nwgc + s of them
     // The workgroup's items in the order they are dealt: slot j -> block; wave w takes slots w, w + 8, ...  The two waves of a SIMD do NOT progress
     // alike -- the older one (waves 0..3) is served first and ran its equally long list in 74 us where waves 4..7 took 90 (stamps of 32 -> 32 @
-    // 162 x 162 x 36, profiles/r05_res_wave_exit.txt) -- but dealing the slots through an LDS counter (WR_DYN=1: a wave takes the next undealt slot
-    // when it finishes an item) bought only 1 % there and cost 1 % on small layers: the SIMD finishes items at one rate whichever wave owns them; the
-    // younger wave simply runs faster once it is alone.  Slots are monotonic in the block index, so the first slot past the end ends a wave.
+    // 162 x 162 x 36, profiles/r05_res_wave_exit.txt) -- but dealing the slots through an LDS counter (a wave takes the next undealt slot
+    // when it finishes an item: profiles/EXPERIMENTS.md) bought only 1 % there and cost 1 % on small layers: the SIMD finishes items at one
+    // rate whichever wave owns them; the younger wave simply runs faster once it is alone.  Slots are monotonic in the block index, so the
+    // first slot past the end ends a wave.
     auto item_of = [&](int j) { return xmap ? xcd * (8 * nwgc) + wgc + nwgc * (j & 7) + 64 * nwgc * (j >> 3) : wgc + nwgc * j; };
     int item = item_of(wave);
-    [[maybe_unused]] int slot = wave;
-    if (WR_EXP_HALF && wave >= 4) item = a.nblk;            // experiment: the younger wave of every SIMD stays idle
-    if (WR_DYN && tid == 0) *ldsNext = 8;                   // visible behind the prologue barrier
+    int slot = wave;
     // the patch of (item, chunk) -> this wave's LDS buffer: 10 DMAs; out-of-range rows / columns deliver zeros
     int in_n = 0, in_y0 = 0, in_x0 = 0;
     auto locate = [&](int it) {
-        in_n = WR_DIV(it, a.m_bpi);
+        in_n = WINO_DIV(it, a.m_bpi);
         const int rem = it - in_n * a.bpi;
-        const int by = WR_DIV(rem, a.m_regs_x);
+        const int by = WINO_DIV(rem, a.m_regs_x);
         in_y0 = by * 8;
         in_x0 = (rem - by * a.regs_x) * 8;
     };
     auto fetch = [&](int, int cc) {
         const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)a.in + (size_t)in_n * inimg), 0, inimg, 0x00020000);
-        if constexpr (WR_EXP_SALU > 0) {
-            int dummy_ = cc;
-            asm volatile(".rept %1\n\ts_add_u32 %0, %0, 1\n\t.endr" : "+s"(dummy_) : "i"(WR_EXP_SALU));
-            if (dummy_ == 0x7fffffff) return;
-        }
         const unsigned gx = (unsigned)(in_x0 - 1 + dpx);
-        const int off = (dpx < 10 && gx < (unsigned)a.W && cc * 16 + 4 * dq < a.Cin) ? lcd + ((in_x0 >> sh) - 1 + sh) * a.Cin * 4 + cc * 64 : WR_OOB;
+        const int off = (dpx < 10 && gx < (unsigned)a.W && cc * 16 + 4 * dq < a.Cin) ? lcd + ((in_x0 >> sh) - 1 + sh) * a.Cin * 4 + cc * 64 : WINO_OOB;
 #pragma unroll
         for (int r = 0; r < 10; ++r) {
             const int urow = ((in_y0 - 1 + r) >> sh) * inrow;           // row -1 stays -1: outside the image's resource
-            wr_dma(rs_in, ldsP + r * WR_RP, off + urow);
+            wino_dma(rs_in, ldsP + r * WR_RP, off + urow);
         }
     };
     if (item < a.nblk) {
@@ -200,30 +150,10 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
         fetch(item, 0);
     }
     WR_STAMP(1)
-    bool second_barrier = false;            // uniform over the workgroup
-    if constexpr (WR_EXP_SPLITPRO) {
-        for (int cc = 1; cc < nchunks; ++cc) filter_chunk(cc);
-        second_barrier = nchunks > 1;
-    }
     if (tid < WR_TN) ldsBias[tid] = bias_v;
-    if constexpr (WR_EXP_SPLITPRO) {
-        // all but this wave's (nchunks - 1) * WR_WFL / 4 / WR_NT youngest DMAs: chunk 0 of the filter and the first patch
-        constexpr int PER = WR_WFL / 4 / WR_NT;
-        switch (nchunks) {
-            case 1: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-            case 2: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory"); break;
-            case 3: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PER) : "memory"); break;
-            default: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * PER) : "memory"); break;
-        }
-        if (nchunks > 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // explicit: this wave's share of the filter DMAs has landed before it arrives
-    }
-    __syncthreads();            // U (chunk 0 at least) and bias are in LDS (every wave waited for its own part)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // explicit: this wave's share of the filter DMAs has landed before it arrives
+    __syncthreads();            // U and bias are in LDS (every wave waited for its own part)
     WR_STAMP(2)
-    if constexpr (WR_EXP_STAGGER > 0) {
-        for (int k = 0; k < wave; ++k) __builtin_amdgcn_s_sleep(WR_EXP_STAGGER);
-    }
 
     f32x4 acc[16][WR_NB];
     int cc = 0;
@@ -231,20 +161,8 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
     while (item < a.nblk) {
         // ---- the 4x4 input pixels of this lane's tile, 4 channels each ----
         // the DMAs of this patch are the oldest outstanding memory operations; the previous item's stores may still be in flight
-        if constexpr (WR_EXP_PRIO != WR_EXP_PRIO_MFMA) __builtin_amdgcn_s_setprio(WR_EXP_PRIO);
-        int next_slot = 0;
-        if constexpr (WR_DYN != 0) {
-            // last chunk of the item: ask for the next slot now, one lane, so that the answer returns with the patch reads below
-            if (cc + 1 == nchunks && lane == 0) next_slot = __hip_atomic_fetch_add(ldsNext, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
         if (after_stores) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * WR_NB) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if constexpr (WR_EXP_SPLITPRO) {
-            if (second_barrier && cc == 1) {        // first item only; vmcnt(0) above: this wave's share of the later filter chunks has landed
-                __syncthreads();
-                second_barrier = false;
-            }
-        }
         if constexpr (STAMP) {
             if (stamped_items == 0 && cc < 4) stamp[3 + 2 * cc] = __builtin_amdgcn_s_memrealtime();
         }
@@ -256,7 +174,7 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
         const float* wb = wbl + cc * WR_WFL;
         // PP positions per MFMA group: with ONE accumulator register set per position (16-cout workgroups) the four MFMAs of a position
         // form a dependent chain -- 40 cycles each instead of the 32 of independent ones -- so two positions are interleaved there
-        constexpr int PP = (WR_NB == 1 && WR_EXP_PAIR) ? 2 : 1;
+        constexpr int PP = (WR_NB == 1) ? 2 : 1;
         f32x4 wnx[PP][WR_NB];
 #pragma unroll
         for (int pp = 0; pp < PP; ++pp)
@@ -264,14 +182,10 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
             for (int nb = 0; nb < WR_NB; ++nb) wnx[pp][nb] = *(const f32x4*)(wb + pp * (4 * WR_TN * 4) + nb * 64);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         // the patch is in registers: request the next one (next chunk, or chunk 0 of the next item) into the same buffer
-        const int cur_item = item, cur_n = in_n, cur_y0 = in_y0, cur_x0 = in_x0;
+        const int cur_n = in_n, cur_y0 = in_y0, cur_x0 = in_x0;
         const bool last = cc + 1 == nchunks;
         if (last) {
-            if constexpr (WR_DYN != 0) {
-                slot = __builtin_amdgcn_readfirstlane(next_slot);
-            } else {
-                slot += WR_EXP_HALF ? 4 : 8;
-            }
+            slot += 8;
             item = item_of(slot);
             if (item < a.nblk) {
                 locate(item);
@@ -280,24 +194,15 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
         } else {
             fetch(item, cc + 1);
         }
-        (void)cur_item;
         // row half of the transform (B^T d)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const f32x4 d0 = t[0][j], d1 = t[1][j], d2 = t[2][j], d3 = t[3][j];
-            t[0][j] = aesr_sub4(d0, d2);
-            t[1][j] = d1 + d2;
-            t[2][j] = aesr_sub4(d2, d1);
-            t[3][j] = aesr_sub4(d1, d3);
-        }
+        WINO_ROW_HALF(t)
         // column half, one position ahead of the MFMAs that consume it: V[i][j] = (t[i] B)[j].  In the FIRST chunk of an item the
         // MFMA of each accumulator's first use takes 0 (the bias in position (1,1)) as its C operand: nothing is zeroed between items
-#define WR_V(i, j) ((j) == 0 ? aesr_sub4(t[i][0], t[i][2]) : (j) == 1 ? t[i][1] + t[i][2] : (j) == 2 ? aesr_sub4(t[i][2], t[i][1]) : aesr_sub4(t[i][1], t[i][3]))
         auto positions = [&](auto firstc) {
             constexpr bool FIRST = decltype(firstc)::value;
             f32x4 vnx[PP];
 #pragma unroll
-            for (int pp = 0; pp < PP; ++pp) vnx[pp] = WR_V(pp >> 2, pp & 3);
+            for (int pp = 0; pp < PP; ++pp) vnx[pp] = WINO_V(t, pp >> 2, pp & 3);
 #pragma unroll
             for (int grp = 0; grp < 16 / PP; ++grp) {
                 f32x4 wc[PP][WR_NB], vc[PP];
@@ -313,7 +218,7 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
                         const int xn = (grp + 1) * PP + pp;
 #pragma unroll
                         for (int nb = 0; nb < WR_NB; ++nb) wnx[pp][nb] = *(const f32x4*)(wb + xn * (4 * WR_TN * 4) + nb * 64);
-                        vnx[pp] = WR_V(xn >> 2, xn & 3);
+                        vnx[pp] = WINO_V(t, xn >> 2, xn & 3);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -331,10 +236,8 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
-        if constexpr (WR_EXP_PRIO != WR_EXP_PRIO_MFMA) __builtin_amdgcn_s_setprio(WR_EXP_PRIO_MFMA);
         if (cc == 0) positions(std::true_type{});
         else positions(std::false_type{});
-#undef WR_V
         if constexpr (STAMP) {
             if (stamped_items == 0 && cc < 4) stamp[4 + 2 * cc] = __builtin_amdgcn_s_memrealtime();
         }
@@ -347,93 +250,13 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
         // ---- item finished: output transform Y = A^T M A, activation, (data gradient) derivative mask, store ----------
         {
             const int y0 = cur_y0 + 2 * ty, x0 = cur_x0 + 2 * tx;
-            int ob[2][2];
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                for (int q = 0; q < 2; ++q)
-                    ob[p][q] = (y0 + p < a.H && x0 + q < a.W) ? ((cur_n * a.H + y0 + p) * a.W + x0 + q) * a.Cout * 4 : WR_OOB;
-#pragma unroll
-            for (int nb = 0; nb < WR_NB; ++nb) {
-                const int co = co0 + nb * 16 + 4 * g;
-                const int cob = co < a.Cout ? co * 4 : WR_OOB;
-                f32x4 ys[2][2];
-                if (MASK) {
-#pragma unroll
-                    for (int p = 0; p < 2; ++p)
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) ys[p][q] = wr_ld(rs_ys, ob[p][q] + cob);
-                }
-                f32x4 P[2][4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    P[0][j] = acc[0 + j][nb] + acc[4 + j][nb] + acc[8 + j][nb];
-                    P[1][j] = aesr_sub4(aesr_sub4(acc[4 + j][nb], acc[8 + j][nb]), acc[12 + j][nb]);
-                }
-                if (a.out_sum2) {
-                    // adjoint of the nearest Upsample(x2) in front of this layer's forward: the 2x2 tile collapses to one pixel
-                    const f32x4 s = aesr_sub4((P[0][0] + P[1][0]) + 2.f * (P[0][1] + P[1][1]), P[0][3] + P[1][3]);
-                    const int obs = (y0 < a.H && x0 < a.W) ? ((cur_n * outH + (y0 >> 1)) * outW + (x0 >> 1)) * a.Cout * 4 : WR_OOB;
-                    wr_st(rs_out, obs + cob, s);
-                    continue;
-                }
-                f32x4 psc = {1.f, 1.f, 1.f, 1.f}, psh = {0.f, 0.f, 0.f, 0.f}, prow = psh, pm = psh;      // pooled: row sums as they come (8 registers, not 16)
-                if (POST && co < a.Cout) {
-                    psc = *(const f32x4*)(a.post_scale + co);
-                    psh = *(const f32x4*)(a.post_shift + co);
-                }
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    f32x4 Y[2];
-                    Y[0] = P[p][0] + P[p][1] + P[p][2];
-                    Y[1] = aesr_sub4(aesr_sub4(P[p][1], P[p][2]), P[p][3]);
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) {
-                        f32x4 o = Y[q];
-                        // none / ReLU / LeakyReLU as ONE branch-free form: max(x, x * slope) for 0 <= slope <= 1
-                        const f32x4 os = o * nslope;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], os[e]);
-                        if (sigm) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) o[e] = 1.f / (1.f + expf(-o[e]));
-                        }
-                        if (MASK) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) o[e] *= (ys[p][q][e] > 0.f ? 1.f : mslope);
-                        }
-                        if (POST) {
-                            if (a.post_pool) prow = q == 0 ? o : prow + o;
-                            else wr_st(rs_out, ob[p][q] + cob, o * psc + psh);              // bn.hip bn_apply: v * scale + shift
-                        } else {
-#if WR_ABL == 1
-                            if (a.slope == 12345.f) wr_st(rs_out, ob[p][q] + cob, o);          // never true: the arithmetic stays, the store does not issue
-#elif WR_ABL == 2
-                            wr_st(rs_out, ob[p][q] + cob, acc[p * 2 + q][nb]);
-#else
-                            wr_st(rs_out, ob[p][q] + cob, o);
-#endif
-                        }
-                    }
-                    if (POST && a.post_pool) pm = p == 0 ? prow : pm + prow;
-                }
-                if (POST && a.post_pool) {
-                    // AvgPool2d(2) of the activated tile, then the affine: the arithmetic and order of bn.hip's bn_apply (pooling mode);
-                    // a window that sticks out of an odd image has no output (floor)
-                    const f32x4 m = pm * 0.25f;                     // ((o00 + o01) + (o10 + o11)) * 0.25
-                    const int obs = (y0 + 1 < a.H && x0 + 1 < a.W) ? ((cur_n * outH + (y0 >> 1)) * outW + (x0 >> 1)) * a.Cout * 4 : WR_OOB;
-                    wr_st(rs_out, obs + cob, m * psc + psh);
-                }
-            }
+            WINO_STORE_TILE(WR_NB, MASK, POST, true, cur_n, y0, x0, co0, g, 0)
         }
         after_stores = !MASK && !halfout;           // exactly 4 NB stores follow the next patch's DMAs
         WR_STAMP(11)
         if constexpr (STAMP) ++stamped_items;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // no DMA may still be writing this workgroup's LDS when it is released
-    if constexpr (WR_EXP_SPLITPRO) {
-        if (second_barrier) __syncthreads();        // a wave without items still owes the others its share of the filter
-    }
     if constexpr (STAMP) {
         stamp[12] = __builtin_amdgcn_s_memrealtime();
         stamp[13] = (unsigned long long)stamped_items;
@@ -444,7 +267,6 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
         }
     }
 #undef WR_STAMP
-#undef WR_DIV
 }
 
 // Output channels per workgroup.  64 K-side channels only fit with 16; with <= 32 both do, and the choice is about balance: a
@@ -458,6 +280,7 @@ static int wino_res_tn(const WinoArgs& a) {
     const double c32 = (double)((nblk * (a.CoutP / 32) + 2047) / 2048), c16 = 0.55 * (double)((nblk * (a.CoutP / 16) + 2047) / 2048);
     return c16 < c32 ? 16 : 32;
 }
+// (the 4 floats behind the bias are spare: once an item counter; kept so that a launch asks for the LDS size it was measured with)
 static size_t wino_res_lds_bytes(int CinP, int TN) { return ((size_t)(CinP >> 4) * (256 * TN) + 8 * WR_PFL + 32 + 4) * sizeof(float); }
 
 bool aesr_wino_res_ok(const WinoArgs& a) {

@@ -45,40 +45,22 @@
 #include <type_traits>
 
 #include "aesr_kernels.h"
+#include "conv_wino_tile.h"
 
 constexpr int RG_WFL = 16 * 4 * 32 * 4;     // floats of one U chunk (16 positions x 16 ci x 32 co) = 8192
 constexpr int RG_SLOTS = 3;
 constexpr int RG_LDS_MAX = 160 * 1024 - 256;      // dynamic LDS a launch may ask for: the arrival counters are static LDS of the kernel
-constexpr int RG_OOB = 0x70000000;
-#ifndef RG_SIG_POS
-#define RG_SIG_POS 4
-#endif
-constexpr int RG_SIG = RG_SIG_POS;          // the arrival of the next chunk is signalled after this many positions (of 16)
+constexpr int RG_SIG = 4;                   // the arrival of the next chunk is signalled after this many positions (of 16)
 constexpr int RG_SPIN_LIMIT = 1 << 22;      // a spin that long means a protocol bug: give up (flagged, results are garbage) instead of hanging the GPU
 
 __device__ unsigned int g_ring_timeouts = 0;
 
-__device__ __forceinline__ void rg_dma(__amdgpu_buffer_rsrc_t rs, float* lds_wave_base, int byte_off, int uniform_off = 0) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds_wave_base, 16, byte_off, uniform_off, 0, 0);
-}
 // lane id without a live register: the per-lane parts of the DMA addresses are rebuilt where they are used (the accumulators and
 // the raw tile leave ~30 registers for everything else)
 __device__ __forceinline__ int rg_lane() {
     int l;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
     return l;
-}
-__device__ __forceinline__ f32x4 rg_ld(__amdgpu_buffer_rsrc_t rs, int byte_off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off, 0, 0));
-}
-// The slab offset of a channel split is added to the per-lane offset, NOT passed as the instruction's scalar offset.  With an SGPR
-// soffset the compiler (ROCm 7.2 clang) leaves out the wait state between "buffer_store_dwordx4 v[128:131], v, s[..], sN offen" and
-// the next VALU instruction that overwrites v[128:131] -- its hazard recognizer holds that this store-data hazard "only exists if the
-// instruction is not using a register in the soffset field" -- and on gfx950 the store then picks up the NEW contents in part of its
-// lanes: odd output channels of tiles 12..15 came out wrong (scripts/diag_ring_tail.py; the ISA of the two forms differs by exactly
-// that s_nop).  With soffset = 0 the compiler inserts the wait state.
-__device__ __forceinline__ void rg_st(__amdgpu_buffer_rsrc_t rs, int byte_off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned int)))) unsigned int, v), rs, byte_off, 0, 0);
 }
 
 // PWT: pixel slots of a patch row (>= 2 TWt + 2) at compile time; rows are pitched PWT * 16 + 4 floats, so the 16 patch reads of a
@@ -140,8 +122,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino_ring_f32(WinoArgs a) {
     }
     constexpr int upw = 32 / NW;                                        // 1 KB pieces of a U chunk this wave fetches
 
-    const float mslope = a.mask_act == ACT_LRELU ? a.slope : (a.mask_act == ACT_RELU ? 0.f : 1.f);
-    const float nslope = a.act == ACT_LRELU ? a.slope : (a.act == ACT_RELU ? 0.f : 1.f);      // ACT_NONE / ACT_SIGMOID: identity
+    const float mslope = wino_slope(a.mask_act, a.slope), nslope = wino_slope(a.act, a.slope);
     const bool sigm = a.act == ACT_SIGMOID;
 
     // workgroup order: the workgroups of one XCD (blockIdx % 8 under round-robin placement: speed only) take consecutive items
@@ -149,16 +130,15 @@ __global__ __launch_bounds__(512, 2) void conv_wino_ring_f32(WinoArgs a) {
     const int xcd = blockIdx.x & 7;
     const int wg = xcd * (G >> 3) + min(xcd, G & 7) + (int)(blockIdx.x >> 3);          // XCD x owns (G - x + 7) / 8 consecutive items per round
 
-#define RG_DIV(x, m) ((m) ? (int)__umulhi((unsigned)(x), (m)) : (int)(x))          /* m == 0: divisor 1 */
     // item -> (block group, cout tile); this wave's block of the group -> (image group, block row, block column)
     // channel split: item = ((block group, split), cout tile); split s streams chunks [s kchunks, (s + 1) kchunks) of the K side into its
     // own output-shaped slab (no bias, no activation: the split-reduce kernel finishes the layer)
     int in_n0 = 0, in_ty0 = 0, in_tx0 = 0, in_co0 = 0, in_c0 = 0, in_c1 = nchunks, in_so = 0;
     bool in_active = false;
     auto locate = [&](int it) {
-        const int bgs = RG_DIV(it, a.m_ncot);
+        const int bgs = WINO_DIV(it, a.m_ncot);
         in_co0 = (it - bgs * ncot) * 32;
-        const int bg = RG_DIV(bgs, a.m_ksplit);
+        const int bg = WINO_DIV(bgs, a.m_ksplit);
         const int sp = bgs - bg * a.ksplit;
         in_c0 = sp * a.kchunks;
         in_c1 = min(in_c0 + a.kchunks, nchunks);
@@ -169,9 +149,9 @@ __global__ __launch_bounds__(512, 2) void conv_wino_ring_f32(WinoArgs a) {
         const int blk = tj < 0 ? bg * NW + wave : a.nfull * NW + tj * a.tail_k + wave;
         in_active = blk < a.nblk && (tj < 0 || wave < a.tail_k);
         const int b = in_active ? blk : 0;
-        const int ng = RG_DIV(b, a.m_bpi);
+        const int ng = WINO_DIV(b, a.m_bpi);
         const int rem = b - ng * a.bpi;
-        const int by = RG_DIV(rem, a.m_regs_x);
+        const int by = WINO_DIV(rem, a.m_regs_x);
         in_n0 = ng * a.TI;
         in_ty0 = by * a.THt;
         in_tx0 = (rem - by * a.regs_x) * a.TWt;
@@ -182,15 +162,15 @@ __global__ __launch_bounds__(512, 2) void conv_wino_ring_f32(WinoArgs a) {
         const int dq = (ln & 3) ^ ((((dpx >> a.sw_a) & a.sw_m) << a.sw_b) & 3);
         const int lcd = (((dpx - sh) >> sh) * a.Cin + 4 * dq) * 4;      // bytes from (row start + block column origin); arithmetic shift: -1 stays -1
         const unsigned gx = (unsigned)(2 * in_tx0 - 1 + dpx);
-        const int lane_off = (gx < (unsigned)a.W) ? lcd + (((2 * in_tx0) >> sh) - 1 + sh) * a.Cin * 4 + cc * 64 : RG_OOB;
+        const int lane_off = (gx < (unsigned)a.W) ? lcd + (((2 * in_tx0) >> sh) - 1 + sh) * a.Cin * 4 + cc * 64 : WINO_OOB;
         if (dpx < PW) {
             int ti = 0, pr = 0;
             const int nrows = a.TI * PH;
 #pragma unroll 2
             for (int r = 0; r < nrows; ++r) {
                 const int n = in_n0 + ti, gy = 2 * in_ty0 - 1 + pr;
-                const int urow = (n < a.N && (unsigned)gy < (unsigned)a.H) ? n * inimg + (gy >> sh) * inrow : RG_OOB;
-                rg_dma(rs_in, ldsP + ti * a.imgP + pr * rowP, lane_off + urow);
+                const int urow = (n < a.N && (unsigned)gy < (unsigned)a.H) ? n * inimg + (gy >> sh) * inrow : WINO_OOB;
+                wino_dma(rs_in, ldsP + ti * a.imgP + pr * rowP, lane_off + urow);
                 if (++pr == PH) { pr = 0; ++ti; }
             }
         }
@@ -201,7 +181,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino_ring_f32(WinoArgs a) {
         float* dst = ldsU + slot * RG_WFL + wave * upw * 256;
         const int voff = rg_lane() * 16;
 #pragma unroll
-        for (int k = 0; k < upw; ++k) rg_dma(rs_w, dst + k * 256, voff, wbase + k * 1024);
+        for (int k = 0; k < upw; ++k) wino_dma(rs_w, dst + k * 256, voff, wbase + k * 1024);
     };
     auto signal = [&](int slot, bool on) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // this wave's DMAs (U part and patch of the next chunk) have landed
@@ -284,18 +264,10 @@ __global__ __launch_bounds__(512, 2) void conv_wino_ring_f32(WinoArgs a) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             fetch_next();                           // the patch is in registers: its buffer is free
             // row half of the transform (B^T d)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f32x4 d0 = t[0][j], d1 = t[1][j], d2 = t[2][j], d3 = t[3][j];
-                t[0][j] = aesr_sub4(d0, d2);
-                t[1][j] = d1 + d2;
-                t[2][j] = aesr_sub4(d2, d1);
-                t[3][j] = aesr_sub4(d1, d3);
-            }
+            WINO_ROW_HALF(t)
             // column half, one position ahead of the MFMAs that consume it: V[i][j] = (t[i] B)[j].  In the FIRST chunk of an item the
             // MFMA of each accumulator's first use takes 0 (the bias in position (1,1)) as its C operand: nothing is zeroed between items
-#define RG_V(i, j) ((j) == 0 ? aesr_sub4(t[i][0], t[i][2]) : (j) == 1 ? t[i][1] + t[i][2] : (j) == 2 ? aesr_sub4(t[i][2], t[i][1]) : aesr_sub4(t[i][1], t[i][3]))
-            f32x4 vnx = RG_V(0, 0);
+            f32x4 vnx = WINO_V(t, 0, 0);
             auto positions = [&](auto firstc, auto X0c, auto X1c) {
                 constexpr bool FIRST = decltype(firstc)::value;
 #pragma unroll
@@ -307,7 +279,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino_ring_f32(WinoArgs a) {
                     if (xi + 1 < 16) {
 #pragma unroll
                         for (int nb = 0; nb < 2; ++nb) wnx[nb] = *(const f32x4*)(wb + (xi + 1) * 512 + nb * 64);
-                        vnx = RG_V((xi + 1) >> 2, (xi + 1) & 3);
+                        vnx = WINO_V(t, (xi + 1) >> 2, (xi + 1) & 3);
                     }
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -335,7 +307,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino_ring_f32(WinoArgs a) {
                 signal(nslot, has_next);
                 positions(std::false_type{}, XS{}, XE{});
             }
-#undef RG_V
         }
         // chunk done: the next one sits in the next slot; a slot's arrivals grow by NW every time the ring comes round
         slot = nslot;
@@ -351,83 +322,12 @@ __global__ __launch_bounds__(512, 2) void conv_wino_ring_f32(WinoArgs a) {
             const int g = rg_lane() >> 4;
             const int n = cur_n0 + (tmap >> 16), y0 = 2 * (cur_ty0 + ((tmap >> 8) & 255)), x0 = 2 * (cur_tx0 + (tmap & 255));
             const bool okn = tmap >= 0 && n < a.N;
-            int ob[2][2];
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                for (int q = 0; q < 2; ++q)
-                    ob[p][q] = (okn && y0 + p < a.H && x0 + q < a.W) ? ((n * a.H + y0 + p) * a.W + x0 + q) * a.Cout * 4 : RG_OOB;
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb) {
-                const int co = cur_co0 + nb * 16 + 4 * g;
-                const int cob = co < a.Cout ? co * 4 : RG_OOB;
-                f32x4 ys[2][2];
-                if (MASK) {
-#pragma unroll
-                    for (int p = 0; p < 2; ++p)
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) ys[p][q] = rg_ld(rs_ys, ob[p][q] + cob);
-                }
-                f32x4 P[2][4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    P[0][j] = acc[0 + j][nb] + acc[4 + j][nb] + acc[8 + j][nb];
-                    P[1][j] = aesr_sub4(aesr_sub4(acc[4 + j][nb], acc[8 + j][nb]), acc[12 + j][nb]);
-                }
-                if (a.out_sum2) {
-                    // adjoint of the nearest Upsample(x2) in front of this layer's forward: the 2x2 tile collapses to one pixel
-                    const f32x4 s = aesr_sub4((P[0][0] + P[1][0]) + 2.f * (P[0][1] + P[1][1]), P[0][3] + P[1][3]);
-                    const int obs = (okn && y0 < a.H && x0 < a.W) ? ((n * outH + (y0 >> 1)) * outW + (x0 >> 1)) * a.Cout * 4 : RG_OOB;
-                    rg_st(rs_out, obs + cob + cur_so, s);
-                    continue;
-                }
-                f32x4 psc = {1.f, 1.f, 1.f, 1.f}, psh = {0.f, 0.f, 0.f, 0.f}, prow = psh, pm = psh;      // pooled: row sums as they come (8 registers, not 16)
-                if (POST && co < a.Cout) {
-                    psc = *(const f32x4*)(a.post_scale + co);
-                    psh = *(const f32x4*)(a.post_shift + co);
-                }
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    f32x4 Y[2];
-                    Y[0] = P[p][0] + P[p][1] + P[p][2];
-                    Y[1] = aesr_sub4(aesr_sub4(P[p][1], P[p][2]), P[p][3]);
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) {
-                        f32x4 o = Y[q];
-                        // none / ReLU / LeakyReLU as ONE branch-free form: max(x, x * slope) for 0 <= slope <= 1
-                        const f32x4 os = o * nslope;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], os[e]);
-                        if (sigm) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) o[e] = 1.f / (1.f + expf(-o[e]));
-                        }
-                        if (MASK) {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) o[e] *= (ys[p][q][e] > 0.f ? 1.f : mslope);
-                        }
-                        if (POST) {
-                            if (a.post_pool) prow = q == 0 ? o : prow + o;
-                            else rg_st(rs_out, ob[p][q] + cob, o * psc + psh);              // bn.hip bn_apply: v * scale + shift
-                        } else {
-                            rg_st(rs_out, ob[p][q] + cob + cur_so, o);
-                        }
-                    }
-                    if (POST && a.post_pool) pm = p == 0 ? prow : pm + prow;
-                }
-                if (POST && a.post_pool) {
-                    // AvgPool2d(2) of the activated tile, then the affine, in bn_apply's order; an odd image's last row / column has no window
-                    const f32x4 m = pm * 0.25f;                     // ((o00 + o01) + (o10 + o11)) * 0.25
-                    const int obs = (okn && y0 + 1 < a.H && x0 + 1 < a.W) ? ((n * outH + (y0 >> 1)) * outW + (x0 >> 1)) * a.Cout * 4 : RG_OOB;
-                    rg_st(rs_out, obs + cob, m * psc + psh);
-                }
-            }
+            WINO_STORE_TILE(2, MASK, POST, okn, n, y0, x0, cur_co0, g, cur_so)
         }
         if (!has_next) break;
         after_stores = active && !MASK && !halfout;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // no DMA may still be writing this workgroup's LDS when it is released
-#undef RG_DIV
 }
 
 // ---- launcher: block shape, LDS layout, item list ----------------------------------------------------------------------------------
@@ -587,8 +487,8 @@ int aesr_wino_ring_mode() {
 static int ring_smax(const WinoArgs& a) {
     if (a.ws_floats == 0 || a.out_sum2) return 1;       // (queries pass ws_floats = SIZE_MAX without a buffer: "whatever the plan wants")
     const size_t out_floats = (size_t)a.N * a.H * a.W * a.Cout;
-    // a store's 32-bit offset is (pixel or RG_OOB) + (channel or RG_OOB) + slab offset: with BOTH sentinels set, a slab offset of
-    // 0x20000000 and more would wrap 2 RG_OOB + offset past 2^32 into a valid slab -- splits are for small layers, so larger ones get none
+    // a store's 32-bit offset is (pixel or WINO_OOB) + (channel or WINO_OOB) + slab offset: with BOTH sentinels set, a slab offset of
+    // 0x20000000 and more would wrap 2 WINO_OOB + offset past 2^32 into a valid slab -- splits are for small layers, so larger ones get none
     if (out_floats * 4 * (size_t)RG_KSPLIT_MAX >= (size_t)0x20000000) return 1;
     const RingPlan p = plan_ring(a, RG_KSPLIT_MAX);
     return (size_t)p.ksplit * out_floats <= a.ws_floats ? RG_KSPLIT_MAX : 1;
@@ -640,8 +540,7 @@ __global__ __launch_bounds__(256) void wino_split_reduce_kernel(const float* __r
                                                                 const float* __restrict__ bias, int Cout4, const float* __restrict__ ysave,
                                                                 float* __restrict__ out, int act, float slope, int mask_act) {
     const f32x4* p4 = (const f32x4*)part;
-    const float nslope = act == ACT_LRELU ? slope : (act == ACT_RELU ? 0.f : 1.f);
-    const float mslope = mask_act == ACT_LRELU ? slope : (mask_act == ACT_RELU ? 0.f : 1.f);
+    const float nslope = wino_slope(act, slope), mslope = wino_slope(mask_act, slope);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
         f32x4 v = p4[i];
         for (int s_ = 1; s_ < S; ++s_) v += p4[s_ * stride4 + i];          // fixed order: deterministic
@@ -684,7 +583,7 @@ int aesr_launch_conv_wino_ring(const WinoArgs& a_in, hipStream_t st) {
     a.kchunks = ceil_div(a.CinP / 16, p.ksplit);
     const bool halfout = a.out_sum2 || (a.post_scale && a.post_pool);
     const size_t out_floats = (size_t)a.N * (halfout ? a.H / 2 : a.H) * (halfout ? a.W / 2 : a.W) * a.Cout;
-    if (out_floats * 4 * (size_t)a.ksplit >= (size_t)(a.ksplit > 1 ? 0x20000000 : RG_OOB)) {      // split: see ring_smax
+    if (out_floats * 4 * (size_t)a.ksplit >= (size_t)(a.ksplit > 1 ? 0x20000000 : WINO_OOB)) {      // split: see ring_smax
         aesr_set_error("conv_wino_ring: %zu output bytes x %d channel splits exceed the kernel's 32-bit offsets", out_floats * 4, a.ksplit);
         return AESR_ERR_UNSUPPORTED;
     }
