@@ -1,13 +1,14 @@
 #!/usr/bin/env python
-"""Are the device listings of two source trees the same, kernel by kernel?  For refactors of the Winograd kernels, which must not move
-an instruction.
+"""Are the device listings of two source trees the same, kernel by kernel?  For refactors that must not move an instruction.
 
     python scripts/isa_same.py OLD_CSRC NEW_CSRC [file.hip ...] [-o report.txt]
 
-Compiles every file (default: the four Winograd sources) of both directories with the Makefile's flags for them plus
---cuda-device-only -S, drops comment lines, .file / .ident / .loc and the per-translation-unit __hip_cuid_ symbol, and prints per
-kernel: mangled name, sgpr / vgpr / spilled-vgpr counts of the metadata, instructions, "identical" or "DIFFERENT".  Exit status 1
-unless the whole normalised listings are equal."""
+Compiles every file (default: every entry of SRCS in either tree's Makefile) of both directories with the flags its Makefile gives that
+file plus --cuda-device-only -S, drops comment lines, .file / .ident / .loc and the per-translation-unit __hip_cuid_ symbol, and prints
+per kernel: mangled name, sgpr / vgpr / spilled-vgpr counts of the metadata, instructions, "identical" or "DIFFERENT".  A source that
+only one tree has counts as one without kernels in the other.  Kernels are compared as a set and the rest of a listing as a bag of
+lines: another order of instantiation is reported as that.  Exit status 1 unless every file has the same kernels, each identical, and
+the same lines."""
 import argparse
 import concurrent.futures
 import os
@@ -16,14 +17,24 @@ import subprocess
 import sys
 import tempfile
 
-FILES = ["conv_wino.hip", "conv_wino_res.hip", "conv_wino_ring.hip", "conv_wgrad_wino.hip"]
-FLAGS = "-O3 -fPIC -std=c++17 --offload-arch=gfx950 -Wall -Wno-unused-result -ffp-contract=off -fno-slp-vectorize".split()
+def makefile(csrc):
+    """SRCS of csrc/Makefile and a function name -> the CXXFLAGS of that file (the target-specific additions included)"""
+    text = open(os.path.join(csrc, "Makefile")).read()
+    srcs = re.search(r"^SRCS\s*=\s*(.*)$", text, re.M).group(1).split()
+    base = re.search(r"^CXXFLAGS\s*=\s*(.*)$", text, re.M).group(1).replace("$(ARCH)", "gfx950").split()
+    extra = {}
+    for objs, more in re.findall(r"^((?:build/\w+\.o\s*)+):\s*CXXFLAGS\s*\+=\s*(.*)$", text, re.M):
+        for o in objs.split():
+            extra.setdefault(os.path.basename(o)[:-2] + ".hip", []).extend(more.split())
+    return srcs, lambda name: base + extra.get(name, [])
 
 
 def listing(csrc, name, tmp):
+    if not os.path.exists(os.path.join(csrc, name)):
+        return []
     out = os.path.join(tmp, name + ".s")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    subprocess.run([hipcc, *FLAGS, "--cuda-device-only", "-S", name, "-o", out], cwd=csrc, check=True)
+    subprocess.run([hipcc, *makefile(csrc)[1](name), "--cuda-device-only", "-S", name, "-o", out], cwd=csrc, check=True)
     keep = []
     for l in open(out):
         t = l.strip()
@@ -51,9 +62,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("old")
     ap.add_argument("new")
-    ap.add_argument("files", nargs="*", default=FILES)
+    ap.add_argument("files", nargs="*")
     ap.add_argument("-o", "--out")
     args = ap.parse_args()
+    if not args.files:
+        old_srcs, new_srcs = makefile(args.old)[0], makefile(args.new)[0]
+        args.files = new_srcs + [f for f in old_srcs if f not in new_srcs]
     rows, same = [], True
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
         with concurrent.futures.ThreadPoolExecutor(8) as ex:          # the compiles run side by side
@@ -61,8 +75,13 @@ def main():
         for name, (ja, jb) in zip(args.files, jobs):
             la, lb = ja.result(), jb.result()
             ka, kb = kernels(la), kernels(lb)
-            rows.append("%s: %d kernels, whole listing %s" % (name, len(kb), "identical" if la == lb else "DIFFERENT"))
-            same &= la == lb and sorted(ka) == sorted(kb)
+            whole = "identical" if la == lb else "the same lines in another order" if sorted(la) == sorted(lb) else "DIFFERENT"
+            if la and lb:
+                rows.append("%s: %d kernels, whole listing %s" % (name, len(kb), whole))
+                same &= sorted(la) == sorted(lb) and all(k in ka and k in kb and ka[k] == kb[k] for k in set(ka) | set(kb))
+            else:
+                rows.append("%s (only in the %s tree): %d kernels" % (name, "old" if la else "new", len(ka) + len(kb)))
+                same &= not ka and not kb
             for k in sorted(set(ka) | set(kb)):
                 if k not in ka or k not in kb:
                     rows.append("  %s\n    only in the %s tree" % (k, "old" if k in ka else "new"))
@@ -73,7 +92,8 @@ def main():
                     ka[k][1]["sgpr_count"], ka[k][1]["vgpr_count"], ka[k][1]["vgpr_spill_count"])
                 rows.append("  %s\n    sgpr %s vgpr %s vgpr_spill %s instructions %d  %s" % (
                     k, f["sgpr_count"], f["vgpr_count"], f["vgpr_spill_count"], ninstr, verdict))
-    report = "device listings (hipcc %s --cuda-device-only -S), normalised, old tree against new\n" % " ".join(FLAGS) + "\n".join(rows) + "\n"
+    report = ("device listings (hipcc <the Makefile's CXXFLAGS of each file> --cuda-device-only -S), normalised, old tree against new\n" + "\n".join(rows)
+              + "\n%s\n" % ("every kernel identical" if same else "NOT the same"))
     sys.stdout.write(report)
     if args.out:
         open(args.out, "w").write(report)

@@ -1,17 +1,14 @@
-// extern "C" entry points of libaesr_hip.so (declared in include/aesr_hip.h) + the host-side tile planners.
+// extern "C" entry points of libaesr_hip.so (declared in include/aesr_hip.h); the tile planners they ask are in conv_plan.hip.
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <map>
-#include <mutex>
-#include <tuple>
-
 #include "../../include/aesr_hip.h"
 #include "../../include/aesr_hip_dataprep.h"
 #include "../../include/aesr_hip_train.h"
 #include "aesr_kernels.h"
+#include "conv_plan.h"
 
 // ---- error string ------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
@@ -22,294 +19,71 @@ void aesr_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-// ---- tile planning ------------------------------------------------------------------------------------------
-static void cout_padding(int Cout, int* CoutP, int* NB) {
-    if (Cout <= 16) { *CoutP = 16; *NB = 1; }
-    else if (Cout <= 32) { *CoutP = 32; *NB = 2; }
-    else { *CoutP = round_up(Cout, 64); *NB = 4; }
-}
-
-// Every convolution entry point and query decides FIRST, in 64 bits, whether the tensors stay inside the kernels' 32-bit element offsets (the
-// launchers refuse 0x1C000000 elements and more): the planners below do their tile arithmetic in int and must never see sizes beyond that
-// (found by the host-side sanitizer sweep of round 6, tests/test_host_sanitized.py: ceil_div(INT_MAX, 2) in plan_wino from a query).
-static bool conv_dims_ok(int N, int H, int W, int Cin, int Cout) {
-    if (N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return false;
-    if (N > (1 << 24) || H > (1 << 15) || W > (1 << 15) || Cin > (1 << 15) || Cout > (1 << 15)) return false;
-    const unsigned long long px = (unsigned long long)N * (unsigned)(H + 2) * (unsigned)(W + 2);       // <= 2^24 * 2^16 * 2^16: no overflow
-    return px * (unsigned long long)(Cin > Cout ? Cin : Cout) < 0x1C000000ull;
-}
-#define AESR_CHECK_DIMS(who, N, H, W, Cin, Cout)                                                                                            \
-    do {                                                                                                                                    \
-        if (!conv_dims_ok(N, H, W, Cin, Cout)) {                                                                                            \
-            aesr_set_error("%s: %d x %d x %d with %d -> %d channels is empty or beyond the kernels' 32-bit element offsets (469M elements)", who, N, H, \
-                           W, Cin, Cout);                                                                                                   \
-            return AESR_ERR_UNSUPPORTED;                                                                                                    \
-        }                                                                                                                                   \
-    } while (0)
-
-struct ConvPlan { int TI, TH, TW, NB, MBW, CinP, CoutP, NT, ksplit; };
-static std::mutex g_plan_mu;
-
-static std::map<std::tuple<int, int, int, int, int, int>, ConvPlan> g_conv_plans;
-
-// Pick the workgroup shape (512 threads = one workgroup per CU, or 256 = two per CU) and the output tile (TI images x TH x
-// TW) that minimise estimated MFMA time: idle M-block slots at tile edges (the network's sizes are 162, 81, 40 ...) and the
-// work-item quantisation over the CUs.
-static ConvPlan plan_conv(int N, int Ho, int Wo, int Cin, int Cout, int KS) {
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    const auto key = std::make_tuple(N, Ho, Wo, Cin, Cout, KS);
-    auto it = g_conv_plans.find(key);
-    if (it != g_conv_plans.end()) return it->second;
-    ConvPlan p;
-    cout_padding(Cout, &p.CoutP, &p.NB);
-    p.CinP = round_up(Cin, 16);
-    p.MBW = (p.NB == 4) ? 2 : 4;                     // M-blocks per wave
-    const int ncout = p.CoutP / (16 * p.NB);
-    int force_nt = 0;
-    if (const char* e = getenv("AESR_IGEMM_NT")) force_nt = atoi(e);
-    double best = 1e300;
-    p.TI = 1; p.TH = 1; p.TW = 1; p.NT = 512;
-    for (int NT = 512; NT >= 256; NT -= 256) {
-        // two 4-wave workgroups per CU measured 2-5 % slower than one 8-wave workgroup on all but the 32->32 160x160 layer
-        // (profiles/r01_igemm_nt256.txt): kept as an experiment knob, not chosen by the planner
-        (void)force_nt;
-        if (NT != 512) continue;
-        const int NW = NT / 64, wgs_per_cu = 512 / NT;
-        const int maxpix = 16 * NW * p.MBW;
-        // LDS per workgroup: patch (80 B per pixel) + the chunk's weights + bias; 6 staging pieces of 16 B per thread
-        const int lds_budget = 160 * 1024 / wgs_per_cu - (KS * KS * 4 * 16 * p.NB * 16 + p.CoutP * 4);
-        int maxpatch = lds_budget / 80;
-        if (maxpatch > NT * 6 / 4) maxpatch = NT * 6 / 4;
-        if (NT == 512 && maxpatch > 760) maxpatch = 760;
-        auto consider = [&](int TI, int TH, int TW) {
-            const int PP = TI * (TH + KS - 1) * (TW + KS - 1);
-            const int TP = TI * TH * TW;
-            if (TP > maxpix || PP > maxpatch) return;
-            const int nblk = ceil_div(TP, 16);
-            const long nwg = (long)ceil_div(N, TI) * ceil_div(Ho, TH) * ceil_div(Wo, TW) * ncout;
-            // per CU and 16-channel chunk: the MFMA time of a SIMD (2 waves x blocks x NB x taps x 4 k-steps x 32 cycles)
-            // plus the staging / barrier phases in which the matrix pipe idles (phase stamps: ~4.5k cycles with one
-            // workgroup per CU)
-            const double nch = p.CinP / 16;
-            const double per = nch * (ceil_div(nblk, NW) * 2.0 * p.NB * KS * KS * 4 * 32 + 4500.0) + 3000.0;
-            const double slots = 256.0 * wgs_per_cu;
-            const double rounds = nwg <= 8 * slots ? (double)ceil_div((int)nwg, (int)slots) : (double)nwg / slots;
-            const double t = per * rounds;
-            if (t < best * 0.999 || (t < best * 1.001 && NT == p.NT && TP > p.TI * p.TH * p.TW)) {
-                if (t < best) best = t;
-                p.TI = TI; p.TH = TH; p.TW = TW; p.NT = NT;
-            }
-        };
-        if (Ho * Wo <= maxpix && (Ho + KS - 1) * (Wo + KS - 1) <= maxpatch) {
-            for (int TI = 1; TI <= N && TI * Ho * Wo <= maxpix; ++TI) consider(TI, Ho, Wo);
-        }
-        for (int TH = 1; TH <= Ho && TH <= 64; ++TH)
-            for (int TW = 1; TW <= Wo && TW <= 64; ++TW) consider(1, TH, TW);
-    }
-    if (const char* e = getenv("AESR_IGEMM_TILE")) {          // experiments: force "TI,TH,TW"
-        int ti, th, tw;
-        if (sscanf(e, "%d,%d,%d", &ti, &th, &tw) == 3) { p.TI = ti; p.TH = th < Ho ? th : Ho; p.TW = tw < Wo ? tw : Wo; }
-    }
-    // K-split for layers whose work items under-fill the 256 persistent workgroups (VGG conv4/5 at 20x20 / 10x10): slices of
-    // the input channels become extra work items that write raw partial sums, a fix-up pass adds them (+bias, activation,
-    // mask).  Used only when the caller passes a workspace (aesr_conv2d_fwd_ws / _dgrad_ws).
-    p.ksplit = 1;
-    {
-        const long items = (long)ceil_div(N, p.TI) * ceil_div(Ho, p.TH) * ceil_div(Wo, p.TW) * ncout;
-        const int nch = p.CinP / 16, nblk = ceil_div(p.TI * p.TH * p.TW, 16);
-        const double chunk = ceil_div(nblk, 8) * 2.0 * p.NB * KS * KS * 4 * 32 + 4500.0;
-        const double out_bytes = (double)N * Ho * Wo * Cout * 4;
-        double bestt = 1e300;
-        for (int ks = 1; ks <= 4; ++ks) {
-            if (nch % ks != 0 || nch / ks < 4 || (Cout & 3)) continue;
-            if (ks > 1 && items * ks > 4 * 256) break;
-            const double rounds = (double)ceil_div((int)(items * ks), 256);
-            double t = rounds * ((nch / ks) * chunk + 3000.0);
-            if (ks > 1) t += (ks + 2) * out_bytes / 2000.0 + 12000.0;        // fix-up traffic at ~4 TB/s + a launch
-            if (t < bestt * 0.97) { bestt = t; p.ksplit = ks; }
-        }
-        if (const char* e = getenv("AESR_IGEMM_KSPLIT")) { const int k = atoi(e); if (k >= 1 && nch % k == 0) p.ksplit = k; }
-    }
-    if (getenv("AESR_PLAN_DEBUG"))
-        fprintf(stderr, "[aesr plan] conv N=%d %dx%d Cin=%d Cout=%d KS=%d -> NT=%d TI=%d TH=%d TW=%d NB=%d nblk=%d items=%ld ksplit=%d\n", N, Ho, Wo,
-                Cin, Cout, KS, p.NT, p.TI, p.TH, p.TW, p.NB, ceil_div(p.TI * p.TH * p.TW, 16),
-                (long)ceil_div(N, p.TI) * ceil_div(Ho, p.TH) * ceil_div(Wo, p.TW) * ncout, p.ksplit);
-    g_conv_plans[key] = p;
-    return p;
-}
-
-// Winograd F(2x2,3x3) work-item shape: TI images x THt x TWt tiles (<= 128 tiles = 8 waves x 16), patch within LDS (two buffers)
-// and within 5 staging pieces per thread.  Cost = work-item rounds over the 256 CUs x chunk time; a chunk costs one or two
-// wave-passes per SIMD (waves whose 16 tiles are all invalid skip the arithmetic).
-struct WinoPlan { int TI, THt, TWt, CinP, CoutP; double cost; };
-static std::map<std::tuple<int, int, int, int, int>, WinoPlan> g_wino_plans;
-
-static WinoPlan plan_wino(int N, int H, int W, int Cin, int Cout) {
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    const auto key = std::make_tuple(N, H, W, Cin, Cout);
-    auto it = g_wino_plans.find(key);
-    if (it != g_wino_plans.end()) return it->second;
-    WinoPlan p;
-    p.CinP = round_up(Cin, 16);
-    p.CoutP = round_up(Cout, 32);
-    const int Ht = ceil_div(H, 2), Wt = ceil_div(W, 2), ncot = p.CoutP / 32, nch = p.CinP / 16;
-    p.TI = 1; p.THt = 1; p.TWt = 1; p.cost = 1e300;
-    auto consider = [&](int TI, int THt, int TWt) {
-        const int TP = TI * THt * TWt, PP = TI * (2 * THt + 2) * (2 * TWt + 2);
-        if (TP > 128 || PP * 4 > 512 * 5 || aesr_wino_lds_bytes(PP) > (size_t)160 * 1024) return;
-        const long items = (long)ceil_div(N, TI) * ceil_div(Ht, THt) * ceil_div(Wt, TWt) * ncot;
-        const double passes = ceil_div(ceil_div(TP, 16), 4);
-        const double per = nch * (passes * 128 * 32.0 + 1200.0) + 2500.0;
-        const double rounds = items <= 8 * 256 ? (double)ceil_div((int)items, 256) : (double)items / 256.0;
-        const double t = per * rounds;
-        if (t < p.cost * 0.999 || (t < p.cost * 1.001 && TP > p.TI * p.THt * p.TWt)) {
-            if (t < p.cost) p.cost = t;
-            p.TI = TI; p.THt = THt; p.TWt = TWt;
-        }
-    };
-    for (int TI = 1; TI <= N && TI * Ht * Wt <= 128; ++TI) consider(TI, Ht, Wt);
-    for (int THt = 1; THt <= Ht && THt <= 64; ++THt)
-        for (int TWt = 1; TWt <= Wt && TWt <= 64; ++TWt) consider(1, THt, TWt);
-    if (const char* e = getenv("AESR_WINO_TILE")) {           // experiments: force "TI,THt,TWt"
-        int ti, th, tw;
-        if (sscanf(e, "%d,%d,%d", &ti, &th, &tw) == 3) { p.TI = ti; p.THt = th < Ht ? th : Ht; p.TWt = tw < Wt ? tw : Wt; }
-    }
-    if (getenv("AESR_PLAN_DEBUG"))
-        fprintf(stderr, "[aesr plan] wino N=%d %dx%d Cin=%d Cout=%d -> TI=%d THt=%d TWt=%d (tiles %d, patch %d px) cost %.0f\n", N, H, W, Cin, Cout,
-                p.TI, p.THt, p.TWt, p.TI * p.THt * p.TWt, p.TI * (2 * p.THt + 2) * (2 * p.TWt + 2), p.cost);
-    g_wino_plans[key] = p;
-    return p;
-}
-
-struct WgradPlan { int variant, COT, CinP, CoutP, TH, TW, S, nslab, PWS, TWS, PSX, PSD; size_t slab_floats; };
-static std::map<std::tuple<int, int, int, int, int, int>, WgradPlan> g_wgrad_plans;
-
-static int plane_stride(int n) { return round_up(n, 64) + 4; }    // = 4 (mod 64): 16 channel planes hit 16 distinct bank quads
-
-// Winograd F(2x2,3x3) weight gradient (conv_wgrad_wino.hip, variant 2): 3x3 / padding 1 with both channel counts multiples of 32.
-// One 4-wave workgroup per CU walks spatial tiles of TH x TW output pixels (TH even, TW a multiple of 8, within the register
-// prefetch slots); S splits x (ci, co) chunks ~ 256 workgroups.  AESR_WGRAD_WINO=0 keeps the direct kernels.
-static bool wgrad_wino_ok(int Cin, int Cout, int KS, int pad) {
-    static int enabled = -1;
-    if (enabled < 0) { const char* e = getenv("AESR_WGRAD_WINO"); enabled = (e && atoi(e) == 0) ? 0 : 1; }
-    return enabled && KS == 3 && pad == 1 && Cin % 32 == 0 && Cout % 32 == 0;
-}
-
-static WgradPlan plan_wgrad_wino(int N, int H, int W, int Cin, int Cout) {
-    WgradPlan p;
-    p.variant = 2;
-    p.COT = 32;
-    p.CinP = Cin;
-    p.CoutP = Cout;
-    const int nchunks = (Cin / 32) * (Cout / 32);
-    int S = 256 / nchunks;
-    if (S >= 8) S &= ~7;                       // multiple of 8: XCD-aware workgroup order
-    if (S < 1) S = 1;
-    double best = 1e300;
-    p.TH = 16; p.TW = 8; p.S = S;
-    for (int v = 0; v < 2; ++v) {
-        const int TH = v ? 8 : 16, TW = v ? 16 : 8;                 // the kernel's two tiles (aesr_wgrad_wino_tile_ok): 8 k-steps, 2 per wave
-        const int ntiles = N * ceil_div(H, TH) * ceil_div(W, TW);
-        const int s = S < ntiles ? S : ntiles;
-        // per visit: 128 MFMAs of a wave (4 096 cycles) + ~270 other instructions, which this chip does not overlap with them
-        const double t = (double)ceil_div(ntiles, s) * (4096.0 + 1300.0);
-        if (t < best) { best = t; p.TH = TH; p.TW = TW; p.S = s; }
-    }
-    if (const char* e = getenv("AESR_WGRAD_WINO_TILE")) {     // experiment knob: "TH,TW"
-        int th = 0, tw = 0;
-        if (sscanf(e, "%d,%d", &th, &tw) == 2 && aesr_wgrad_wino_tile_ok(th, tw)) {
-            p.TH = th; p.TW = tw;
-            const int ntiles = N * ceil_div(H, p.TH) * ceil_div(W, p.TW);
-            p.S = S < ntiles ? S : ntiles;
-        }
-    }
-    if (const char* e = getenv("AESR_WGRAD_WINO_S")) { const int s_ = atoi(e); if (s_ > 0) p.S = s_; }
-    // experiment knob (round-4 verdict, next 3a): cap the slab count of every layer (fewer, longer-lived workgroups; fewer slabs to sum)
-    if (const char* e = getenv("AESR_WGRAD_WINO_SMAX")) { const int s_ = atoi(e); if (s_ > 0 && p.S > s_) p.S = s_; }
-    p.PWS = round_up(p.TW + 2, 4);             // LDS row strides in pixels (conv_wgrad_wino.hip)
-    p.TWS = round_up(p.TW, 4);
-    p.PSX = p.PSD = 0;
-    p.nslab = p.S;
-    p.slab_floats = (size_t)p.nslab * 10 * p.CinP * p.CoutP;
-    if (getenv("AESR_PLAN_DEBUG"))
-        fprintf(stderr, "[plan_wgrad] wino N=%d %dx%d %d->%d: tile %dx%d S=%d tiles=%d\n", N, H, W, Cin, Cout, p.TH, p.TW, p.S,
-                N * ceil_div(H, p.TH) * ceil_div(W, p.TW));
-    return p;
-}
-
-static WgradPlan plan_wgrad(int N, int Ho, int Wo, int Cin, int Cout, int KS, int pad = -1) {
-    std::lock_guard<std::mutex> lk(g_plan_mu);
-    const bool wino = wgrad_wino_ok(Cin, Cout, KS, pad);
-    const auto key = std::make_tuple(N, Ho, Wo, Cin, Cout, wino ? -KS : KS);
-    auto it = g_wgrad_plans.find(key);
-    if (it != g_wgrad_plans.end()) return it->second;
-    if (wino) {
-        const WgradPlan pw = plan_wgrad_wino(N, Ho, Wo, Cin, Cout);
-        g_wgrad_plans[key] = pw;
-        return pw;
-    }
-    WgradPlan p;
-    p.variant = Cout > 32 ? 1 : 0;
-    p.COT = p.variant ? 64 : 32;
-    const int cibw = p.variant ? 2 : 1;
-    p.CinP = round_up(Cin, 32);
-    p.CoutP = round_up(Cout, p.COT);
-    const size_t max_lds = 52 * 1024;        // three workgroups per CU
-    const int nchunks = (p.CinP / 32) * (p.CoutP / p.COT);
-    const int S0 = round_up(768 / nchunks > 0 ? 768 / nchunks : 1, 8);      // multiple of 8: XCD-aware workgroup order
-    double best = 1e300;
-    p.TH = 1; p.TW = 8; p.S = 1;
-    for (int TW = 8; TW <= 64; TW += 8) {
-        if (TW - 8 >= Wo) break;
-        for (int TH = 1; TH <= 32 && TH <= Ho; ++TH) {
-            const int PH = TH + KS - 1, PWp = TW + KS - 1, PWS = PWp + (PWp & 1);
-            // the kernel prefetches a whole tile into registers: WG_NX / WG_ND float4 slots per thread (conv_wgrad.hip)
-            if (PH * PWp * 8 > 256 * (p.variant ? 4 : 6) || TH * TW * (p.COT / 4) > 256 * (p.variant ? 5 : 6)) break;
-            const size_t ldsb = ((size_t)32 * plane_stride(PH * PWS) + (size_t)p.COT * plane_stride(TH * TW)) * 4;
-            if (ldsb > max_lds) break;
-            const int ntiles = N * ceil_div(Ho, TH) * ceil_div(Wo, TW);
-            const int S = S0 < ntiles ? S0 : ntiles;
-            const double rounds = (double)ceil_div(ntiles, S);
-            // three workgroups share a SIMD's matrix pipe; per tile about 4.5k cycles of LDS-write phase, barriers and
-            // address work are not hidden (fitted to the phase stamps of AESR_WGRAD_DBG on the layers of the AE)
-            const double mf = 3.0 * (TH * TW / 8) * (2 * KS * KS * cibw) * 32.0;
-            const double t = rounds * (mf + 4500.0);
-            if (t < best) { best = t; p.TH = TH; p.TW = TW; p.S = S; }
-        }
-    }
-    if (const char* e = getenv("AESR_WGRAD_TILE")) {          // experiment knob: "TH,TW"
-        int th = 0, tw = 0;
-        if (sscanf(e, "%d,%d", &th, &tw) == 2 && th > 0 && tw > 0 && tw % 8 == 0) {
-            p.TH = th < Ho ? th : Ho; p.TW = tw;
-            const int ntiles = N * ceil_div(Ho, p.TH) * ceil_div(Wo, p.TW);
-            p.S = S0 < ntiles ? S0 : ntiles;
-        }
-    }
-    if (const char* e = getenv("AESR_WGRAD_S")) {             // experiment knob: splits per (ci, co) chunk
-        const int s_ = atoi(e);
-        const int ntiles = N * ceil_div(Ho, p.TH) * ceil_div(Wo, p.TW);
-        if (s_ > 0) p.S = s_ < ntiles ? s_ : ntiles;
-    }
-    p.PWS = p.TW + KS - 1 + ((p.TW + KS - 1) & 1);
-    p.TWS = p.TW;
-    p.PSX = plane_stride((p.TH + KS - 1) * p.PWS);
-    p.PSD = plane_stride(p.TH * p.TW);
-    p.nslab = p.S;
-    if (getenv("AESR_PLAN_DEBUG"))
-        fprintf(stderr, "[plan_wgrad] N=%d %dx%d %d->%d k%d: tile %dx%d S=%d tiles=%d rounds=%d lds=%zu\n", N, Ho, Wo, Cin, Cout, KS,
-                p.TH, p.TW, p.S, N * ceil_div(Ho, p.TH) * ceil_div(Wo, p.TW), ceil_div(N * ceil_div(Ho, p.TH) * ceil_div(Wo, p.TW), p.S),
-                ((size_t)32 * p.PSX + (size_t)p.COT * p.PSD) * 4);
-    p.slab_floats = (size_t)p.nslab * (KS * KS + 1) * p.CinP * p.CoutP;
-    g_wgrad_plans[key] = p;
-    return p;
-}
-
 static bool fill_groups(BnGroups* gr, int G, const int* nstart_host) {
     if (G < 1 || G > 4 || !nstart_host) return false;
     gr->G = G;
     for (int i = 0; i <= G; ++i) gr->nstart[i] = nstart_host[i];
     for (int i = G + 1; i < 5; ++i) gr->nstart[i] = nstart_host[G];
     return true;
+}
+
+// ---- what the convolution entry points share ----------------------------------------------------------------------
+// The one shape check: filter and padding legal, tensors inside the kernels' offsets (conv_dims_ok), a non-empty output.  Ho and Wo
+// are set whenever the filter is legal.  Queries answer 0 for anything but GEOM_OK; launches turn the code into their own message.
+enum { GEOM_OK = 0, GEOM_FILTER, GEOM_DIMS, GEOM_SMALL };
+static int conv_geom(int N, int H, int W, int Cin, int Cout, int KS, int pad, int* Ho, int* Wo) {
+    if ((KS != 1 && KS != 3) || pad < 0 || pad >= KS) return GEOM_FILTER;
+    *Ho = (int)((long long)H + 2 * pad - KS + 1);       // (H, W are unchecked here: no int overflow)
+    *Wo = (int)((long long)W + 2 * pad - KS + 1);
+    if (!conv_dims_ok(N, H, W, Cin, Cout)) return GEOM_DIMS;
+    return *Ho > 0 && *Wo > 0 ? GEOM_OK : GEOM_SMALL;
+}
+
+// Padded sizes and column tile of a packed filter: kin / nout are the K-side and output channel counts (swapped for the data gradient)
+struct PackGeom { int KinP, NoutP, TN; };
+static PackGeom pack_geom(int Cout, int Cin, int transpose, bool wino) {
+    const int kin = transpose ? Cout : Cin, nout = transpose ? Cin : Cout;
+    PackGeom g;
+    g.KinP = round_up(kin, 16);
+    if (wino) {
+        g.NoutP = round_up(nout, 32);
+        g.TN = 32;
+    } else {
+        int NB;
+        cout_padding(nout, &g.NoutP, &NB);
+        g.TN = 16 * NB;
+    }
+    return g;
+}
+
+// The planned part of a Winograd launch or query; pointers, activation and the folded forms are the caller's
+static WinoArgs wino_args(int N, int H, int W, int kin, int nout, const WinoPlan& p) {
+    WinoArgs a = {};
+    a.N = N; a.H = H; a.W = W; a.Cin = kin; a.CinP = p.CinP; a.Cout = nout; a.CoutP = p.CoutP;
+    a.TI = p.TI; a.THt = p.THt; a.TWt = p.TWt;
+    a.plan_cost = p.cost;
+    a.ksplit = 1;
+    return a;
+}
+
+// Job tables: chunks of the table's capacity, each zeroed, filled (fill(job, index, entry, &blocks): 0 or the refusal), given its
+// block0 offsets and launched; stops at the first error.
+template <class Table, class Job, class Fill>
+static int run_job_table(const Job* jobs, int njobs, Fill fill, int (*launch)(const Table&, hipStream_t), void* stream) {
+    const int cap = (int)(sizeof(Table().job) / sizeof(Table().job[0]));
+    for (int j0 = 0; j0 < njobs; j0 += cap) {
+        Table t;
+        memset(&t, 0, sizeof(t));
+        t.njobs = njobs - j0 < cap ? njobs - j0 : cap;
+        for (int k = 0; k < t.njobs; ++k) {
+            int blocks = 0;
+            if (int e = fill(jobs[j0 + k], j0 + k, t.job[k], &blocks)) return e;
+            t.job[k].block0 = t.nblocks;
+            t.nblocks += blocks;
+        }
+        if (int e = launch(t, (hipStream_t)stream)) return e;
+    }
+    return AESR_OK;
 }
 
 // ---- C ABI ------------------------------------------------------------------------------------------------------
@@ -319,32 +93,72 @@ int aesr_version(void) { return AESR_ABI_VERSION; }
 const char* aesr_last_error_string(void) { return g_err; }
 
 size_t aesr_conv2d_packed_floats(int Cout, int Cin, int KS, int transpose) {
-    int NP, NB;
-    const int kin = transpose ? Cout : Cin, nout = transpose ? Cin : Cout;
-    cout_padding(nout, &NP, &NB);
-    return (size_t)KS * KS * round_up(kin, 16) * NP;
+    const PackGeom g = pack_geom(Cout, Cin, transpose, false);
+    return (size_t)KS * KS * g.KinP * g.NoutP;
 }
 
 int aesr_conv2d_pack(const float* w, float* packed, int Cout, int Cin, int KS, int transpose, void* stream) {
     AESR_CHECK_ARG(w && packed && Cout > 0 && Cin > 0 && (KS == 1 || KS == 3), "aesr_conv2d_pack: bad arguments");
-    int NP, NB;
-    const int kin = transpose ? Cout : Cin, nout = transpose ? Cin : Cout;
-    cout_padding(nout, &NP, &NB);
-    return aesr_launch_pack_weights(w, packed, Cout, Cin, KS, round_up(kin, 16), NP, 16 * NB, transpose, (hipStream_t)stream);
+    const PackGeom g = pack_geom(Cout, Cin, transpose, false);
+    return aesr_launch_pack_weights(w, packed, Cout, Cin, KS, g.KinP, g.NoutP, g.TN, transpose, (hipStream_t)stream);
 }
 
+static int blocks_of(size_t threads) { return threads > (size_t)256 * 256 ? 256 : (int)((threads + 255) / 256); }
+
+int aesr_conv2d_pack_many(const aesr_pack_job* jobs_host, int njobs, void* stream) {
+    AESR_CHECK_ARG(jobs_host && njobs > 0, "aesr_conv2d_pack_many: no jobs");
+    return run_job_table<PackTable>(jobs_host, njobs, [](const aesr_pack_job& jb, int j, PackJob& o, int* blocks) -> int {
+        AESR_CHECK_ARG(jb.w && jb.packed && jb.Cout > 0 && jb.Cin > 0 && (jb.KS == 1 || jb.KS == 3), "aesr_conv2d_pack_many: bad job %d", j);
+        const PackGeom g = pack_geom(jb.Cout, jb.Cin, jb.transpose, false);
+        o.w = jb.w; o.p = jb.packed; o.Cout = jb.Cout; o.Cin = jb.Cin; o.KS = jb.KS; o.KinP = g.KinP; o.NoutP = g.NoutP; o.TN = g.TN;
+        o.transpose = jb.transpose;
+        *blocks = blocks_of(((size_t)jb.KS * jb.KS * g.KinP * g.NoutP + 3) / 4);         // 4 elements per thread
+        return AESR_OK;
+    }, aesr_launch_pack_many, stream);
+}
+
+int aesr_weight_prep_many(const aesr_prep_job* jobs_host, int njobs, void* stream) {
+    AESR_CHECK_ARG(jobs_host && njobs > 0, "aesr_weight_prep_many: no jobs");
+    return run_job_table<PrepTable>(jobs_host, njobs, [](const aesr_prep_job& jb, int j, PrepJob& o, int* blocks) -> int {
+        AESR_CHECK_ARG(jb.w && jb.out && jb.Cout > 0 && jb.Cin > 0, "aesr_weight_prep_many: bad job %d", j);
+        o.w = jb.w; o.aux0 = jb.aux0; o.aux1 = jb.aux1; o.out = jb.out; o.kind = jb.kind; o.Cout = jb.Cout; o.Cin = jb.Cin; o.KS = jb.KS;
+        o.transpose = jb.transpose;
+        size_t threads = 0;
+        if (jb.kind == AESR_PREP_PACK || jb.kind == AESR_PREP_WINO_PACK) {     // as aesr_conv2d_pack_many / aesr_conv2d_wino_pack_many
+            const bool wino = jb.kind == AESR_PREP_WINO_PACK;
+            AESR_CHECK_ARG(wino || jb.KS == 1 || jb.KS == 3, "aesr_weight_prep_many: job %d: KS=%d", j, jb.KS);
+            AESR_CHECK_ARG(!wino || jb.KS == 3, "aesr_weight_prep_many: job %d: the Winograd transform is for 3x3 filters", j);
+            const PackGeom g = pack_geom(jb.Cout, jb.Cin, jb.transpose, wino);
+            o.KinP = g.KinP; o.NoutP = g.NoutP; o.TN = g.TN;
+            threads = wino ? (size_t)g.KinP * g.NoutP : ((size_t)jb.KS * jb.KS * g.KinP * g.NoutP + 3) / 4;       // direct: 4 elements per thread
+        } else if (jb.kind == AESR_PREP_STEM_FOLD) {           // as aesr_stemconv_fold: Cout = C1, Cin = Cs, aux0 / aux1 = stem weight / bias
+            AESR_CHECK_ARG(jb.aux0, "aesr_weight_prep_many: job %d: stem fold needs the stem weight", j);
+            threads = (size_t)9 * jb.Cout;
+        } else if (jb.kind == AESR_PREP_COUT1_FLIP) {
+            threads = (size_t)9 * jb.Cin;
+        } else {
+            aesr_set_error("aesr_weight_prep_many: job %d: unknown kind %d", j, jb.kind);
+            return AESR_ERR_ARG;
+        }
+        *blocks = blocks_of(threads);
+        return AESR_OK;
+    }, aesr_launch_prep_many, stream);
+}
+
+// ---- implicit-GEMM path ----------------------------------------------------------------------------------------------
 static int run_igemm(const float* in, const float* packed, const float* bias, const float* ysave, float* out, int N, int H,
                      int W, int Cin, int Cout, int KS, int pad, int act, int mask_act, float slope, float* workspace,
                      hipStream_t st) {
-    AESR_CHECK_DIMS("aesr_conv2d (implicit GEMM)", N, H, W, Cin, Cout);
-    const int Ho = H + 2 * pad - KS + 1, Wo = W + 2 * pad - KS + 1;
-    AESR_CHECK_ARG(Ho > 0 && Wo > 0, "aesr_conv2d: the %d x %d input is smaller than the %d x %d filter", H, W, KS, KS);
+    int Ho, Wo;
+    const int g = conv_geom(N, H, W, Cin, Cout, KS, pad, &Ho, &Wo);
+    if (g == GEOM_DIMS) AESR_CHECK_DIMS("aesr_conv2d (implicit GEMM)", N, H, W, Cin, Cout);
+    AESR_CHECK_ARG(g == GEOM_OK, "aesr_conv2d: the %d x %d input is smaller than the %d x %d filter", H, W, KS, KS);
     const ConvPlan p = plan_conv(N, Ho, Wo, Cin, Cout, KS);
-    IgemmArgs a;
+    IgemmArgs a = {};
     a.in = in; a.wpk = packed; a.bias = bias; a.ysave = ysave; a.out = out;
     a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.CinP = p.CinP; a.Cout = Cout; a.CoutP = p.CoutP; a.Ho = Ho; a.Wo = Wo; a.pad = pad;
     a.TI = p.TI; a.TH = p.TH; a.TW = p.TW; a.tiles_y = ceil_div(Ho, p.TH); a.tiles_x = ceil_div(Wo, p.TW);
-    a.act = act; a.mask_act = mask_act; a.slope = slope; a.dbgbuf = nullptr; a.NT = p.NT; a.ksplit = 1;
+    a.act = act; a.mask_act = mask_act; a.slope = slope; a.ksplit = 1;
     if (workspace && p.ksplit > 1) {
         // raw partial sums of the k slices -> workspace, then the fix-up pass (bias, activation, derivative mask)
         a.ksplit = p.ksplit; a.out = workspace; a.bias = nullptr; a.ysave = nullptr; a.act = ACT_NONE; a.mask_act = ACT_NONE;
@@ -355,128 +169,50 @@ static int run_igemm(const float* in, const float* packed, const float* bias, co
     return aesr_launch_conv_igemm(a, KS, p.NB, p.MBW, st);
 }
 
-int aesr_conv2d_pack_many(const aesr_pack_job* jobs_host, int njobs, void* stream) {
-    AESR_CHECK_ARG(jobs_host && njobs > 0, "aesr_conv2d_pack_many: no jobs");
-    for (int j0 = 0; j0 < njobs; j0 += PACK_MAX_JOBS) {
-        PackTable t;
-        memset(&t, 0, sizeof(t));
-        t.njobs = njobs - j0 < PACK_MAX_JOBS ? njobs - j0 : PACK_MAX_JOBS;
-        int nb = 0;
-        for (int k = 0; k < t.njobs; ++k) {
-            const aesr_pack_job& jb = jobs_host[j0 + k];
-            AESR_CHECK_ARG(jb.w && jb.packed && jb.Cout > 0 && jb.Cin > 0 && (jb.KS == 1 || jb.KS == 3),
-                           "aesr_conv2d_pack_many: bad job %d", j0 + k);
-            int NP, NB;
-            const int kin = jb.transpose ? jb.Cout : jb.Cin, nout = jb.transpose ? jb.Cin : jb.Cout;
-            cout_padding(nout, &NP, &NB);
-            PackJob& o = t.job[k];
-            o.w = jb.w; o.p = jb.packed; o.Cout = jb.Cout; o.Cin = jb.Cin; o.KS = jb.KS; o.KinP = round_up(kin, 16); o.NoutP = NP;
-            o.TN = 16 * NB; o.transpose = jb.transpose; o.block0 = nb;
-            const size_t total = (size_t)jb.KS * jb.KS * o.KinP * NP;
-            int blocks = (int)((total + 1023) / 1024);         // 4 elements per thread
-            if (blocks > 256) blocks = 256;
-            nb += blocks;
-        }
-        t.nblocks = nb;
-        if (int e = aesr_launch_pack_many(t, (hipStream_t)stream)) return e;
-    }
-    return AESR_OK;
+// forward (in = x, aux = bias) or data gradient (in = dy [N,Ho,Wo,Cout], packed = the flipped filter, aux = the saved x for the derivative
+// mask): dx = conv(dy, flipped w) with Cout and Cin swapped and padding KS-1-pad -> [N,H,W,Cin]
+static int igemm_entry(const char* who, bool dgrad, const float* in, const float* packed, const float* aux, float* out, float* workspace,
+                       int N, int H, int W, int Cin, int Cout, int KS, int pad, int act, float slope, void* stream) {
+    AESR_CHECK_ARG(in && packed && out && N > 0 && H > 0 && W > 0, "%s: null pointer or empty shape", who);
+    AESR_CHECK_ARG((dgrad ? Cout : Cin) % 4 == 0 && Cin > 0 && Cout > 0, "%s: %s=%d must be a positive multiple of 4", who, dgrad ? "Cout" : "Cin",
+                   dgrad ? Cout : Cin);
+    int Ho, Wo;
+    AESR_CHECK_ARG(conv_geom(N, H, W, Cin, Cout, KS, pad, &Ho, &Wo) != GEOM_FILTER, "%s: unsupported KS=%d pad=%d", who, KS, pad);
+    if (dgrad) return run_igemm(in, packed, nullptr, aux, out, N, Ho, Wo, Cout, Cin, KS, KS - 1 - pad, ACT_NONE, act, slope, workspace, (hipStream_t)stream);
+    return run_igemm(in, packed, aux, nullptr, out, N, H, W, Cin, Cout, KS, pad, act, ACT_NONE, slope, workspace, (hipStream_t)stream);
 }
 
-int aesr_weight_prep_many(const aesr_prep_job* jobs_host, int njobs, void* stream) {
-    AESR_CHECK_ARG(jobs_host && njobs > 0, "aesr_weight_prep_many: no jobs");
-    for (int j0 = 0; j0 < njobs; j0 += PACK_MAX_JOBS) {
-        PrepTable t;
-        memset(&t, 0, sizeof(t));
-        t.njobs = njobs - j0 < PACK_MAX_JOBS ? njobs - j0 : PACK_MAX_JOBS;
-        int nb = 0;
-        for (int k = 0; k < t.njobs; ++k) {
-            const aesr_prep_job& jb = jobs_host[j0 + k];
-            AESR_CHECK_ARG(jb.w && jb.out && jb.Cout > 0 && jb.Cin > 0, "aesr_weight_prep_many: bad job %d", j0 + k);
-            PrepJob& o = t.job[k];
-            o.w = jb.w; o.aux0 = jb.aux0; o.aux1 = jb.aux1; o.out = jb.out; o.kind = jb.kind; o.Cout = jb.Cout; o.Cin = jb.Cin; o.KS = jb.KS;
-            o.transpose = jb.transpose; o.block0 = nb;
-            const int kin = jb.transpose ? jb.Cout : jb.Cin, nout = jb.transpose ? jb.Cin : jb.Cout;
-            size_t threads = 0;
-            if (jb.kind == AESR_PREP_PACK) {                       // as aesr_conv2d_pack_many
-                AESR_CHECK_ARG(jb.KS == 1 || jb.KS == 3, "aesr_weight_prep_many: job %d: KS=%d", j0 + k, jb.KS);
-                int NP, NB;
-                cout_padding(nout, &NP, &NB);
-                o.KinP = round_up(kin, 16); o.NoutP = NP; o.TN = 16 * NB;
-                threads = ((size_t)jb.KS * jb.KS * o.KinP * NP + 3) / 4;            // 4 elements per thread
-            } else if (jb.kind == AESR_PREP_WINO_PACK) {           // as aesr_conv2d_wino_pack_many
-                AESR_CHECK_ARG(jb.KS == 3, "aesr_weight_prep_many: job %d: the Winograd transform is for 3x3 filters", j0 + k);
-                o.KinP = round_up(kin, 16); o.NoutP = round_up(nout, 32); o.TN = 32;
-                threads = (size_t)o.KinP * o.NoutP;
-            } else if (jb.kind == AESR_PREP_STEM_FOLD) {           // as aesr_stemconv_fold: Cout = C1, Cin = Cs, aux0 / aux1 = stem weight / bias
-                AESR_CHECK_ARG(jb.aux0, "aesr_weight_prep_many: job %d: stem fold needs the stem weight", j0 + k);
-                threads = (size_t)9 * jb.Cout;
-            } else if (jb.kind == AESR_PREP_COUT1_FLIP) {
-                threads = (size_t)9 * jb.Cin;
-            } else {
-                aesr_set_error("aesr_weight_prep_many: job %d: unknown kind %d", j0 + k, jb.kind);
-                return AESR_ERR_ARG;
-            }
-            int blocks = (int)((threads + 255) / 256);
-            if (blocks > 256) blocks = 256;
-            nb += blocks;
-        }
-        t.nblocks = nb;
-        if (int e = aesr_launch_prep_many(t, (hipStream_t)stream)) return e;
-    }
-    return AESR_OK;
+int aesr_conv2d_fwd_ws(const float* in, const float* packed, const float* bias, float* out, float* workspace, int N, int H, int W,
+                       int Cin, int Cout, int KS, int pad, int act, float slope, void* stream) {
+    return igemm_entry("aesr_conv2d_fwd_ws", false, in, packed, bias, out, workspace, N, H, W, Cin, Cout, KS, pad, act, slope, stream);
 }
 
 int aesr_conv2d_fwd(const float* in, const float* packed, const float* bias, float* out, int N, int H, int W, int Cin,
                     int Cout, int KS, int pad, int act, float slope, void* stream) {
-    AESR_CHECK_ARG(in && packed && out && N > 0 && H > 0 && W > 0, "aesr_conv2d_fwd: null pointer or empty shape");
-    AESR_CHECK_ARG(Cin % 4 == 0 && Cin > 0 && Cout > 0, "aesr_conv2d_fwd: Cin=%d must be a positive multiple of 4", Cin);
-    AESR_CHECK_ARG((KS == 1 || KS == 3) && pad >= 0 && pad < KS, "aesr_conv2d_fwd: unsupported KS=%d pad=%d", KS, pad);
-    return run_igemm(in, packed, bias, nullptr, out, N, H, W, Cin, Cout, KS, pad, act, ACT_NONE, slope, nullptr, (hipStream_t)stream);
+    return igemm_entry("aesr_conv2d_fwd", false, in, packed, bias, out, nullptr, N, H, W, Cin, Cout, KS, pad, act, slope, stream);
+}
+
+int aesr_conv2d_dgrad_ws(const float* dy, const float* packed_t, const float* x_saved, float* dx, float* workspace, int N, int H,
+                         int W, int Cin, int Cout, int KS, int pad, int mask_act, float slope, void* stream) {
+    return igemm_entry("aesr_conv2d_dgrad_ws", true, dy, packed_t, x_saved, dx, workspace, N, H, W, Cin, Cout, KS, pad, mask_act, slope, stream);
+}
+
+int aesr_conv2d_dgrad(const float* dy, const float* packed_t, const float* x_saved, float* dx, int N, int H, int W, int Cin,
+                      int Cout, int KS, int pad, int mask_act, float slope, void* stream) {
+    return igemm_entry("aesr_conv2d_dgrad", true, dy, packed_t, x_saved, dx, nullptr, N, H, W, Cin, Cout, KS, pad, mask_act, slope, stream);
 }
 
 size_t aesr_conv2d_workspace_floats(int N, int H, int W, int Cin, int Cout, int KS, int pad) {
-    if (!conv_dims_ok(N, H, W, Cin, Cout) || (KS != 1 && KS != 3) || pad < 0 || pad >= KS) return 0;
-    const int Ho = H + 2 * pad - KS + 1, Wo = W + 2 * pad - KS + 1;
-    if (Ho <= 0 || Wo <= 0) return 0;
+    int Ho, Wo;
+    if (conv_geom(N, H, W, Cin, Cout, KS, pad, &Ho, &Wo) != GEOM_OK) return 0;
     const ConvPlan p = plan_conv(N, Ho, Wo, Cin, Cout, KS);
     return p.ksplit > 1 ? (size_t)p.ksplit * N * Ho * Wo * Cout : 0;
 }
 
 size_t aesr_conv2d_dgrad_workspace_floats(int N, int H, int W, int Cin, int Cout, int KS, int pad) {
-    // the data gradient is the forward kernel on dy [N,Ho,Wo,Cout] with Cout and Cin swapped and padding KS-1-pad
-    if (!conv_dims_ok(N, H, W, Cin, Cout) || (KS != 1 && KS != 3) || pad < 0 || pad >= KS) return 0;
-    const int Ho = H + 2 * pad - KS + 1, Wo = W + 2 * pad - KS + 1;
-    return aesr_conv2d_workspace_floats(N, Ho, Wo, Cout, Cin, KS, KS - 1 - pad);
-}
-
-int aesr_conv2d_fwd_ws(const float* in, const float* packed, const float* bias, float* out, float* workspace, int N, int H, int W,
-                       int Cin, int Cout, int KS, int pad, int act, float slope, void* stream) {
-    AESR_CHECK_ARG(in && packed && out && N > 0 && H > 0 && W > 0, "aesr_conv2d_fwd_ws: null pointer or empty shape");
-    AESR_CHECK_ARG(Cin % 4 == 0 && Cin > 0 && Cout > 0, "aesr_conv2d_fwd_ws: Cin=%d must be a positive multiple of 4", Cin);
-    AESR_CHECK_ARG((KS == 1 || KS == 3) && pad >= 0 && pad < KS, "aesr_conv2d_fwd_ws: unsupported KS=%d pad=%d", KS, pad);
-    return run_igemm(in, packed, bias, nullptr, out, N, H, W, Cin, Cout, KS, pad, act, ACT_NONE, slope, workspace, (hipStream_t)stream);
-}
-
-int aesr_conv2d_dgrad_ws(const float* dy, const float* packed_t, const float* x_saved, float* dx, float* workspace, int N, int H,
-                         int W, int Cin, int Cout, int KS, int pad, int mask_act, float slope, void* stream) {
-    AESR_CHECK_ARG(dy && packed_t && dx && N > 0 && H > 0 && W > 0, "aesr_conv2d_dgrad_ws: null pointer or empty shape");
-    AESR_CHECK_ARG(Cout % 4 == 0 && Cin > 0 && Cout > 0, "aesr_conv2d_dgrad_ws: Cout=%d must be a positive multiple of 4", Cout);
-    AESR_CHECK_ARG((KS == 1 || KS == 3) && pad >= 0 && pad < KS, "aesr_conv2d_dgrad_ws: unsupported KS=%d pad=%d", KS, pad);
-    const int Ho = H + 2 * pad - KS + 1, Wo = W + 2 * pad - KS + 1;
-    return run_igemm(dy, packed_t, nullptr, x_saved, dx, N, Ho, Wo, Cout, Cin, KS, KS - 1 - pad, ACT_NONE, mask_act, slope, workspace,
-                     (hipStream_t)stream);
-}
-
-int aesr_conv2d_dgrad(const float* dy, const float* packed_t, const float* x_saved, float* dx, int N, int H, int W, int Cin,
-                      int Cout, int KS, int pad, int mask_act, float slope, void* stream) {
-    AESR_CHECK_ARG(dy && packed_t && dx && N > 0 && H > 0 && W > 0, "aesr_conv2d_dgrad: null pointer or empty shape");
-    AESR_CHECK_ARG(Cout % 4 == 0 && Cin > 0 && Cout > 0, "aesr_conv2d_dgrad: Cout=%d must be a positive multiple of 4", Cout);
-    AESR_CHECK_ARG((KS == 1 || KS == 3) && pad >= 0 && pad < KS, "aesr_conv2d_dgrad: unsupported KS=%d pad=%d", KS, pad);
-    const int Ho = H + 2 * pad - KS + 1, Wo = W + 2 * pad - KS + 1;
-    // dx = conv(dy [N,Ho,Wo,Cout], flipped w) with padding KS-1-pad -> output [N,H,W,Cin]
-    return run_igemm(dy, packed_t, nullptr, x_saved, dx, N, Ho, Wo, Cout, Cin, KS, KS - 1 - pad, ACT_NONE, mask_act, slope, nullptr,
-                     (hipStream_t)stream);
+    int Ho, Wo;
+    if (conv_geom(N, H, W, Cin, Cout, KS, pad, &Ho, &Wo) != GEOM_OK) return 0;
+    return aesr_conv2d_workspace_floats(N, Ho, Wo, Cout, Cin, KS, KS - 1 - pad);        // the forward kernel on dy, as igemm_entry runs it
 }
 
 // ---- Winograd F(2x2,3x3) path --------------------------------------------------------------------------------------
@@ -485,29 +221,25 @@ int aesr_conv2d_wino_supported(int Cin, int Cout, int KS, int pad, int transpose
     return KS == 3 && pad == 1 && kin > 0 && nout > 0 && kin % 16 == 0 && nout % 32 == 0;
 }
 
-int aesr_conv2d_wino_kernel(int N, int H, int W, int Cin, int Cout, int KS, int pad, int transpose) {
-    if (!aesr_conv2d_wino_supported(Cin, Cout, KS, pad, transpose) || !conv_dims_ok(N, H, W, Cin, Cout)) return 0;
+// a query's arguments: false where the layer is no Winograd layer or beyond the kernels' offsets
+static bool wino_query(int N, int H, int W, int Cin, int Cout, int KS, int pad, int transpose, WinoArgs* a) {
+    if (!aesr_conv2d_wino_supported(Cin, Cout, KS, pad, transpose) || !conv_dims_ok(N, H, W, Cin, Cout)) return false;
     const int kin = transpose ? Cout : Cin, nout = transpose ? Cin : Cout;
-    const WinoPlan p = plan_wino(N, H, W, kin, nout);
-    WinoArgs a = {};
-    a.N = N; a.H = H; a.W = W; a.Cin = kin; a.Cout = nout;
-    a.CinP = p.CinP; a.CoutP = p.CoutP;
-    a.plan_cost = p.cost;
+    *a = wino_args(N, H, W, kin, nout, plan_wino(N, H, W, kin, nout));
+    return true;
+}
+
+int aesr_conv2d_wino_kernel(int N, int H, int W, int Cin, int Cout, int KS, int pad, int transpose) {
+    WinoArgs a;
+    if (!wino_query(N, H, W, Cin, Cout, KS, pad, transpose, &a)) return 0;
     if (aesr_wino_res_ok(a)) return 2;
-    a.ws = nullptr;                     // a query: as called with the workspace aesr_conv2d_wino_workspace_floats asks for
-    a.ws_floats = ~(size_t)0;
+    a.ws_floats = ~(size_t)0;           // a query: as called with the workspace aesr_conv2d_wino_workspace_floats asks for
     return aesr_wino_ring_takes(a) ? 3 : 1;
 }
 
 size_t aesr_conv2d_wino_workspace_floats(int N, int H, int W, int Cin, int Cout, int transpose) {
-    if (!aesr_conv2d_wino_supported(Cin, Cout, 3, 1, transpose) || !conv_dims_ok(N, H, W, Cin, Cout)) return 0;
-    const int kin = transpose ? Cout : Cin, nout = transpose ? Cin : Cout;
-    const WinoPlan p = plan_wino(N, H, W, kin, nout);
-    WinoArgs a = {};
-    a.N = N; a.H = H; a.W = W; a.Cin = kin; a.Cout = nout;
-    a.CinP = p.CinP; a.CoutP = p.CoutP;
-    a.plan_cost = p.cost;
-    if (aesr_wino_res_ok(a)) return 0;
+    WinoArgs a;
+    if (!wino_query(N, H, W, Cin, Cout, 3, 1, transpose, &a) || aesr_wino_res_ok(a)) return 0;
     return aesr_wino_ring_workspace_floats(a);
 }
 
@@ -517,48 +249,30 @@ unsigned int aesr_conv2d_wino_ring_timeouts(void) {
 }
 
 size_t aesr_conv2d_wino_packed_floats(int Cout, int Cin, int transpose) {
-    const int kin = transpose ? Cout : Cin, nout = transpose ? Cin : Cout;
-    return (size_t)16 * round_up(kin, 16) * round_up(nout, 32);
+    const PackGeom g = pack_geom(Cout, Cin, transpose, true);
+    return (size_t)16 * g.KinP * g.NoutP;
 }
 
 int aesr_conv2d_wino_pack_many(const aesr_pack_job* jobs_host, int njobs, void* stream) {
     AESR_CHECK_ARG(jobs_host && njobs > 0, "aesr_conv2d_wino_pack_many: no jobs");
-    for (int j0 = 0; j0 < njobs; j0 += PACK_MAX_JOBS) {
-        PackTable t;
-        memset(&t, 0, sizeof(t));
-        t.njobs = njobs - j0 < PACK_MAX_JOBS ? njobs - j0 : PACK_MAX_JOBS;
-        int nb = 0;
-        for (int k = 0; k < t.njobs; ++k) {
-            const aesr_pack_job& jb = jobs_host[j0 + k];
-            AESR_CHECK_ARG(jb.w && jb.packed && jb.Cout > 0 && jb.Cin > 0 && jb.KS == 3, "aesr_conv2d_wino_pack_many: bad job %d", j0 + k);
-            const int kin = jb.transpose ? jb.Cout : jb.Cin, nout = jb.transpose ? jb.Cin : jb.Cout;
-            PackJob& o = t.job[k];
-            o.w = jb.w; o.p = jb.packed; o.Cout = jb.Cout; o.Cin = jb.Cin; o.KS = 3; o.KinP = round_up(kin, 16); o.NoutP = round_up(nout, 32);
-            o.TN = 32; o.transpose = jb.transpose; o.block0 = nb;
-            const size_t pairs = (size_t)o.KinP * o.NoutP;
-            int blocks = (int)((pairs + 255) / 256);
-            if (blocks > 256) blocks = 256;
-            nb += blocks;
-        }
-        t.nblocks = nb;
-        if (int e = aesr_launch_wino_pack_many(t, (hipStream_t)stream)) return e;
-    }
-    return AESR_OK;
+    return run_job_table<PackTable>(jobs_host, njobs, [](const aesr_pack_job& jb, int j, PackJob& o, int* blocks) -> int {
+        AESR_CHECK_ARG(jb.w && jb.packed && jb.Cout > 0 && jb.Cin > 0 && jb.KS == 3, "aesr_conv2d_wino_pack_many: bad job %d", j);
+        const PackGeom g = pack_geom(jb.Cout, jb.Cin, jb.transpose, true);
+        o.w = jb.w; o.p = jb.packed; o.Cout = jb.Cout; o.Cin = jb.Cin; o.KS = 3; o.KinP = g.KinP; o.NoutP = g.NoutP; o.TN = g.TN;
+        o.transpose = jb.transpose;
+        *blocks = blocks_of((size_t)g.KinP * g.NoutP);
+        return AESR_OK;
+    }, aesr_launch_wino_pack_many, stream);
 }
 
 static int run_wino(const float* in, const float* upk, const float* bias, const float* ysave, float* out, int N, int H, int W,
                     int Cin, int Cout, int act, int mask_act, float slope, hipStream_t st, int in_up2 = 0, int out_sum2 = 0,
                     float* ws = nullptr, size_t ws_floats = 0) {
     AESR_CHECK_DIMS("aesr_conv2d_wino", N, H, W, Cin, Cout);
-    const WinoPlan p = plan_wino(N, H, W, Cin, Cout);
-    WinoArgs a = {};
+    WinoArgs a = wino_args(N, H, W, Cin, Cout, plan_wino(N, H, W, Cin, Cout));
     a.in = in; a.upk = upk; a.bias = bias; a.ysave = ysave; a.out = out;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.CinP = p.CinP; a.Cout = Cout; a.CoutP = p.CoutP;
-    a.TI = p.TI; a.THt = p.THt; a.TWt = p.TWt; a.regs_y = a.regs_x = a.nitems = 0;
-    a.plan_cost = p.cost;
-    a.act = act; a.mask_act = mask_act; a.slope = slope; a.dbgbuf = nullptr; a.flags = 0; a.in_up2 = in_up2; a.out_sum2 = out_sum2;
+    a.act = act; a.mask_act = mask_act; a.slope = slope; a.in_up2 = in_up2; a.out_sum2 = out_sum2;
     a.ws = ws_floats ? ws : nullptr; a.ws_floats = ws ? ws_floats : 0;
-    a.ksplit = 1;
     return aesr_launch_conv_wino(a, st);
 }
 
@@ -594,14 +308,9 @@ int aesr_conv2d_wino_dgrad_ws(const float* dy, const float* upacked_t, const flo
 /* conv + activation + eval-mode BatchNorm (per-channel scale / shift) [+ AvgPool2d(2)] as one launch: the resident-filter kernel, and the
    ring kernel where it takes the layer WITHOUT a workspace (no channel split: the epilogue has to see the finished sums) */
 int aesr_conv2d_wino_fwd_bn_supported(int N, int H, int W, int Cin, int Cout) {
-    if (!aesr_conv2d_wino_supported(Cin, Cout, 3, 1, 0) || !conv_dims_ok(N, H, W, Cin, Cout)) return 0;
-    const WinoPlan p = plan_wino(N, H, W, Cin, Cout);
-    WinoArgs a = {};
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-    a.CinP = p.CinP; a.CoutP = p.CoutP;
-    a.plan_cost = p.cost;
-    if (aesr_wino_res_ok(a)) return 1;
-    return aesr_wino_ring_takes(a) ? 1 : 0;          /* a.ws_floats = 0: as the call below runs it */
+    WinoArgs a;
+    if (!wino_query(N, H, W, Cin, Cout, 3, 1, 0, &a)) return 0;
+    return aesr_wino_res_ok(a) || aesr_wino_ring_takes(a) ? 1 : 0;          /* a.ws_floats = 0: as the call below runs it */
 }
 
 int aesr_conv2d_wino_fwd_bn(const float* in, const float* upacked, const float* bias, const float* bn_scale, const float* bn_shift, float* out, int N,
@@ -610,13 +319,9 @@ int aesr_conv2d_wino_fwd_bn(const float* in, const float* upacked, const float* 
     AESR_CHECK_ARG(!pool || (H >= 2 && W >= 2), "aesr_conv2d_wino_fwd_bn: pooling needs H, W >= 2");
     AESR_CHECK_ARG(aesr_conv2d_wino_fwd_bn_supported(N, H, W, Cin, Cout), "aesr_conv2d_wino_fwd_bn: %d -> %d at %d x %d x %d is not a resident-filter or ring-kernel layer "
                    "(aesr_conv2d_wino_fwd_bn_supported)", Cin, Cout, N, H, W);
-    const WinoPlan p = plan_wino(N, H, W, Cin, Cout);
-    WinoArgs a = {};
-    a.in = in; a.upk = upacked; a.bias = bias; a.ysave = nullptr; a.out = out;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.CinP = p.CinP; a.Cout = Cout; a.CoutP = p.CoutP;
-    a.TI = p.TI; a.THt = p.THt; a.TWt = p.TWt;
-    a.plan_cost = p.cost;
-    a.act = act; a.mask_act = ACT_NONE; a.slope = slope; a.ksplit = 1;
+    WinoArgs a = wino_args(N, H, W, Cin, Cout, plan_wino(N, H, W, Cin, Cout));
+    a.in = in; a.upk = upacked; a.bias = bias; a.out = out;
+    a.act = act; a.mask_act = ACT_NONE; a.slope = slope;
     a.post_scale = bn_scale; a.post_shift = bn_shift; a.post_pool = pool ? 1 : 0;
     return aesr_launch_conv_wino(a, (hipStream_t)stream);
 }
@@ -636,15 +341,37 @@ int aesr_conv2d_wino_dgrad_sum2(const float* dy, const float* upacked_t, float* 
     return run_wino(dy, upacked_t, nullptr, nullptr, dx_half, N, H, W, Cout, Cin, ACT_NONE, ACT_NONE, 0.f, (hipStream_t)stream, 0, 1);
 }
 
+// ---- weight gradient ---------------------------------------------------------------------------------------------------
 size_t aesr_conv2d_wgrad_workspace_floats(int N, int H, int W, int Cin, int Cout, int KS, int pad) {
-    if (!conv_dims_ok(N, H, W, Cin, Cout) || (KS != 1 && KS != 3) || pad < 0 || pad >= KS) return 0;
-    const int Ho = H + 2 * pad - KS + 1, Wo = W + 2 * pad - KS + 1;
-    if (Ho <= 0 || Wo <= 0) return 0;
+    int Ho, Wo;
+    if (conv_geom(N, H, W, Cin, Cout, KS, pad, &Ho, &Wo) != GEOM_OK) return 0;
     return plan_wgrad(N, Ho, Wo, Cin, Cout, KS, pad).slab_floats;
 }
 
 static int wgrad_impl(const float* x, const float* dy, float* dw, float* db, float* workspace, int N, int H, int W, int Cin,
-                      int Cout, int KS, int pad, void* stream, int x_up2);
+                      int Cout, int KS, int pad, void* stream, int x_up2) {
+    AESR_CHECK_ARG(x && dy && workspace && N > 0, "aesr_conv2d_wgrad: null pointer or empty shape");
+    AESR_CHECK_ARG(Cin % 4 == 0 && Cout % 4 == 0, "aesr_conv2d_wgrad: Cin=%d, Cout=%d must be multiples of 4", Cin, Cout);
+    int Ho, Wo;
+    const int g = conv_geom(N, H, W, Cin, Cout, KS, pad, &Ho, &Wo);
+    AESR_CHECK_ARG(g != GEOM_FILTER, "aesr_conv2d_wgrad: unsupported KS=%d pad=%d", KS, pad);
+    if (g == GEOM_DIMS) AESR_CHECK_DIMS("aesr_conv2d_wgrad", N, H, W, Cin, Cout);
+    AESR_CHECK_ARG(g == GEOM_OK, "aesr_conv2d_wgrad: the %d x %d input is smaller than the %d x %d filter", H, W, KS, KS);
+    const WgradPlan p = plan_wgrad(N, Ho, Wo, Cin, Cout, KS, pad);
+    WgradArgs a;
+    a.x = x; a.dy = dy; a.slab = workspace;
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.CinP = p.CinP; a.Cout = Cout; a.CoutP = p.CoutP; a.Ho = Ho; a.Wo = Wo; a.pad = pad;
+    a.TH = p.TH; a.TW = p.TW; a.tiles_y = ceil_div(Ho, p.TH); a.tiles_x = ceil_div(Wo, p.TW);
+    a.ntiles = N * a.tiles_y * a.tiles_x; a.S = p.S;
+    a.PWS = p.PWS; a.TWS = p.TWS; a.PSX = p.PSX; a.PSD = p.PSD; a.dbgbuf = nullptr; a.x_up2 = x_up2;
+    if (p.variant == 2) {
+        if (int e = aesr_launch_conv_wgrad_wino(a, (hipStream_t)stream)) return e;
+    } else if (int e = aesr_launch_conv_wgrad(a, KS, p.variant, (hipStream_t)stream)) {
+        return e;
+    }
+    if (!dw) return AESR_OK;            // partial-slab form (aesr_conv2d_wgrad_partial): the caller reduces later
+    return aesr_launch_wgrad_reduce(workspace, dw, db, p.nslab, KS, Cin, p.CinP, Cout, p.CoutP, (hipStream_t)stream);
+}
 
 int aesr_conv2d_wgrad(const float* x, const float* dy, float* dw, float* db, float* workspace, int N, int H, int W, int Cin,
                       int Cout, int KS, int pad, void* stream) {
@@ -660,27 +387,16 @@ int aesr_conv2d_wgrad_partial(const float* x, const float* dy, float* workspace,
 
 int aesr_conv2d_wgrad_reduce_many(const aesr_wgrad_reduce_job* jobs_host, int njobs, void* stream) {
     AESR_CHECK_ARG(jobs_host && njobs > 0, "aesr_conv2d_wgrad_reduce_many: no jobs");
-    for (int j0 = 0; j0 < njobs; j0 += REDUCE_MAX_JOBS) {
-        ReduceTable t;
-        memset(&t, 0, sizeof(t));
-        t.njobs = njobs - j0 < REDUCE_MAX_JOBS ? njobs - j0 : REDUCE_MAX_JOBS;
-        int nb = 0;
-        for (int k = 0; k < t.njobs; ++k) {
-            const aesr_wgrad_reduce_job& jb = jobs_host[j0 + k];
-            AESR_CHECK_ARG(jb.workspace && jb.dw && jb.N > 0 && (jb.KS == 1 || jb.KS == 3), "aesr_conv2d_wgrad_reduce_many: bad job %d", j0 + k);
-            AESR_CHECK_ARG(conv_dims_ok(jb.N, jb.H, jb.W, jb.Cin, jb.Cout) && jb.pad >= 0 && jb.pad < jb.KS && jb.H + 2 * jb.pad >= jb.KS && jb.W + 2 * jb.pad >= jb.KS,
-                           "aesr_conv2d_wgrad_reduce_many: job %d: bad shape", j0 + k);
-            const int Ho = jb.H + 2 * jb.pad - jb.KS + 1, Wo = jb.W + 2 * jb.pad - jb.KS + 1;
-            const WgradPlan p = plan_wgrad(jb.N, Ho, Wo, jb.Cin, jb.Cout, jb.KS, jb.pad);      // the plan the partial launch used
-            ReduceJob& o = t.job[k];
-            o.slab = jb.workspace; o.dw = jb.dw; o.db = jb.db; o.nslab = p.nslab; o.KS2 = jb.KS * jb.KS; o.Cin = jb.Cin; o.CinP = p.CinP;
-            o.Cout = jb.Cout; o.CoutP = p.CoutP; o.block0 = nb;
-            nb += ceil_div(o.KS2 * jb.Cin * jb.Cout + (jb.db ? jb.Cout : 0), 64);
-        }
-        t.nblocks = nb;
-        if (int e = aesr_launch_wgrad_reduce_many(t, (hipStream_t)stream)) return e;
-    }
-    return AESR_OK;
+    return run_job_table<ReduceTable>(jobs_host, njobs, [](const aesr_wgrad_reduce_job& jb, int j, ReduceJob& o, int* blocks) -> int {
+        AESR_CHECK_ARG(jb.workspace && jb.dw && jb.N > 0 && (jb.KS == 1 || jb.KS == 3), "aesr_conv2d_wgrad_reduce_many: bad job %d", j);
+        int Ho, Wo;
+        AESR_CHECK_ARG(conv_geom(jb.N, jb.H, jb.W, jb.Cin, jb.Cout, jb.KS, jb.pad, &Ho, &Wo) == GEOM_OK, "aesr_conv2d_wgrad_reduce_many: job %d: bad shape", j);
+        const WgradPlan p = plan_wgrad(jb.N, Ho, Wo, jb.Cin, jb.Cout, jb.KS, jb.pad);      // the plan the partial launch used
+        o.slab = jb.workspace; o.dw = jb.dw; o.db = jb.db; o.nslab = p.nslab; o.KS2 = jb.KS * jb.KS; o.Cin = jb.Cin; o.CinP = p.CinP;
+        o.Cout = jb.Cout; o.CoutP = p.CoutP;
+        *blocks = ceil_div(o.KS2 * jb.Cin * jb.Cout + (jb.db ? jb.Cout : 0), 64);
+        return AESR_OK;
+    }, aesr_launch_wgrad_reduce_many, stream);
 }
 
 int aesr_conv2d_wgrad_up2_supported(int Cin, int Cout) { return wgrad_wino_ok(Cin, Cout, 3, 1) ? 1 : 0; }
@@ -690,30 +406,6 @@ int aesr_conv2d_wgrad_up2(const float* x_half, const float* dy, float* dw, float
     AESR_CHECK_ARG(wgrad_wino_ok(Cin, Cout, 3, 1) && !((H | W) & 1), "aesr_conv2d_wgrad_up2: needs the Winograd weight-gradient kernel "
                    "(Cin, Cout multiples of 32; got %d -> %d) and an even size", Cin, Cout);
     return wgrad_impl(x_half, dy, dw, db, workspace, N, H, W, Cin, Cout, 3, 1, stream, 1);
-}
-
-static int wgrad_impl(const float* x, const float* dy, float* dw, float* db, float* workspace, int N, int H, int W, int Cin,
-                      int Cout, int KS, int pad, void* stream, int x_up2) {
-    AESR_CHECK_ARG(x && dy && workspace && N > 0, "aesr_conv2d_wgrad: null pointer or empty shape");
-    AESR_CHECK_ARG(Cin % 4 == 0 && Cout % 4 == 0, "aesr_conv2d_wgrad: Cin=%d, Cout=%d must be multiples of 4", Cin, Cout);
-    AESR_CHECK_ARG((KS == 1 || KS == 3) && pad >= 0 && pad < KS, "aesr_conv2d_wgrad: unsupported KS=%d pad=%d", KS, pad);
-    AESR_CHECK_DIMS("aesr_conv2d_wgrad", N, H, W, Cin, Cout);
-    const int Ho = H + 2 * pad - KS + 1, Wo = W + 2 * pad - KS + 1;
-    AESR_CHECK_ARG(Ho > 0 && Wo > 0, "aesr_conv2d_wgrad: the %d x %d input is smaller than the %d x %d filter", H, W, KS, KS);
-    const WgradPlan p = plan_wgrad(N, Ho, Wo, Cin, Cout, KS, pad);
-    WgradArgs a;
-    a.x = x; a.dy = dy; a.slab = workspace;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.CinP = p.CinP; a.Cout = Cout; a.CoutP = p.CoutP; a.Ho = Ho; a.Wo = Wo; a.pad = pad;
-    a.TH = p.TH; a.TW = p.TW; a.tiles_y = ceil_div(Ho, p.TH); a.tiles_x = ceil_div(Wo, p.TW);
-    a.ntiles = N * a.tiles_y * a.tiles_x; a.S = p.S;
-    a.PWS = p.PWS; a.TWS = p.TWS; a.PSX = p.PSX; a.PSD = p.PSD; a.dbgbuf = nullptr; a.x_up2 = x_up2;
-    if (p.variant == 2) {
-        if (int e = aesr_launch_conv_wgrad_wino(a, (hipStream_t)stream)) return e;
-    } else if (int e = aesr_launch_conv_wgrad(a, KS, p.variant, (hipStream_t)stream)) {
-        return e;
-    }
-    if (!dw) return AESR_OK;            // partial-slab form (aesr_conv2d_wgrad_partial): the caller reduces later
-    return aesr_launch_wgrad_reduce(workspace, dw, db, p.nslab, KS, Cin, p.CinP, Cout, p.CoutP, (hipStream_t)stream);
 }
 
 int aesr_conv2d_smallcin_fwd(const float* in, const float* w, const float* bias, const float* y_saved, float* out, int N,
@@ -807,29 +499,30 @@ int aesr_conv2d_cout1_wgrad(const float* x, const float* dy, float* dw, float* d
     return aesr_launch_sum_partials(workspace, nwg, Cin * 9 + 1, dw, Cin * 9, db, (hipStream_t)stream);
 }
 
-int aesr_conv2d_cout1_dgrad(const float* dy, const float* w, const float* y_saved, float* dx, float* workspace, int N, int H,
-                            int W, int Cin, int mask_act, float slope, void* stream) {
-    AESR_CHECK_ARG(dy && w && dx && workspace && N > 0 && H > 0 && W > 0, "aesr_conv2d_cout1_dgrad: null pointer or empty shape");
-    AESR_CHECK_ARG(thin_channels_ok(Cin), "aesr_conv2d_cout1_dgrad: Cin=%d must be 4 times a power of two (4..256)", Cin);
-    if (int e = aesr_launch_thin_cout1_flip(w, workspace, Cin, (hipStream_t)stream)) return e;
+// flip_ws: where to flip w into first (aesr_conv2d_cout1_dgrad), or nullptr for a filter that is flipped already (.._pre)
+static int cout1_dgrad(const char* who, const float* dy, const float* w, float* flip_ws, const float* y_saved, float* dx, int N, int H, int W,
+                       int Cin, int mask_act, float slope, void* stream) {
+    AESR_CHECK_ARG(dy && w && dx && N > 0 && H > 0 && W > 0, "%s: null pointer or empty shape", who);
+    AESR_CHECK_ARG(thin_channels_ok(Cin), "%s: Cin=%d must be 4 times a power of two (4..256)", who, Cin);
+    if (flip_ws)
+        if (int e = aesr_launch_thin_cout1_flip(w, flip_ws, Cin, (hipStream_t)stream)) return e;
     ThinArgs a;
     memset(&a, 0, sizeof(a));
-    a.s = dy; a.w = workspace; a.ysave = y_saved; a.out = dx;
+    a.s = dy; a.w = flip_ws ? flip_ws : w; a.ysave = y_saved; a.out = dx;
     a.N = N; a.Hs = H; a.Ws = W; a.Ho = H; a.Wo = W; a.C = Cin; a.ps = 0;
     a.act = ACT_NONE; a.mask_act = y_saved ? mask_act : ACT_NONE; a.slope = slope;
     return aesr_launch_thin_expand(a, (hipStream_t)stream);
 }
 
+int aesr_conv2d_cout1_dgrad(const float* dy, const float* w, const float* y_saved, float* dx, float* workspace, int N, int H,
+                            int W, int Cin, int mask_act, float slope, void* stream) {
+    AESR_CHECK_ARG(workspace, "aesr_conv2d_cout1_dgrad: null pointer or empty shape");
+    return cout1_dgrad("aesr_conv2d_cout1_dgrad", dy, w, workspace, y_saved, dx, N, H, W, Cin, mask_act, slope, stream);
+}
+
 int aesr_conv2d_cout1_dgrad_pre(const float* dy, const float* w_flipped, const float* y_saved, float* dx, int N, int H, int W, int Cin,
                                 int mask_act, float slope, void* stream) {
-    AESR_CHECK_ARG(dy && w_flipped && dx && N > 0 && H > 0 && W > 0, "aesr_conv2d_cout1_dgrad_pre: null pointer or empty shape");
-    AESR_CHECK_ARG(thin_channels_ok(Cin), "aesr_conv2d_cout1_dgrad_pre: Cin=%d must be 4 times a power of two (4..256)", Cin);
-    ThinArgs a;
-    memset(&a, 0, sizeof(a));
-    a.s = dy; a.w = w_flipped; a.ysave = y_saved; a.out = dx;
-    a.N = N; a.Hs = H; a.Ws = W; a.Ho = H; a.Wo = W; a.C = Cin; a.ps = 0;
-    a.act = ACT_NONE; a.mask_act = y_saved ? mask_act : ACT_NONE; a.slope = slope;
-    return aesr_launch_thin_expand(a, (hipStream_t)stream);
+    return cout1_dgrad("aesr_conv2d_cout1_dgrad_pre", dy, w_flipped, nullptr, y_saved, dx, N, H, W, Cin, mask_act, slope, stream);
 }
 
 // ---- include/aesr_hip_train.h: the Cout == 1 convolution's backward in one pass over its saved input --------------------------------

@@ -71,3 +71,21 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 static inline int ceil_div(int a, int b) { return a / b + (a % b != 0); }       // (a, b > 0; no a + b - 1 to overflow)
 static inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
+
+// ceil(2^32 / d): the kernels divide their item index by d with one multiply-high (0: d == 1, no division)
+static inline unsigned aesr_magic_u32(int d) { return d <= 1 ? 0u : (unsigned)((((unsigned long long)1 << 32) + d - 1) / d); }
+
+// Opt a kernel in to the full dynamic LDS, once per device; a failure is reported here, with its cause.  `done` is the caller's
+// static bool[AESR_MAX_DEVICES] of this kernel instantiation, `name` the kernel's name in the message.
+static inline int aesr_lds_opt_in(const void* kernel, const char* name, bool* done, int bytes = 160 * 1024, const char* size = "160 KB") {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= AESR_MAX_DEVICES) dev = 0;
+    if (done[dev]) return AESR_OK;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) {
+        aesr_set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize = %s) failed: %s", name, size, hipGetErrorString(e));
+        return AESR_ERR_HIP;
+    }
+    done[dev] = true;
+    return AESR_OK;
+}

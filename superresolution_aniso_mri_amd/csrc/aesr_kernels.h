@@ -7,7 +7,7 @@ struct IgemmArgs {
     const float* in; const float* wpk; const float* bias; const float* ysave; float* out;
     int N, H, W, Cin, CinP, Cout, CoutP, Ho, Wo, pad;
     int TI, TH, TW, tiles_y, tiles_x, nitems, dbg;
-    int NT;          // threads per workgroup: 512 or 256
+    int unused_;     // holds the kernel-argument offsets of the fields below, and with them every conv_igemm listing, where they are
     int ksplit;      // K-split slices (1 = off): raw partial sums go to slab ks of `out`, see conv_igemm.hip
     float* dbgbuf;   // debug stamps (nullptr in normal operation)
     int act, mask_act;

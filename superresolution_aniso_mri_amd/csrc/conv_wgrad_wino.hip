@@ -416,18 +416,9 @@ bool aesr_wgrad_wino_tile_ok(int TH, int TW) { return (TH == 16 && TW == 8) || (
 template <int TH, int TW>
 static int launch_wgrad_wino(const WgradArgs& a, hipStream_t st) {
     const size_t shmem = aesr_wgrad_wino_lds_bytes(TH, TW);
-    static bool attr_set[AESR_MAX_DEVICES] = {};
-    int dev_ = 0;
-    if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= AESR_MAX_DEVICES) dev_ = 0;
-    if (!attr_set[dev_]) {
-        const hipError_t e_ = hipFuncSetAttribute((const void*)conv_wgrad_wino_f32<TH, TW, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e_ == hipSuccess) (void)hipFuncSetAttribute((const void*)conv_wgrad_wino_f32<TH, TW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e_ != hipSuccess) {
-            aesr_set_error("conv_wgrad_wino_f32: hipFuncSetAttribute(MaxDynamicSharedMemorySize = 160 KB) failed: %s", hipGetErrorString(e_));
-            return AESR_ERR_HIP;
-        }
-        attr_set[dev_] = true;
-    }
+    static bool attr_set[AESR_MAX_DEVICES] = {}, attr_set_dbg[AESR_MAX_DEVICES] = {};
+    if (int e = aesr_lds_opt_in((const void*)conv_wgrad_wino_f32<TH, TW, false>, "conv_wgrad_wino_f32", attr_set)) return e;
+    (void)aesr_lds_opt_in((const void*)conv_wgrad_wino_f32<TH, TW, true>, "conv_wgrad_wino_f32", attr_set_dbg);        // the stamped form
     dim3 grid(a.S * (a.CinP / 32) * (a.CoutP / 32));
     if (getenv("AESR_WGRAD_WINO_DBG") && grid.x <= 4096) {     // debug: per-phase cycle stamps, printed after a host sync
         static float* dbuf = nullptr;

@@ -331,16 +331,7 @@ static int wino_launch_one(const WinoArgs& a, hipStream_t st) {
     const int PP = a.TI * (2 * a.THt + 2) * (2 * a.TWt + 2);
     const size_t shmem = aesr_wino_lds_bytes(PP);
     static bool attr_set[AESR_MAX_DEVICES] = {};
-    int dev_ = 0;
-    if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= AESR_MAX_DEVICES) dev_ = 0;
-    if (!attr_set[dev_]) {
-        const hipError_t e_ = hipFuncSetAttribute((const void*)conv_wino_f32<NPP, MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e_ != hipSuccess) {
-            aesr_set_error("conv_wino_f32: hipFuncSetAttribute(MaxDynamicSharedMemorySize = 160 KB) failed: %s", hipGetErrorString(e_));
-            return AESR_ERR_HIP;
-        }
-        attr_set[dev_] = true;
-    }
+    if (int e = aesr_lds_opt_in((const void*)conv_wino_f32<NPP, MASK>, "conv_wino_f32", attr_set)) return e;
     int grid = 256;                    // persistent: one 8-wave workgroup per CU
     if (const char* e = getenv("AESR_WINO_GRID")) grid = atoi(e);
     if (grid > a.nitems) grid = a.nitems;
@@ -427,8 +418,7 @@ int aesr_launch_conv_wino(const WinoArgs& a_in, hipStream_t st) {
     a.regs_x = ceil_div(ceil_div(a.W, 2), a.TWt);
     a.nitems = ceil_div(a.N, a.TI) * a.regs_y * a.regs_x * (a.CoutP / WN_TN);
     // magic numbers of the item decomposition: exact while item * divisor < 2^32
-    auto magic = [](int d) { return d <= 1 ? 0u : (unsigned)((((unsigned long long)1 << 32) + d - 1) / d); };
-    a.m_ncot = magic(a.CoutP / WN_TN); a.m_regs_x = magic(a.regs_x); a.m_regs_y = magic(a.regs_y);
+    a.m_ncot = aesr_magic_u32(a.CoutP / WN_TN); a.m_regs_x = aesr_magic_u32(a.regs_x); a.m_regs_y = aesr_magic_u32(a.regs_y);
     if ((unsigned long long)a.nitems * (unsigned)(a.CoutP / WN_TN + a.regs_x + a.regs_y) >= ((unsigned long long)1 << 31)) {
         aesr_set_error("conv_wino: %d work items exceed the exact range of the item decomposition", a.nitems);
         return AESR_ERR_UNSUPPORTED;

@@ -370,16 +370,7 @@ template <int WR_TN, bool MASK, bool POST = false>
 static int wino_res_launch_one(const WinoArgs& a, hipStream_t st) {
     const size_t shmem = wino_res_lds_bytes(a.CinP, WR_TN);
     static bool attr_set[AESR_MAX_DEVICES] = {};
-    int dev_ = 0;
-    if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= AESR_MAX_DEVICES) dev_ = 0;
-    if (!attr_set[dev_]) {
-        const hipError_t e_ = hipFuncSetAttribute((const void*)conv_wino_res_f32<WR_TN, MASK, POST>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e_ != hipSuccess) {
-            aesr_set_error("conv_wino_res_f32: hipFuncSetAttribute(MaxDynamicSharedMemorySize = 160 KB) failed: %s", hipGetErrorString(e_));
-            return AESR_ERR_HIP;
-        }
-        attr_set[dev_] = true;
-    }
+    if (int e = aesr_lds_opt_in((const void*)conv_wino_res_f32<WR_TN, MASK, POST>, "conv_wino_res_f32", attr_set)) return e;
     const int ncot = a.CoutP / WR_TN;
     int grid = 256 / ncot * ncot;                          // one workgroup per CU, a whole number of them per cout tile
     if (const char* e = getenv("AESR_WINO_GRID")) grid = atoi(e) / ncot * ncot;
@@ -413,8 +404,7 @@ int aesr_launch_conv_wino_res(const WinoArgs& a_in, hipStream_t st) {
     a.nblk = a.N * a.bpi;
     const int TN = wino_res_tn(a);
     a.nitems = a.nblk * (a.CoutP / TN);
-    auto magic = [](int d) { return d <= 1 ? 0u : (unsigned)((((unsigned long long)1 << 32) + d - 1) / d); };
-    a.m_bpi = magic(a.bpi); a.m_regs_x = magic(a.regs_x);
+    a.m_bpi = aesr_magic_u32(a.bpi); a.m_regs_x = aesr_magic_u32(a.regs_x);
     // the wave's item index runs up to nblk + 8 * 256 past the end before it is compared: exactness of the multiply-high division
     if (((unsigned long long)a.nblk + 4096) * (unsigned)(a.bpi + a.regs_x) >= ((unsigned long long)1 << 31) || (size_t)a.H * a.W * a.Cin * 4 >= (size_t)0x10000000) {
         aesr_set_error("conv_wino_res: %d blocks exceed the exact range of the item decomposition (or images of 256 MB and more)", a.nblk);

@@ -39,12 +39,11 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include <map>
-#include <mutex>
 #include <tuple>
 #include <type_traits>
 
 #include "aesr_kernels.h"
+#include "conv_plan.h"
 #include "conv_wino_tile.h"
 
 constexpr int RG_WFL = 16 * 4 * 32 * 4;     // floats of one U chunk (16 positions x 16 ci x 32 co) = 8192
@@ -365,8 +364,6 @@ static int ring_conflicts(int TI, int THt, int TWt, int P16, int IP16, int sa, i
 static int ring_pwt(int TWt) { const int pw = 2 * TWt + 2; return pw <= 8 ? 8 : pw <= 10 ? 10 : pw <= 12 ? 12 : 16; }
 
 struct RingPlan { int TI, THt, TWt, PWT, imgP, sa, sm, sb, patch_fl, nfull, tail_k, ntail, conf, ksplit; double cost; };
-static std::map<std::tuple<int, int, int, int, int, int, int>, RingPlan> g_ring_plans;
-static std::mutex g_ring_mu;
 
 static size_t ring_lds_bytes(int patch_fl, int CoutP) { return ((size_t)RG_SLOTS * RG_WFL + (size_t)8 * patch_fl + CoutP + 16) * sizeof(float); }
 
@@ -408,15 +405,7 @@ static void ring_items(RingPlan& p, long B, int ncot, int G) {
 constexpr int RG_KSPLIT_MAX = 16;
 
 // smax: the largest channel split the caller's workspace allows (1: none)
-static RingPlan plan_ring(const WinoArgs& a, int smax) {
-    std::lock_guard<std::mutex> lk(g_ring_mu);
-    if (smax > RG_KSPLIT_MAX) smax = RG_KSPLIT_MAX;
-    if (smax < 1) smax = 1;
-    int fks = 0;
-    if (const char* e = getenv("AESR_RING_KSPLIT")) fks = atoi(e);                  // experiments / tests: force the channel split (where the workspace allows)
-    const auto key = std::make_tuple(a.N, a.H, a.W, a.CinP, a.CoutP, smax, fks);
-    auto it = g_ring_plans.find(key);
-    if (it != g_ring_plans.end()) return it->second;
+static RingPlan plan_ring_compute(const WinoArgs& a, int smax, int fks, const int* fshape) {
     const int Ht = ceil_div(a.H, 2), Wt = ceil_div(a.W, 2), ncot = a.CoutP / 32, nch = a.CinP / 16;
     RingPlan best;
     best.cost = 1e300;
@@ -452,9 +441,7 @@ static RingPlan plan_ring(const WinoArgs& a, int smax) {
             if (p.cost < best.cost) best = p;
         }
     };
-    int fti = 0, fth = 0, ftw = 0;
-    if (const char* e = getenv("AESR_RING_SHAPE")) (void)sscanf(e, "%d,%d,%d", &fti, &fth, &ftw);      // experiments: "TI,THt,TWt"
-    if (fti > 0 && fth > 0 && ftw > 0) consider(fti, fth, ftw);
+    if (fshape[0] > 0 && fshape[1] > 0 && fshape[2] > 0) consider(fshape[0], fshape[1], fshape[2]);
     if (best.cost > 1e299) {
         for (int TI = 1; TI <= 16 && TI <= a.N; ++TI)
             for (int THt = 1; THt <= 7 && THt <= Ht; ++THt)
@@ -467,8 +454,18 @@ static RingPlan plan_ring(const WinoArgs& a, int smax) {
         fprintf(stderr, "[aesr plan] ring N=%d %dx%d Cin=%d Cout=%d -> TI=%d THt=%d TWt=%d PWT=%d imgP=%d swizzle (%d,%d,%d) conflicts %d patch %d B; "
                 "channel split %d (of <= %d); %d full groups + %d tail groups of %d; cost %.0f\n", a.N, a.H, a.W, a.CinP, a.CoutP, best.TI, best.THt, best.TWt,
                 best.PWT, best.imgP, best.sa, best.sm, best.sb, best.conf, best.patch_fl * 4, best.ksplit, smax, best.nfull, best.ntail, best.tail_k, best.cost);
-    g_ring_plans[key] = best;
     return best;
+}
+
+// AESR_RING_KSPLIT forces the channel split (where the workspace allows), AESR_RING_SHAPE="TI,THt,TWt" the block (experiments, tests)
+static RingPlan plan_ring(const WinoArgs& a, int smax) {
+    smax = smax > RG_KSPLIT_MAX ? RG_KSPLIT_MAX : smax < 1 ? 1 : smax;
+    int fks, fshape[3];
+    env_ints("AESR_RING_KSPLIT", &fks, 1);
+    env_ints("AESR_RING_SHAPE", fshape, 3);
+    static PlanCache<std::tuple<int, int, int, int, int, int, int, int, int, int>, RingPlan> cache;
+    return cache.get(std::make_tuple(a.N, a.H, a.W, a.CinP, a.CoutP, smax, fks, fshape[0], fshape[1], fshape[2]),
+                     [&] { return plan_ring_compute(a, smax, fks, fshape); });
 }
 
 int aesr_wino_ring_mode() {
@@ -519,16 +516,7 @@ unsigned aesr_wino_ring_timeouts() {
 template <int PWT, bool MASK, bool POST = false>
 static int ring_launch_one(const WinoArgs& a, int grid, size_t shmem, hipStream_t st) {
     static bool attr_set[AESR_MAX_DEVICES] = {};
-    int dev_ = 0;
-    if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= AESR_MAX_DEVICES) dev_ = 0;
-    if (!attr_set[dev_]) {
-        const hipError_t e_ = hipFuncSetAttribute((const void*)conv_wino_ring_f32<PWT, MASK, POST>, hipFuncAttributeMaxDynamicSharedMemorySize, RG_LDS_MAX);
-        if (e_ != hipSuccess) {
-            aesr_set_error("conv_wino_ring_f32: hipFuncSetAttribute(MaxDynamicSharedMemorySize = 160 KB - 256 B) failed: %s", hipGetErrorString(e_));
-            return AESR_ERR_HIP;
-        }
-        attr_set[dev_] = true;
-    }
+    if (int e = aesr_lds_opt_in((const void*)conv_wino_ring_f32<PWT, MASK, POST>, "conv_wino_ring_f32", attr_set, RG_LDS_MAX, "160 KB - 256 B")) return e;
     hipLaunchKernelGGL((conv_wino_ring_f32<PWT, MASK, POST>), dim3(grid), dim3(512), shmem, st, a);
     AESR_LAUNCH_CHECK("conv_wino_ring_f32");
     return AESR_OK;
@@ -589,8 +577,7 @@ int aesr_launch_conv_wino_ring(const WinoArgs& a_in, hipStream_t st) {
     }
     a.split_bytes = (int)(out_floats * 4);
     a.nitems = (p.nfull + p.ntail) * ncot * a.ksplit;
-    auto magic = [](int d) { return d <= 1 ? 0u : (unsigned)((((unsigned long long)1 << 32) + d - 1) / d); };
-    a.m_ncot = magic(ncot); a.m_bpi = magic(a.bpi); a.m_regs_x = magic(a.regs_x); a.m_ksplit = magic(a.ksplit);
+    a.m_ncot = aesr_magic_u32(ncot); a.m_bpi = aesr_magic_u32(a.bpi); a.m_regs_x = aesr_magic_u32(a.regs_x); a.m_ksplit = aesr_magic_u32(a.ksplit);
     const float* fin_bias = a.bias;
     const float* fin_mask = a.ysave;
     const int fin_act = a.act;

@@ -90,7 +90,6 @@ def test_conv_fwd(hip, case, act):
     assert rel_l2(nchw(out), ref) < 1e-5
 
 
-# image counts no other test uses: the library caches one tile plan per shape, and the forced split must be planned fresh
 @pytest.mark.parametrize("case", [(23, 20, 20, 512, 512, 4), (11, 10, 10, 512, 512, 2), (5, 10, 10, 256, 128, 4), (3, 9, 11, 128, 64, 2)])
 def test_conv_ksplit_workspace_paths(hip, case, monkeypatch):
     """Under-filled deep layers (VGG conv4/5 shapes): the workspace entry points split the input channels into extra work
@@ -121,6 +120,35 @@ def test_conv_ksplit_workspace_paths(hip, case, monkeypatch):
     dx = torch.full_like(dref, float("nan"))
     hip.check(L.aesr_conv2d_dgrad_ws(hip.ptr(dy), hip.ptr(pb), hip.ptr(mask), hip.ptr(dx), hip.ptr(wsd) if nwd else None, N, H, W, cin,
                                      cout, 3, 1, 2, 0.0, hip.stream()), "dgrad_ws")
+    assert rel_l2(dx, dref) < 1e-5
+
+
+def test_conv_ksplit_forced_after_the_unforced_plan(hip, monkeypatch):
+    """AESR_IGEMM_KSPLIT takes effect on a shape the process has already planned without it: the unsplit kernels run first (and cache
+    their plan), then the variable is set, the workspace queries ask for the two slabs and the workspace entry points run the split."""
+    N, H, W, cin, cout = 2, 5, 5, 32, 32
+    monkeypatch.delenv("AESR_IGEMM_KSPLIT", raising=False)
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(N, H, W, cin, generator=g).cuda()
+    w = (torch.randn(cout, cin, 3, 3, generator=g) / np.sqrt(9 * cin)).cuda()
+    b = torch.randn(cout, generator=g).cuda()
+    dy = torch.randn(N, H, W, cout, generator=g).cuda()
+    mask = torch.randn(N, H, W, cin, generator=g).cuda()
+    L = hip.lib
+    pf, pb = _pack(hip, w, 0), _pack(hip, w, 1)
+    ref, dref = torch.empty(N, H, W, cout, device="cuda"), torch.empty(N, H, W, cin, device="cuda")
+    hip.check(L.aesr_conv2d_fwd(hip.ptr(x), hip.ptr(pf), hip.ptr(b), hip.ptr(ref), N, H, W, cin, cout, 3, 1, 2, 0.0, hip.stream()), "fwd")
+    hip.check(L.aesr_conv2d_dgrad(hip.ptr(dy), hip.ptr(pb), hip.ptr(mask), hip.ptr(dref), N, H, W, cin, cout, 3, 1, 2, 0.0, hip.stream()), "dgrad")
+    assert L.aesr_conv2d_workspace_floats(N, H, W, cin, cout, 3, 1) == 0 and L.aesr_conv2d_dgrad_workspace_floats(N, H, W, cin, cout, 3, 1) == 0
+    monkeypatch.setenv("AESR_IGEMM_KSPLIT", "2")
+    assert L.aesr_conv2d_workspace_floats(N, H, W, cin, cout, 3, 1) == 3200 and L.aesr_conv2d_dgrad_workspace_floats(N, H, W, cin, cout, 3, 1) == 3200
+    ws = torch.empty(3200, device="cuda")
+    out, dx = torch.full_like(ref, float("nan")), torch.full_like(dref, float("nan"))
+    hip.check(L.aesr_conv2d_fwd_ws(hip.ptr(x), hip.ptr(pf), hip.ptr(b), hip.ptr(out), hip.ptr(ws), N, H, W, cin, cout, 3, 1, 2, 0.0,
+                                   hip.stream()), "fwd_ws")
+    assert rel_l2(out, ref) < 1e-5
+    hip.check(L.aesr_conv2d_dgrad_ws(hip.ptr(dy), hip.ptr(pb), hip.ptr(mask), hip.ptr(dx), hip.ptr(ws), N, H, W, cin, cout, 3, 1, 2, 0.0,
+                                     hip.stream()), "dgrad_ws")
     assert rel_l2(dx, dref) < 1e-5
 
 

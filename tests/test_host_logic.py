@@ -271,3 +271,33 @@ def test_largest_activation_of_a_pass_and_planner_queries():
             assert kind in (2, 3)
         else:
             assert kind in (1, 3)        # the first streamed kernel, or the ring kernel only WITH a channel split
+
+
+def test_planner_overrides_take_effect_whenever_set():
+    """The plan caches are keyed by shape AND by the parsed override variables: a forced plan does not depend on what the process planned
+    before, and an unforced one comes back when the variable goes.  Forced values: 2 slabs of 1 x 5 x 5 x 32 outputs; one slab of
+    10 x 64 x 32 (direct kernel: 3 x 3 + 1 planes of CinP x CoutP) and of 10 x 64 x 64 (Winograd weight gradient)."""
+    from superresolution_aniso_mri_amd import _hip
+    L = _hip.lib
+    names = ("AESR_IGEMM_KSPLIT", "AESR_WGRAD_S", "AESR_WGRAD_WINO_S")
+    if any(n in os.environ for n in names):
+        pytest.skip("a planner override is set in the environment")
+    rows = [(L.aesr_conv2d_workspace_floats, (1, 5, 5, 32, 32, 3, 1), 0, "AESR_IGEMM_KSPLIT", "2", 1600),
+            (L.aesr_conv2d_dgrad_workspace_floats, (1, 5, 5, 32, 32, 3, 1), 0, "AESR_IGEMM_KSPLIT", "2", 1600),
+            (L.aesr_conv2d_wgrad_workspace_floats, (3, 40, 40, 48, 20, 3, 1), 6144000, "AESR_WGRAD_S", "1", 20480),
+            (L.aesr_conv2d_wgrad_workspace_floats, (3, 40, 40, 64, 64, 3, 1), 1843200, "AESR_WGRAD_WINO_S", "1", 40960)]
+    try:
+        for query, shape, unforced, name, value, forced in rows:
+            for first_forced in (False, True):
+                if first_forced:
+                    os.environ[name] = value
+                    assert query(*shape) == forced, (name, shape)
+                    del os.environ[name]
+                assert query(*shape) == unforced, (name, shape)
+                os.environ[name] = value
+                assert query(*shape) == forced, (name, shape)
+                del os.environ[name]
+                assert query(*shape) == unforced, (name, shape)
+    finally:
+        for n in names:
+            os.environ.pop(n, None)
