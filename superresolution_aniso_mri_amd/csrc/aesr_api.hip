@@ -640,12 +640,30 @@ static void bn_out_dims(int H, int W, int mode, int* Ho, int* Wo) {
     else { *Ho = H; *Wo = W; }
 }
 
+// The argument blocks of the apply / backward kernels: pointers, dims (with the output's) and groups; false: bad groups.  The entry points
+// check their own pointers (each needs another subset) and what else they refuse.
+static bool bn_apply_args(BnApplyArgs* a, const float* y, const float* scale, const float* shift, float* out, int N, int H, int W, int C,
+                          int mode, int G, const int* nstart_host) {
+    a->y = y; a->scale = scale; a->shift = shift; a->out = out; a->N = N; a->H = H; a->W = W; a->C = C; a->mode = mode;
+    bn_out_dims(H, W, mode, &a->Ho, &a->Wo);
+    return fill_groups(&a->gr, G, nstart_host);
+}
+
+static bool bn_bwd_args(BnBwdArgs* a, const float* gout, const float* y, const float* mean, const float* invstd, const float* scale,
+                        float* coef, float* partial, float* dpre, int N, int H, int W, int C, int mode, int act, float slope, int G,
+                        const int* nstart_host) {
+    memset(a, 0, sizeof(*a));
+    a->gout = gout; a->y = y; a->mean = mean; a->invstd = invstd; a->scale = scale; a->coef = coef; a->partial = partial; a->dpre = dpre;
+    a->N = N; a->H = H; a->W = W; a->C = C; a->mode = mode; a->act = act; a->slope = slope;
+    bn_out_dims(H, W, mode, &a->Ho, &a->Wo);
+    return fill_groups(&a->gr, G, nstart_host);
+}
+
 int aesr_bn_apply(const float* y, const float* scale, const float* shift, float* out, int N, int H, int W, int C, int mode,
                   int G, const int* nstart_host, void* stream) {
     BnApplyArgs a;
-    AESR_CHECK_ARG(y && scale && shift && out && fill_groups(&a.gr, G, nstart_host), "aesr_bn_apply: bad arguments");
-    a.y = y; a.scale = scale; a.shift = shift; a.out = out; a.N = N; a.H = H; a.W = W; a.C = C; a.mode = mode;
-    bn_out_dims(H, W, mode, &a.Ho, &a.Wo);
+    AESR_CHECK_ARG(y && scale && shift && out && bn_apply_args(&a, y, scale, shift, out, N, H, W, C, mode, G, nstart_host),
+                   "aesr_bn_apply: bad arguments");
     AESR_CHECK_ARG(a.Ho > 0 && a.Wo > 0, "aesr_bn_apply: empty output");
     return aesr_launch_bn_apply(a, (hipStream_t)stream);
 }
@@ -661,29 +679,82 @@ size_t aesr_bn_fused1_workspace_floats(int C, int G) { return (size_t)256 * G * 
 size_t aesr_bn_fused1_barrier_words(void) { return 16 * 32; }
 unsigned int aesr_bn_fused1_timeouts(void) { return aesr_bn_fused_timeouts_impl(); }
 
+// the caller's exchange arguments of the *_p2p entry points, as given (fill_p2p checks them)
+struct BnP2P { void* const* peers_host; int world, rank, slot; const unsigned int* gen_dev; };
+
+static int fill_p2p(BnFusedArgs* a, const BnP2P& p, const char* who) {
+    if (!p.peers_host || !p.gen_dev || p.world < 1 || p.world > 8 || p.rank < 0 || p.rank >= p.world || p.slot < 0 || p.slot >= AESR_P2P_SLOTS) {
+        aesr_set_error("%s: bad exchange arguments (world %d, rank %d, slot %d of %d)", who, p.world, p.rank, p.slot, AESR_P2P_SLOTS);
+        return AESR_ERR_ARG;
+    }
+    a->world = p.world; a->rank = p.rank; a->slot = p.slot; a->gen = p.gen_dev;
+    for (int r = 0; r < p.world; ++r) {
+        if (!p.peers_host[r]) {
+            aesr_set_error("%s: the region of rank %d is not mapped", who, r);
+            return AESR_ERR_ARG;
+        }
+        a->peers[r] = (unsigned char*)p.peers_host[r];
+    }
+    return AESR_OK;
+}
+
+// what the forward and the backward entry share: dims, groups, counts, workspace, barrier state and (p2p) the exchange
+static int bn_fused1_args(BnFusedArgs* a, const char* who, float* workspace, unsigned int* barrier_state, const double* counts_host, int N, int H,
+                          int W, int C, int mode, const BnGroups& gr, const BnP2P* p2p) {
+    if (mode != AESR_BN_NONE && mode != AESR_BN_POOL) {
+        aesr_set_error(p2p ? "%s: mode %d" : "%s: mode %d (the un-folded Upsample takes the three-launch path)", who, mode);
+        return AESR_ERR_ARG;
+    }
+    a->rec = workspace; a->bar = barrier_state; a->N = N; a->H = H; a->W = W; a->C = C; a->pool = mode == AESR_BN_POOL;
+    bn_out_dims(H, W, mode, &a->Ho, &a->Wo);
+    a->G = gr.G;
+    a->counts = bn_counts(counts_host, gr.G);
+    memcpy(a->nstart, gr.nstart, sizeof(a->nstart));
+    return p2p ? fill_p2p(a, *p2p, who) : AESR_OK;
+}
+
+static int bn_fused1_fwd(const char* who, const float* y, float* out, float* workspace, unsigned int* barrier_state, const double* counts_host,
+                         const float* gamma, const float* beta, float* running_mean, float* running_var, int64_t* num_batches_tracked, float* mean,
+                         float* invstd, float* scale, float* shift, int N, int H, int W, int C, int mode, int G, const int* nstart_host,
+                         float momentum, float eps, int update_running, const BnP2P* p2p, void* stream) {
+    BnGroups gr;
+    BnFusedArgs a = {};
+    AESR_CHECK_ARG(y && out && workspace && barrier_state && counts_host && gamma && beta && mean && invstd && scale && shift &&
+                       fill_groups(&gr, G, nstart_host) && gr.nstart[G] == N, "%s: bad arguments", who);
+    if (int e = bn_fused1_args(&a, who, workspace, barrier_state, counts_host, N, H, W, C, mode, gr, p2p)) return e;
+    a.y = y; a.out = out; a.gamma = gamma; a.beta = beta; a.running_mean = running_mean; a.running_var = running_var;
+    a.nbt = (long long*)num_batches_tracked; a.mean = mean; a.invstd = invstd; a.scale = scale; a.shift = shift;
+    a.momentum = momentum; a.eps = eps; a.update_running = update_running && running_mean && running_var; a.act = ACT_NONE;
+    return aesr_launch_bn_fused(a, 0, (hipStream_t)stream);
+}
+
+static int bn_fused1_bwd(const char* who, const float* gout, const float* y, const float* mean, const float* invstd, const float* scale,
+                         float* workspace, unsigned int* barrier_state, const double* counts_host, float* coef, float* dgamma, float* dbeta,
+                         float* dpre, int N, int H, int W, int C, int mode, int act, float slope, int G, const int* nstart_host, const BnP2P* p2p,
+                         void* stream) {
+    BnGroups gr;
+    BnFusedArgs a = {};
+    AESR_CHECK_ARG(gout && y && mean && invstd && scale && workspace && barrier_state && counts_host && coef && dgamma && dbeta && dpre &&
+                       fill_groups(&gr, G, nstart_host) && gr.nstart[G] == N, "%s: bad arguments", who);
+    if (int e = bn_fused1_args(&a, who, workspace, barrier_state, counts_host, N, H, W, C, mode, gr, p2p)) return e;
+    a.y = y; a.gout = gout; a.out = dpre; a.mean_in = mean; a.invstd_in = invstd; a.scale_in = scale; a.coef = coef; a.dgamma = dgamma;
+    a.dbeta = dbeta; a.act = act; a.slope = slope;
+    return aesr_launch_bn_fused(a, 1, (hipStream_t)stream);
+}
+
 int aesr_bn_fused1_fwd(const float* y, float* out, float* workspace, unsigned int* barrier_state, const double* counts_host, const float* gamma,
                        const float* beta, float* running_mean, float* running_var, int64_t* num_batches_tracked, float* mean, float* invstd,
                        float* scale, float* shift, int N, int H, int W, int C, int mode, int G, const int* nstart_host, float momentum, float eps,
                        int update_running, void* stream) {
-    BnGroups gr;
-    AESR_CHECK_ARG(y && out && workspace && barrier_state && counts_host && gamma && beta && mean && invstd && scale && shift &&
-                       fill_groups(&gr, G, nstart_host) && gr.nstart[G] == N, "aesr_bn_fused1_fwd: bad arguments");
-    AESR_CHECK_ARG(mode == AESR_BN_NONE || mode == AESR_BN_POOL, "aesr_bn_fused1_fwd: mode %d (the un-folded Upsample takes the three-launch path)", mode);
-    return aesr_bn_fused_run(y, nullptr, out, workspace, barrier_state, gamma, beta, running_mean, running_var, (long long*)num_batches_tracked, mean,
-                             invstd, scale, shift, nullptr, nullptr, nullptr, N, H, W, C, mode == AESR_BN_POOL, G, gr.nstart, counts_host, momentum, eps,
-                             update_running && running_mean && running_var, ACT_NONE, 0.f, 0, nullptr, (hipStream_t)stream);
+    return bn_fused1_fwd("aesr_bn_fused1_fwd", y, out, workspace, barrier_state, counts_host, gamma, beta, running_mean, running_var,
+                         num_batches_tracked, mean, invstd, scale, shift, N, H, W, C, mode, G, nstart_host, momentum, eps, update_running, nullptr, stream);
 }
 
 int aesr_bn_fused1_bwd(const float* gout, const float* y, const float* mean, const float* invstd, const float* scale, float* workspace,
                        unsigned int* barrier_state, const double* counts_host, float* coef, float* dgamma, float* dbeta, float* dpre, int N, int H,
                        int W, int C, int mode, int act, float slope, int G, const int* nstart_host, void* stream) {
-    BnGroups gr;
-    AESR_CHECK_ARG(gout && y && mean && invstd && scale && workspace && barrier_state && counts_host && coef && dgamma && dbeta && dpre &&
-                       fill_groups(&gr, G, nstart_host) && gr.nstart[G] == N, "aesr_bn_fused1_bwd: bad arguments");
-    AESR_CHECK_ARG(mode == AESR_BN_NONE || mode == AESR_BN_POOL, "aesr_bn_fused1_bwd: mode %d (the un-folded Upsample takes the three-launch path)", mode);
-    return aesr_bn_fused_run(y, gout, dpre, workspace, barrier_state, nullptr, nullptr, nullptr, nullptr, nullptr, (float*)mean, (float*)invstd,
-                             (float*)scale, nullptr, coef, dgamma, dbeta, N, H, W, C, mode == AESR_BN_POOL, G, gr.nstart, counts_host, 0.f, 0.f, 0, act, slope,
-                             1, nullptr, (hipStream_t)stream);
+    return bn_fused1_bwd("aesr_bn_fused1_bwd", gout, y, mean, invstd, scale, workspace, barrier_state, counts_host, coef, dgamma, dbeta, dpre, N, H, W,
+                         C, mode, act, slope, G, nstart_host, nullptr, stream);
 }
 
 /* ---- the same two with the SyncBN exchange inside: data parallel over peer-mapped regions ---- */
@@ -694,49 +765,22 @@ int aesr_p2p_tick(unsigned int* gen_dev, void* stream) {
     return aesr_launch_p2p_tick(gen_dev, (hipStream_t)stream);
 }
 
-static int fill_p2p(BnP2P* p, void* const* peers_host, int world, int rank, int slot, const unsigned int* gen_dev, const char* who) {
-    if (!peers_host || !gen_dev || world < 1 || world > 8 || rank < 0 || rank >= world || slot < 0 || slot >= AESR_P2P_SLOTS) {
-        aesr_set_error("%s: bad exchange arguments (world %d, rank %d, slot %d of %d)", who, world, rank, slot, AESR_P2P_SLOTS);
-        return AESR_ERR_ARG;
-    }
-    p->world = world; p->rank = rank; p->slot = slot; p->gen = gen_dev;
-    for (int r = 0; r < 8; ++r) p->peers[r] = r < world ? peers_host[r] : nullptr;
-    for (int r = 0; r < world; ++r)
-        if (!p->peers[r]) {
-            aesr_set_error("%s: the region of rank %d is not mapped", who, r);
-            return AESR_ERR_ARG;
-        }
-    return AESR_OK;
-}
-
 int aesr_bn_fused1_fwd_p2p(const float* y, float* out, float* workspace, unsigned int* barrier_state, const double* counts_host, const float* gamma,
                            const float* beta, float* running_mean, float* running_var, int64_t* num_batches_tracked, float* mean, float* invstd,
                            float* scale, float* shift, int N, int H, int W, int C, int mode, int G, const int* nstart_host, float momentum, float eps,
                            int update_running, void* const* peers_host, int world, int rank, int slot, const unsigned int* gen_dev, void* stream) {
-    BnGroups gr;
-    BnP2P p2p;
-    AESR_CHECK_ARG(y && out && workspace && barrier_state && counts_host && gamma && beta && mean && invstd && scale && shift &&
-                       fill_groups(&gr, G, nstart_host) && gr.nstart[G] == N, "aesr_bn_fused1_fwd_p2p: bad arguments");
-    AESR_CHECK_ARG(mode == AESR_BN_NONE || mode == AESR_BN_POOL, "aesr_bn_fused1_fwd_p2p: mode %d", mode);
-    if (int e = fill_p2p(&p2p, peers_host, world, rank, slot, gen_dev, "aesr_bn_fused1_fwd_p2p")) return e;
-    return aesr_bn_fused_run(y, nullptr, out, workspace, barrier_state, gamma, beta, running_mean, running_var, (long long*)num_batches_tracked, mean,
-                             invstd, scale, shift, nullptr, nullptr, nullptr, N, H, W, C, mode == AESR_BN_POOL, G, gr.nstart, counts_host, momentum, eps,
-                             update_running && running_mean && running_var, ACT_NONE, 0.f, 0, &p2p, (hipStream_t)stream);
+    const BnP2P p2p = {peers_host, world, rank, slot, gen_dev};
+    return bn_fused1_fwd("aesr_bn_fused1_fwd_p2p", y, out, workspace, barrier_state, counts_host, gamma, beta, running_mean, running_var,
+                         num_batches_tracked, mean, invstd, scale, shift, N, H, W, C, mode, G, nstart_host, momentum, eps, update_running, &p2p, stream);
 }
 
 int aesr_bn_fused1_bwd_p2p(const float* gout, const float* y, const float* mean, const float* invstd, const float* scale, float* workspace,
                            unsigned int* barrier_state, const double* counts_host, float* coef, float* dgamma, float* dbeta, float* dpre, int N, int H,
                            int W, int C, int mode, int act, float slope, int G, const int* nstart_host, void* const* peers_host, int world, int rank,
                            int slot, const unsigned int* gen_dev, void* stream) {
-    BnGroups gr;
-    BnP2P p2p;
-    AESR_CHECK_ARG(gout && y && mean && invstd && scale && workspace && barrier_state && counts_host && coef && dgamma && dbeta && dpre &&
-                       fill_groups(&gr, G, nstart_host) && gr.nstart[G] == N, "aesr_bn_fused1_bwd_p2p: bad arguments");
-    AESR_CHECK_ARG(mode == AESR_BN_NONE || mode == AESR_BN_POOL, "aesr_bn_fused1_bwd_p2p: mode %d", mode);
-    if (int e = fill_p2p(&p2p, peers_host, world, rank, slot, gen_dev, "aesr_bn_fused1_bwd_p2p")) return e;
-    return aesr_bn_fused_run(y, gout, dpre, workspace, barrier_state, nullptr, nullptr, nullptr, nullptr, nullptr, (float*)mean, (float*)invstd,
-                             (float*)scale, nullptr, coef, dgamma, dbeta, N, H, W, C, mode == AESR_BN_POOL, G, gr.nstart, counts_host, 0.f, 0.f, 0, act, slope,
-                             1, &p2p, (hipStream_t)stream);
+    const BnP2P p2p = {peers_host, world, rank, slot, gen_dev};
+    return bn_fused1_bwd("aesr_bn_fused1_bwd_p2p", gout, y, mean, invstd, scale, workspace, barrier_state, counts_host, coef, dgamma, dbeta, dpre, N, H,
+                         W, C, mode, act, slope, G, nstart_host, &p2p, stream);
 }
 
 int aesr_bn_finalize_apply(const double* sums, const double* counts_host, const float* gamma, const float* beta, float* running_mean,
@@ -744,11 +788,9 @@ int aesr_bn_finalize_apply(const double* sums, const double* counts_host, const 
                            const float* y, float* out, int N, int H, int W, int C, int mode, int G, const int* nstart_host, float momentum,
                            float eps, int update_running, void* stream) {
     BnApplyArgs a;
-    AESR_CHECK_ARG(sums && counts_host && gamma && beta && mean && invstd && scale && shift && y && out && fill_groups(&a.gr, G, nstart_host),
-                   "aesr_bn_finalize_apply: bad arguments");
+    AESR_CHECK_ARG(sums && counts_host && gamma && beta && mean && invstd && scale && shift && y && out &&
+                       bn_apply_args(&a, y, scale, shift, out, N, H, W, C, mode, G, nstart_host), "aesr_bn_finalize_apply: bad arguments");
     AESR_CHECK_ARG(aesr_bn_fused_ok(C, G), "aesr_bn_finalize_apply: %d groups x %d channels exceed the kernel's tables (aesr_bn_fused_supported)", G, C);
-    a.y = y; a.scale = scale; a.shift = shift; a.out = out; a.N = N; a.H = H; a.W = W; a.C = C; a.mode = mode;
-    bn_out_dims(H, W, mode, &a.Ho, &a.Wo);
     AESR_CHECK_ARG(a.Ho > 0 && a.Wo > 0, "aesr_bn_finalize_apply: empty output");
     return aesr_launch_bn_finalize_apply(sums, counts_host, gamma, beta, running_mean, running_var, (long long*)num_batches_tracked, mean, invstd,
                                          scale, shift, momentum, eps, update_running && running_mean && running_var, G, a, (hipStream_t)stream);
@@ -757,12 +799,10 @@ int aesr_bn_finalize_apply(const double* sums, const double* counts_host, const 
 int aesr_bn_bwd_reduce(const float* gout, const float* y, const float* mean, const float* invstd, float* partial, double* sums,
                        int N, int H, int W, int C, int mode, int G, const int* nstart_host, void* stream) {
     BnBwdArgs a;
-    memset(&a, 0, sizeof(a));
-    AESR_CHECK_ARG(gout && y && mean && invstd && partial && sums && fill_groups(&a.gr, G, nstart_host), "aesr_bn_bwd_reduce: bad arguments");
-    a.gout = gout; a.y = y; a.mean = mean; a.invstd = invstd; a.partial = partial;
-    a.N = N; a.H = H; a.W = W; a.C = C; a.mode = mode;
+    AESR_CHECK_ARG(gout && y && mean && invstd && partial && sums &&
+                       bn_bwd_args(&a, gout, y, mean, invstd, nullptr, nullptr, partial, nullptr, N, H, W, C, mode, 0, 0.f, G, nstart_host),
+                   "aesr_bn_bwd_reduce: bad arguments");
     AESR_CHECK_ARG((double)N * H * W < 2147483648.0, "aesr_bn_bwd_reduce: more than 2^31 pixels");
-    bn_out_dims(H, W, mode, &a.Ho, &a.Wo);
     if (int e = aesr_launch_bn_bwd_reduce(a, AESR_BN_NWG, (hipStream_t)stream)) return e;
     return aesr_launch_bn_reduce(partial, sums, AESR_BN_NWG, C, G, (hipStream_t)stream);
 }
@@ -771,12 +811,9 @@ int aesr_bn_bwd_apply(const float* gout, const float* y, const float* mean, cons
                       const double* sums, const double* counts_host, float* coef, float* dgamma, float* dbeta, float* dpre, int N,
                       int H, int W, int C, int mode, int act, float slope, int G, const int* nstart_host, void* stream) {
     BnBwdArgs a;
-    memset(&a, 0, sizeof(a));
     AESR_CHECK_ARG(gout && y && mean && invstd && scale && sums && counts_host && coef && dgamma && dbeta && dpre &&
-                       fill_groups(&a.gr, G, nstart_host), "aesr_bn_bwd_apply: bad arguments");
-    a.gout = gout; a.y = y; a.mean = mean; a.invstd = invstd; a.scale = scale; a.coef = coef; a.dpre = dpre;
-    a.N = N; a.H = H; a.W = W; a.C = C; a.mode = mode; a.act = act; a.slope = slope;
-    bn_out_dims(H, W, mode, &a.Ho, &a.Wo);
+                       bn_bwd_args(&a, gout, y, mean, invstd, scale, coef, nullptr, dpre, N, H, W, C, mode, act, slope, G, nstart_host),
+                   "aesr_bn_bwd_apply: bad arguments");
     if (aesr_bn_fused_ok(C, G))          // coef / dgamma / dbeta from the sums in the apply kernel's prologue: one launch
         return aesr_launch_bn_bwd_finalize_apply(sums, counts_host, coef, dgamma, dbeta, G, a, (hipStream_t)stream);
     if (int e = aesr_launch_bn_bwd_finalize(sums, counts_host, coef, dgamma, dbeta, C, G, (hipStream_t)stream)) return e;
@@ -787,13 +824,10 @@ int aesr_bn_bwd(const float* gout, const float* y, const float* mean, const floa
                 const double* counts_host, float* coef, float* dgamma, float* dbeta, float* dpre, int N, int H, int W, int C,
                 int mode, int act, float slope, int G, const int* nstart_host, void* stream) {
     BnBwdArgs a;
-    memset(&a, 0, sizeof(a));
     AESR_CHECK_ARG(gout && y && mean && invstd && scale && partial && counts_host && coef && dgamma && dbeta && dpre &&
-                       fill_groups(&a.gr, G, nstart_host), "aesr_bn_bwd: bad arguments");
+                       bn_bwd_args(&a, gout, y, mean, invstd, scale, coef, partial, dpre, N, H, W, C, mode, act, slope, G, nstart_host),
+                   "aesr_bn_bwd: bad arguments");
     AESR_CHECK_ARG((double)N * H * W < 2147483648.0, "aesr_bn_bwd: more than 2^31 pixels");
-    a.gout = gout; a.y = y; a.mean = mean; a.invstd = invstd; a.scale = scale; a.coef = coef; a.dpre = dpre; a.partial = partial;
-    a.N = N; a.H = H; a.W = W; a.C = C; a.mode = mode; a.act = act; a.slope = slope;
-    bn_out_dims(H, W, mode, &a.Ho, &a.Wo);
     if (int e = aesr_launch_bn_bwd_reduce(a, AESR_BN_NWG, (hipStream_t)stream)) return e;
     if (int e = aesr_launch_bn_bwd_reduce_finalize(partial, AESR_BN_NWG, counts_host, coef, dgamma, dbeta, C, G, (hipStream_t)stream))
         return e;

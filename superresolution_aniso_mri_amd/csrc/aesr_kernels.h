@@ -169,16 +169,43 @@ struct BnBwdArgs {
     unsigned long long m_hw, m_w;   // exact-division constants for H*W and W (filled by the bn_bwd_reduce launcher)
     int k_hw, k_w;
 };
-// one-launch BatchNorm for small batches (bn_fused.hip): activations resident in LDS, one grid barrier
-struct BnFusedArgs;
-struct BnP2P { int world, rank, slot; const unsigned* gen; void* peers[8]; };     // data parallel: peer-mapped exchange regions (p2p.hip)
+// values per statistic group (sub-batch size x H x W; under data parallel the global one); unused groups hold 1.0
+struct BnCounts { double c[4]; };
+static inline BnCounts bn_counts(const double* counts_host, int G) {
+    BnCounts cnt;
+    for (int g = 0; g < 4; ++g) cnt.c[g] = (counts_host && g < G) ? counts_host[g] : 1.0;
+    return cnt;
+}
+// one-launch BatchNorm for small batches (bn_fused.hip): activations resident in LDS, one grid barrier.  The caller zero-initialises the
+// struct, fills what its direction uses by name and hands it to aesr_launch_bn_fused, which adds the plan and p2p_spins.
+struct BnFusedArgs {
+    // forward: y -> out;  backward: (gout, y) -> out = dpre
+    const float* y; const float* gout; float* out;
+    float* rec;                     // [workgroups][G][2][C] floats: the workgroups' partial sums
+    unsigned* bar;                  // grid-barrier state (zeroed once by the owner)
+    const float* gamma; const float* beta; float* running_mean; float* running_var; long long* nbt;       // forward
+    // [G][C]: the forward launch writes mean / invstd / scale / shift, the backward launch reads the *_in views of the first three
+    union { float* mean; const float* mean_in; };
+    union { float* invstd; const float* invstd_in; };
+    union { float* scale; const float* scale_in; };
+    float* shift;
+    float* coef; float* dgamma; float* dbeta;                     // backward
+    int N, H, W, C, Ho, Wo, pool;   // pool: AvgPool2d(2) follows (out / gout are [N][H/2][W/2][C])
+    int RU, upi, nunits, unit_fl, gunit_fl;      // the plan (bf_plan): rows per unit, units per image, units, floats of a unit of y / of the gathered gradient
+    int G, update_running, act;
+    int nb;                         // the plan: workgroups of the launch (64, 128 or 256)
+    // data parallel (SyncBN over peer-mapped regions, p2p.hip): world > 0
+    int world, rank, slot, p2p_spins;      // p2p_spins (set by the launcher): polls before a wait for a peer gives up (AESR_P2P_SPINS; ~4 us each after the first 4096)
+    const unsigned* gen;            // device word: the step generation (same on every rank; aesr_p2p_tick advances it once per step)
+    unsigned char* peers[8];        // every rank's exchange region as mapped into this process (peers[rank] = this rank's own)
+    float momentum, eps, slope;
+    BnCounts counts;
+    int nstart[5];
+};
+int aesr_launch_bn_fused(BnFusedArgs a, int backward, hipStream_t st);
 int aesr_launch_p2p_tick(unsigned* gen, hipStream_t st);
 bool aesr_bn_fused1_ok(int N, int H, int W, int C, int pool, int G, int backward);
 unsigned aesr_bn_fused_timeouts_impl();
-int aesr_bn_fused_run(const float* y, const float* gout, float* out, float* rec, unsigned* bar, const float* gamma, const float* beta,
-                      float* running_mean, float* running_var, long long* nbt, float* mean, float* invstd, float* scale, float* shift, float* coef,
-                      float* dgamma, float* dbeta, int N, int H, int W, int C, int pool, int G, const int* nstart, const double* counts,
-                      float momentum, float eps, int update_running, int act, float slope, int backward, const BnP2P* p2p, hipStream_t st);
 int aesr_launch_bn_stats(const float* y, float* partial, int HW, int C, const BnGroups& gr, int nwg, hipStream_t st);
 int aesr_launch_bn_reduce(const float* partial, double* sums, int nwg, int C, int G, hipStream_t st);
 int aesr_launch_bn_finalize(const double* sums, const double* counts, const float* gamma, const float* beta, float* rm, float* rv,

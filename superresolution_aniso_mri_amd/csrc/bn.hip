@@ -12,17 +12,10 @@
 //   backward : reduce sum(g), sum(g*xhat) -> apply dy = scale*(g - s1/M - xhat*s2/M) * act'(y)
 //
 // Replaces nn.BatchNorm2d + nn.AvgPool2d / nn.Upsample of networks/acai_vanilla.py:58-59,90-92.
-#include "aesr_kernels.h"
+// The arithmetic from the sums on is in bn_math.h (shared with bn_fused.hip); this file adds the reductions and the streaming loops.
+#include "bn_math.h"
 
 enum { BN_MODE_NONE = 0, BN_MODE_POOL = 1, BN_MODE_UP = 2 };
-
-
-__device__ __forceinline__ int group_of(const BnGroups& gr, int n) {
-    int g = 0;
-    for (int k = 1; k < gr.G; ++k)
-        if (n >= gr.nstart[k]) g = k;
-    return g;
-}
 
 // ---- forward statistics ---------------------------------------------------------------------------------
 // partial[g][wg][2][C]; grid = (nwg, G)
@@ -90,8 +83,6 @@ __global__ __launch_bounds__(1024) void bn_reduce_kernel(const float* __restrict
 }
 
 // train: stats from sums/counts (+ running update, group after group); eval: stats from the running buffers
-struct BnCounts { double c[4]; };
-
 struct BnFinArgs {
     const float* gamma; const float* beta; float* running_mean; float* running_var; long long* nbt;
     float* mean; float* invstd; float* scale; float* shift;
@@ -105,26 +96,18 @@ struct BnFinArgs {
 __device__ __forceinline__ void bn_finalize_one(const BnFinArgs& f, int c, int g, double s0, double s1) {
     float m, iv;
     if (f.train) {
-        const double M = f.counts.c[g];
-        const double mu = s0 / M;
-        double var = s1 / M - mu * mu;
-        if (var < 0.0) var = 0.0;
-        m = (float)mu;
-        iv = (float)(1.0 / sqrt(var + (double)f.eps));
-        if (f.update_running) {
-            const double unb = M > 1.0 ? var * M / (M - 1.0) : var;
-            f.running_mean[c] = (1.f - f.momentum) * f.running_mean[c] + f.momentum * m;
-            f.running_var[c] = (1.f - f.momentum) * f.running_var[c] + f.momentum * (float)unb;
-        }
+        const double var = bn_moments(s0, s1, f.counts.c[g], f.eps, &m, &iv);
+        if (f.update_running)      // through memory: the next group's step reads what this one wrote
+            bn_running_step(f.momentum, m, bn_unbiased(var, f.counts.c[g]), &f.running_mean[c], &f.running_var[c]);
     } else {
         m = f.running_mean[c];
         iv = 1.f / sqrtf(f.running_var[c] + f.eps);
     }
     f.mean[g * f.C + c] = m;
     f.invstd[g * f.C + c] = iv;
-    const float sc = f.gamma[c] * iv;
+    const float sc = bn_scale(f.gamma[c], iv);
     f.scale[g * f.C + c] = sc;
-    f.shift[g * f.C + c] = f.beta[c] - m * sc;
+    f.shift[g * f.C + c] = bn_shift(f.beta[c], m, sc);
 }
 
 __global__ void bn_finalize_kernel(const double* __restrict__ sums, BnFinArgs f) {
@@ -188,7 +171,9 @@ __global__ __launch_bounds__(1024) void bn_reduce_finalize_kernel(const float* _
 
 // ---- forward apply (+pool / +upsample) ----------------------------------------------------------------
 
-__global__ __launch_bounds__(256) void bn_apply_kernel(BnApplyArgs a) {
+// out = scale * pool_or_up(y) + shift over the whole output, grid-stride; sc_tab / sh_tab [g][C]: the finalize launch's tables in global
+// memory or the block's own in LDS
+__device__ __forceinline__ void bn_apply_loop(const BnApplyArgs& a, const float* sc_tab, const float* sh_tab) {
     const int C4 = a.C >> 2;
     const size_t total = (size_t)a.N * a.Ho * a.Wo * C4;
     for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
@@ -198,98 +183,35 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(BnApplyArgs a) {
         pix /= a.Wo;
         const int yy = pix % a.Ho;
         const int n = pix / a.Ho;
-        const int g = group_of(a.gr, n);
-        const f32x4 sc = *(const f32x4*)(a.scale + g * a.C + c4 * 4);
-        const f32x4 sh = *(const f32x4*)(a.shift + g * a.C + c4 * 4);
+        const int g = bn_group_of(a.gr.G, a.gr.nstart, n);
+        const f32x4 sc = *(const f32x4*)(sc_tab + g * a.C + c4 * 4);
+        const f32x4 sh = *(const f32x4*)(sh_tab + g * a.C + c4 * 4);
         f32x4 v;
         if (a.mode == BN_MODE_POOL) {
             const float* b = a.y + (((size_t)n * a.H + 2 * yy) * a.W + 2 * x) * a.C + c4 * 4;
-            const f32x4 v00 = *(const f32x4*)b, v01 = *(const f32x4*)(b + a.C);
-            const f32x4 v10 = *(const f32x4*)(b + (size_t)a.W * a.C), v11 = *(const f32x4*)(b + (size_t)a.W * a.C + a.C);
-            v = ((v00 + v01) + (v10 + v11)) * 0.25f;
+            v = bn_pool2x2(*(const f32x4*)b, *(const f32x4*)(b + a.C), *(const f32x4*)(b + (size_t)a.W * a.C),
+                           *(const f32x4*)(b + (size_t)a.W * a.C + a.C));
         } else if (a.mode == BN_MODE_UP) {
             v = *(const f32x4*)(a.y + (((size_t)n * a.H + (yy >> 1)) * a.W + (x >> 1)) * a.C + c4 * 4);
         } else {
             v = *(const f32x4*)(a.y + (((size_t)n * a.H + yy) * a.W + x) * a.C + c4 * 4);
         }
-        *(f32x4*)(a.out + idx * 4) = v * sc + sh;
+        *(f32x4*)(a.out + idx * 4) = bn_fwd_elem(v, sc, sh);
     }
 }
 
-// Data parallel (SyncBN): finalize + apply in ONE launch.  The all-reduced sums are [G][2][C] doubles -- a few hundred values -- so every
-// block derives scale / shift for all groups and channels itself (into LDS, the arithmetic of bn_finalize_one) and block 0 alone
-// writes mean / invstd / scale / shift for the backward pass and updates the running statistics, group after group.
-constexpr int BN_FUSE_MAX = 1024;       // G * C values a block keeps in LDS
+__global__ __launch_bounds__(256) void bn_apply_kernel(BnApplyArgs a) { bn_apply_loop(a, a.scale, a.shift); }
 
-__device__ __forceinline__ void bn_finalize_vals(const BnFinArgs& f, int g, double s0, double s1, float* m, float* iv, double* unb) {
-    const double M = f.counts.c[g];
-    const double mu = s0 / M;
-    double var = s1 / M - mu * mu;
-    if (var < 0.0) var = 0.0;
-    *m = (float)mu;
-    *iv = (float)(1.0 / sqrt(var + (double)f.eps));
-    *unb = M > 1.0 ? var * M / (M - 1.0) : var;
-}
+// Data parallel (SyncBN): finalize + apply in ONE launch.  The all-reduced sums are [G][2][C] doubles -- a few hundred values -- so every
+// block derives scale / shift for all groups and channels itself (bn_math.h: bn_fwd_tables) and block 0 alone writes mean / invstd /
+// scale / shift for the backward pass and updates the running statistics, group after group.
+constexpr int BN_FUSE_MAX = 1024;       // G * C values a block keeps in LDS
 
 __global__ __launch_bounds__(256) void bn_finalize_apply_kernel(const double* __restrict__ sums, BnFinArgs f, BnApplyArgs a) {
     __shared__ __attribute__((aligned(16))) float s_sc[BN_FUSE_MAX], s_sh[BN_FUSE_MAX];
-    const int GC = f.G * f.C;
-    for (int i = threadIdx.x; i < GC; i += 256) {
-        const int g = i / f.C, c = i - g * f.C;
-        float m, iv;
-        double unb;
-        bn_finalize_vals(f, g, sums[(g * 2 + 0) * f.C + c], sums[(g * 2 + 1) * f.C + c], &m, &iv, &unb);
-        const float sc = f.gamma[c] * iv, sh = f.beta[c] - m * sc;
-        s_sc[i] = sc;
-        s_sh[i] = sh;
-        if (blockIdx.x == 0) {
-            f.mean[i] = m;
-            f.invstd[i] = iv;
-            f.scale[i] = sc;
-            f.shift[i] = sh;
-        }
-    }
-    if (blockIdx.x == 0 && f.update_running) {
-        if (threadIdx.x == 0 && f.nbt) *f.nbt += f.G;
-        for (int c = threadIdx.x; c < f.C; c += 256) {
-            float rm = f.running_mean[c], rv = f.running_var[c];
-            for (int g = 0; g < f.G; ++g) {             // group after group, as the reference's successive calls
-                float m, iv;
-                double unb;
-                bn_finalize_vals(f, g, sums[(g * 2 + 0) * f.C + c], sums[(g * 2 + 1) * f.C + c], &m, &iv, &unb);
-                rm = (1.f - f.momentum) * rm + f.momentum * m;
-                rv = (1.f - f.momentum) * rv + f.momentum * (float)unb;
-            }
-            f.running_mean[c] = rm;
-            f.running_var[c] = rv;
-        }
-    }
+    bn_fwd_tables<256>(sums, f, blockIdx.x == 0, s_sc, s_sh);
     __syncthreads();
-    const int C4 = a.C >> 2;
-    const size_t total = (size_t)a.N * a.Ho * a.Wo * C4;
-    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
-        const int c4 = idx % C4;
-        size_t pix = idx / C4;
-        const int x = pix % a.Wo;
-        pix /= a.Wo;
-        const int yy = pix % a.Ho;
-        const int n = pix / a.Ho;
-        const int g = group_of(a.gr, n);
-        const f32x4 sc = *(const f32x4*)(s_sc + g * a.C + c4 * 4);
-        const f32x4 sh = *(const f32x4*)(s_sh + g * a.C + c4 * 4);
-        f32x4 v;
-        if (a.mode == BN_MODE_POOL) {
-            const float* b = a.y + (((size_t)n * a.H + 2 * yy) * a.W + 2 * x) * a.C + c4 * 4;
-            const f32x4 v00 = *(const f32x4*)b, v01 = *(const f32x4*)(b + a.C);
-            const f32x4 v10 = *(const f32x4*)(b + (size_t)a.W * a.C), v11 = *(const f32x4*)(b + (size_t)a.W * a.C + a.C);
-            v = ((v00 + v01) + (v10 + v11)) * 0.25f;
-        } else if (a.mode == BN_MODE_UP) {
-            v = *(const f32x4*)(a.y + (((size_t)n * a.H + (yy >> 1)) * a.W + (x >> 1)) * a.C + c4 * 4);
-        } else {
-            v = *(const f32x4*)(a.y + (((size_t)n * a.H + yy) * a.W + x) * a.C + c4 * 4);
-        }
-        *(f32x4*)(a.out + idx * 4) = v * sc + sh;
-    }
+    bn_apply_loop(a, s_sc, s_sh);
 }
 
 // ---- backward --------------------------------------------------------------------------------------------
@@ -390,16 +312,7 @@ __global__ void bn_bwd_finalize_kernel(const double* __restrict__ sums, BnCounts
                                        int C, int G) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    double dg = 0.0, db = 0.0;
-    for (int g = 0; g < G; ++g) {
-        const double s1 = sums[(g * 2 + 0) * C + c], s2 = sums[(g * 2 + 1) * C + c];
-        coef[(g * 2 + 0) * C + c] = (float)(s1 / counts.c[g]);
-        coef[(g * 2 + 1) * C + c] = (float)(s2 / counts.c[g]);
-        db += s1;
-        dg += s2;
-    }
-    dgamma[c] = (float)dg;
-    dbeta[c] = (float)db;
+    bn_bwd_channel<true>(sums, C, c, counts.c, G, C, c, coef, dgamma, dbeta);
 }
 
 // backward-reduce partials -> coef / dgamma / dbeta in ONE launch (same math as bn_reduce + bn_bwd_finalize)
@@ -412,22 +325,13 @@ __global__ __launch_bounds__(1024) void bn_bwd_reduce_finalize_kernel(const floa
     const bool live = c < C;
     __shared__ double tot[8][BNR_COLS];
     bn_all_totals(partial, nwg, C, G, c, live, red, tot, col, rl);
-    if (rl == 0 && live) {
-        double dg = 0.0, db = 0.0;
-        for (int g = 0; g < G; ++g) {
-            const double s1 = tot[2 * g][col], s2 = tot[2 * g + 1][col];
-            coef[(g * 2 + 0) * C + c] = (float)(s1 / counts.c[g]);
-            coef[(g * 2 + 1) * C + c] = (float)(s2 / counts.c[g]);
-            db += s1;
-            dg += s2;
-        }
-        dgamma[c] = (float)dg;
-        dbeta[c] = (float)db;
-    }
+    if (rl == 0 && live) bn_bwd_channel<true>(&tot[0][0], BNR_COLS, col, counts.c, G, C, c, coef, dgamma, dbeta);
 }
 
+// dpre = scale * (g - k1 - xhat * k2) * act'(y) over the whole layer, grid-stride; k_tab [g][2][C]: coef in global memory or the block's
+// own table in LDS
 template <int MODE>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnBwdArgs a) {
+__device__ __forceinline__ void bn_bwd_apply_loop(const BnBwdArgs& a, const float* k_tab) {
     const int C4 = a.C >> 2;
     const size_t total = (size_t)a.N * a.H * a.W * C4;
     for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
@@ -437,68 +341,29 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnBwdArgs a) {
         pix /= a.W;
         const int yy = pix % a.H;
         const int n = pix / a.H;
-        const int g = group_of(a.gr, n);
+        const int g = bn_group_of(a.gr.G, a.gr.nstart, n);
         const f32x4 mu = *(const f32x4*)(a.mean + g * a.C + c4 * 4);
         const f32x4 iv = *(const f32x4*)(a.invstd + g * a.C + c4 * 4);
         const f32x4 sc = *(const f32x4*)(a.scale + g * a.C + c4 * 4);
-        const f32x4 k1 = *(const f32x4*)(a.coef + (g * 2 + 0) * a.C + c4 * 4);
-        const f32x4 k2 = *(const f32x4*)(a.coef + (g * 2 + 1) * a.C + c4 * 4);
+        const f32x4 k1 = *(const f32x4*)(k_tab + (g * 2 + 0) * a.C + c4 * 4);
+        const f32x4 k2 = *(const f32x4*)(k_tab + (g * 2 + 1) * a.C + c4 * 4);
         const f32x4 yv = *(const f32x4*)(a.y + idx * 4);
         const f32x4 gg = bn_gather_g_t<MODE>(a, n, yy, x, c4);
-        const f32x4 xh = (yv - mu) * iv;
-        f32x4 d = sc * (gg - k1 - xh * k2);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) d[e] *= act_grad_from_output(yv[e], a.act, a.slope);
-        *(f32x4*)(a.dpre + idx * 4) = d;
+        *(f32x4*)(a.dpre + idx * 4) = bn_bwd_elem(yv, gg, mu, iv, sc, k1, k2, a.act, a.slope);
     }
 }
 
-// the same for the backward pass: coef = sums / M per block in LDS, block 0 writes coef / dgamma / dbeta
+template <int MODE>
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnBwdArgs a) { bn_bwd_apply_loop<MODE>(a, a.coef); }
+
+// the same for the backward pass: coef = sums / M per block in LDS, block 0 writes coef / dgamma / dbeta (bn_math.h: bn_bwd_tables)
 template <int MODE>
 __global__ __launch_bounds__(256) void bn_bwd_finalize_apply_kernel(const double* __restrict__ sums, BnCounts counts, float* __restrict__ coef,
                                                                     float* __restrict__ dgamma, float* __restrict__ dbeta, int G, BnBwdArgs a) {
     __shared__ __attribute__((aligned(16))) float s_k[2 * BN_FUSE_MAX];       // [g][2][C]
-    const int GC2 = G * 2 * a.C;
-    for (int i = threadIdx.x; i < GC2; i += 256) {
-        const int g = i / (2 * a.C);
-        const float k = (float)(sums[i] / counts.c[g]);
-        s_k[i] = k;
-        if (blockIdx.x == 0) coef[i] = k;
-    }
-    if (blockIdx.x == 0)
-        for (int c = threadIdx.x; c < a.C; c += 256) {
-            double dg = 0.0, db = 0.0;
-            for (int g = 0; g < G; ++g) {
-                db += sums[(g * 2 + 0) * a.C + c];
-                dg += sums[(g * 2 + 1) * a.C + c];
-            }
-            dgamma[c] = (float)dg;
-            dbeta[c] = (float)db;
-        }
+    bn_bwd_tables<256>(sums, counts.c, G, a.C, blockIdx.x == 0, s_k, coef, dgamma, dbeta);
     __syncthreads();
-    const int C4 = a.C >> 2;
-    const size_t total = (size_t)a.N * a.H * a.W * C4;
-    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
-        const int c4 = idx % C4;
-        size_t pix = idx / C4;
-        const int x = pix % a.W;
-        pix /= a.W;
-        const int yy = pix % a.H;
-        const int n = pix / a.H;
-        const int g = group_of(a.gr, n);
-        const f32x4 mu = *(const f32x4*)(a.mean + g * a.C + c4 * 4);
-        const f32x4 iv = *(const f32x4*)(a.invstd + g * a.C + c4 * 4);
-        const f32x4 sc = *(const f32x4*)(a.scale + g * a.C + c4 * 4);
-        const f32x4 k1 = *(const f32x4*)(s_k + (g * 2 + 0) * a.C + c4 * 4);
-        const f32x4 k2 = *(const f32x4*)(s_k + (g * 2 + 1) * a.C + c4 * 4);
-        const f32x4 yv = *(const f32x4*)(a.y + idx * 4);
-        const f32x4 gg = bn_gather_g_t<MODE>(a, n, yy, x, c4);
-        const f32x4 xh = (yv - mu) * iv;
-        f32x4 d = sc * (gg - k1 - xh * k2);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) d[e] *= act_grad_from_output(yv[e], a.act, a.slope);
-        *(f32x4*)(a.dpre + idx * 4) = d;
-    }
+    bn_bwd_apply_loop<MODE>(a, s_k);
 }
 
 // ---- launchers ----------------------------------------------------------------------------------------------
@@ -509,6 +374,22 @@ static int bn_check_c(int C, const char* who) {
     }
     return AESR_OK;
 }
+
+// blocks of a streaming (grid-stride) kernel over `pixels` pixels of C channels, four channels per thread
+static dim3 bn_stream_grid(size_t pixels, int C) {
+    const size_t total = pixels * (C / 4);
+    int grid = (int)((total + 255) / 256);
+    if (grid > 4096) grid = 4096;
+    return dim3(grid);
+}
+
+// the three compile-time modes of a backward kernel template
+#define BN_LAUNCH_MODE(kernel, mode, grid, shm, st, ...)                                                       \
+    do {                                                                                                       \
+        if ((mode) == BN_MODE_POOL) hipLaunchKernelGGL(kernel<BN_MODE_POOL>, grid, dim3(256), shm, st, __VA_ARGS__); \
+        else if ((mode) == BN_MODE_UP) hipLaunchKernelGGL(kernel<BN_MODE_UP>, grid, dim3(256), shm, st, __VA_ARGS__);  \
+        else hipLaunchKernelGGL(kernel<0>, grid, dim3(256), shm, st, __VA_ARGS__);                             \
+    } while (0)
 
 int aesr_launch_bn_stats(const float* y, float* partial, int HW, int C, const BnGroups& gr, int nwg, hipStream_t st) {
     if (int e = bn_check_c(C, "bn_stats")) return e;
@@ -531,7 +412,7 @@ static BnFinArgs bn_fin_args(const double* counts, const float* gamma, const flo
     f.gamma = gamma; f.beta = beta; f.running_mean = running_mean; f.running_var = running_var; f.nbt = nbt;
     f.mean = mean; f.invstd = invstd; f.scale = scale; f.shift = shift; f.C = C; f.G = G; f.momentum = momentum; f.eps = eps;
     f.train = train; f.update_running = update_running;
-    for (int g = 0; g < 4; ++g) f.counts.c[g] = (counts && g < G) ? counts[g] : 1.0;
+    f.counts = bn_counts(counts, G);
     return f;
 }
 
@@ -559,20 +440,15 @@ int aesr_launch_bn_reduce_finalize(const float* partial, int nwg, const double* 
 
 int aesr_launch_bn_bwd_reduce_finalize(const float* partial, int nwg, const double* counts, float* coef, float* dgamma,
                                        float* dbeta, int C, int G, hipStream_t st) {
-    BnCounts cnt;
-    for (int g = 0; g < 4; ++g) cnt.c[g] = (counts && g < G) ? counts[g] : 1.0;
-    hipLaunchKernelGGL(bn_bwd_reduce_finalize_kernel, dim3(ceil_div(C, BNR_COLS)), dim3(BNR_COLS * BNR_RL), 0, st, partial, nwg, cnt, coef, dgamma,
-                       dbeta, C, G);
+    hipLaunchKernelGGL(bn_bwd_reduce_finalize_kernel, dim3(ceil_div(C, BNR_COLS)), dim3(BNR_COLS * BNR_RL), 0, st, partial, nwg,
+                       bn_counts(counts, G), coef, dgamma, dbeta, C, G);
     AESR_LAUNCH_CHECK("bn_bwd_reduce_finalize");
     return AESR_OK;
 }
 
 int aesr_launch_bn_apply(const BnApplyArgs& a, hipStream_t st) {
     if (int e = bn_check_c(a.C, "bn_apply")) return e;
-    const size_t total = (size_t)a.N * a.Ho * a.Wo * (a.C / 4);
-    int grid = (int)((total + 255) / 256);
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(bn_apply_kernel, bn_stream_grid((size_t)a.N * a.Ho * a.Wo, a.C), dim3(256), 0, st, a);
     AESR_LAUNCH_CHECK("bn_apply");
     return AESR_OK;
 }
@@ -591,32 +467,21 @@ int aesr_launch_bn_bwd_reduce(const BnBwdArgs& a_in, int nwg, hipStream_t st) {
     bn_magic((unsigned)a.W, &a.m_w, &a.k_w);
     if (int e = bn_check_c(a.C, "bn_bwd_reduce")) return e;
     const int PL = 256 / (a.C / 4);
-    const dim3 grid(nwg, a.gr.G);
-    const size_t shm = (size_t)PL * 2 * a.C * sizeof(float);
-    if (a.mode == BN_MODE_POOL) hipLaunchKernelGGL(bn_bwd_reduce_kernel<BN_MODE_POOL>, grid, dim3(256), shm, st, a);
-    else if (a.mode == BN_MODE_UP) hipLaunchKernelGGL(bn_bwd_reduce_kernel<BN_MODE_UP>, grid, dim3(256), shm, st, a);
-    else hipLaunchKernelGGL(bn_bwd_reduce_kernel<0>, grid, dim3(256), shm, st, a);
+    BN_LAUNCH_MODE(bn_bwd_reduce_kernel, a.mode, dim3(nwg, a.gr.G), (size_t)PL * 2 * a.C * sizeof(float), st, a);
     AESR_LAUNCH_CHECK("bn_bwd_reduce");
     return AESR_OK;
 }
 
 int aesr_launch_bn_bwd_finalize(const double* sums, const double* counts, float* coef, float* dgamma, float* dbeta, int C,
                                 int G, hipStream_t st) {
-    BnCounts cnt;
-    for (int g = 0; g < 4; ++g) cnt.c[g] = (counts && g < G) ? counts[g] : 1.0;
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, st, sums, cnt, coef, dgamma, dbeta, C, G);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, st, sums, bn_counts(counts, G), coef, dgamma, dbeta, C, G);
     AESR_LAUNCH_CHECK("bn_bwd_finalize");
     return AESR_OK;
 }
 
 int aesr_launch_bn_bwd_apply(const BnBwdArgs& a, hipStream_t st) {
     if (int e = bn_check_c(a.C, "bn_bwd_apply")) return e;
-    const size_t total = (size_t)a.N * a.H * a.W * (a.C / 4);
-    int grid = (int)((total + 255) / 256);
-    if (grid > 4096) grid = 4096;
-    if (a.mode == BN_MODE_POOL) hipLaunchKernelGGL(bn_bwd_apply_kernel<BN_MODE_POOL>, dim3(grid), dim3(256), 0, st, a);
-    else if (a.mode == BN_MODE_UP) hipLaunchKernelGGL(bn_bwd_apply_kernel<BN_MODE_UP>, dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(bn_bwd_apply_kernel<0>, dim3(grid), dim3(256), 0, st, a);
+    BN_LAUNCH_MODE(bn_bwd_apply_kernel, a.mode, bn_stream_grid((size_t)a.N * a.H * a.W, a.C), 0, st, a);
     AESR_LAUNCH_CHECK("bn_bwd_apply");
     return AESR_OK;
 }
@@ -630,10 +495,7 @@ int aesr_launch_bn_finalize_apply(const double* sums, const double* counts, cons
     if (int e = bn_check_c(a.C, "bn_finalize_apply")) return e;
     const BnFinArgs f = bn_fin_args(counts, gamma, beta, running_mean, running_var, nbt, mean, invstd, scale, shift, a.C, G, momentum, eps, 1,
                                     update_running);
-    const size_t total = (size_t)a.N * a.Ho * a.Wo * (a.C / 4);
-    int grid = (int)((total + 255) / 256);
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(bn_finalize_apply_kernel, dim3(grid), dim3(256), 0, st, sums, f, a);
+    hipLaunchKernelGGL(bn_finalize_apply_kernel, bn_stream_grid((size_t)a.N * a.Ho * a.Wo, a.C), dim3(256), 0, st, sums, f, a);
     AESR_LAUNCH_CHECK("bn_finalize_apply");
     return AESR_OK;
 }
@@ -641,14 +503,8 @@ int aesr_launch_bn_finalize_apply(const double* sums, const double* counts, cons
 int aesr_launch_bn_bwd_finalize_apply(const double* sums, const double* counts, float* coef, float* dgamma, float* dbeta, int G,
                                       const BnBwdArgs& a, hipStream_t st) {
     if (int e = bn_check_c(a.C, "bn_bwd_finalize_apply")) return e;
-    BnCounts cnt;
-    for (int g = 0; g < 4; ++g) cnt.c[g] = (counts && g < G) ? counts[g] : 1.0;
-    const size_t total = (size_t)a.N * a.H * a.W * (a.C / 4);
-    int grid = (int)((total + 255) / 256);
-    if (grid > 4096) grid = 4096;
-    if (a.mode == BN_MODE_POOL) hipLaunchKernelGGL(bn_bwd_finalize_apply_kernel<BN_MODE_POOL>, dim3(grid), dim3(256), 0, st, sums, cnt, coef, dgamma, dbeta, G, a);
-    else if (a.mode == BN_MODE_UP) hipLaunchKernelGGL(bn_bwd_finalize_apply_kernel<BN_MODE_UP>, dim3(grid), dim3(256), 0, st, sums, cnt, coef, dgamma, dbeta, G, a);
-    else hipLaunchKernelGGL(bn_bwd_finalize_apply_kernel<0>, dim3(grid), dim3(256), 0, st, sums, cnt, coef, dgamma, dbeta, G, a);
+    BN_LAUNCH_MODE(bn_bwd_finalize_apply_kernel, a.mode, bn_stream_grid((size_t)a.N * a.H * a.W, a.C), 0, st, sums, bn_counts(counts, G), coef,
+                   dgamma, dbeta, G, a);
     AESR_LAUNCH_CHECK("bn_bwd_finalize_apply");
     return AESR_OK;
 }

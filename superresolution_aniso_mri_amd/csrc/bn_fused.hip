@@ -13,9 +13,9 @@
 //   phase 2  EVERY workgroup adds the 256 records in a fixed order (fp64) and finalizes scale / shift (backward: the two coefficients)
 //            into LDS -- 128 KB of L2 reads per workgroup instead of a third launch; workgroup 0 also writes mean / invstd / scale /
 //            shift for the backward pass and updates the running statistics, group after group (nn.BatchNorm2d semantics,
-//            bn.hip: bn_finalize_vals);
+//            bn_math.h: bn_fwd_tables / bn_bwd_tables, the same code as the finalize-inside-apply kernels of bn.hip);
 //   phase 3  out = scale * pool(y) + shift from LDS (backward: dpre = scale (g - k1 - xhat k2) act'(y)).
-// The arithmetic per element is that of bn.hip; the partial sums are formed over other partitions of the pixels, so batch
+// The arithmetic per element is bn_math.h's, as in bn.hip; the partial sums are formed over other partitions of the pixels, so batch
 // statistics agree with the three-launch path to fp64 rounding of the sums (~1e-16), i.e. to the last bit of the fp32 results
 // except on rounding ties.  The launcher refuses (returns AESR_ERR_UNSUPPORTED, callers take the three-launch path) when the layer
 // does not fit the LDS of 256 workgroups, for the un-folded Upsample mode, and on devices with fewer than 256 CUs.
@@ -32,7 +32,7 @@
 // boundary (_hip.check_device_watchdogs), as for the ring kernel.
 #include <stdlib.h>
 
-#include "aesr_kernels.h"
+#include "bn_math.h"
 
 #define BF_NB_MAX 256             // workgroups of a launch: one per CU (AESR_BN_FUSED_NB = 64 / 128 for rehearsals of several ranks on ONE device)
 #define BF_NT 512
@@ -93,34 +93,6 @@ __device__ __forceinline__ void bf_grid_barrier(unsigned* bar, int nb) {
         }
     }
     __syncthreads();
-}
-
-struct BnFusedArgs {
-    // forward: y -> out;  backward: (gout, y) -> dpre
-    const float* y; const float* gout; float* out;
-    float* rec;                     // [BF_NB][G][2][C] floats: the workgroups' partial sums
-    unsigned* bar;                  // grid-barrier state (zeroed once by the owner)
-    const float* gamma; const float* beta; float* running_mean; float* running_var; long long* nbt;
-    float* mean; float* invstd; float* scale; float* shift;       // [G][C]: written forward, read backward
-    float* coef; float* dgamma; float* dbeta;                     // backward
-    int N, H, W, C, Ho, Wo, pool;   // pool: AvgPool2d(2) follows (out / gout are [N][H/2][W/2][C])
-    int RU, upi, nunits, unit_fl, gunit_fl;      // rows per unit, units per image, units, floats of a unit of y / of the gathered gradient
-    int G, update_running, act;
-    int nb;                         // workgroups of the launch (64, 128 or 256)
-    // data parallel (SyncBN over peer-mapped regions, p2p.hip): world > 0
-    int world, rank, slot, p2p_spins;      // p2p_spins: polls before a wait for a peer gives up (AESR_P2P_SPINS; ~4 us each after the first 4096)
-    const unsigned* gen;            // device word: the step generation (same on every rank; aesr_p2p_tick advances it once per step)
-    unsigned char* peers[8];        // every rank's exchange region as mapped into this process (peers[rank] = this rank's own)
-    float momentum, eps, slope;
-    double counts[4];
-    int nstart[5];
-};
-
-__device__ __forceinline__ int bf_group_of(const BnFusedArgs& a, int n) {
-    int g = 0;
-    for (int k = 1; k < a.G; ++k)
-        if (n >= a.nstart[k]) g = k;
-    return g;
 }
 
 // block reduction of the threads' (s, q) quads that share a channel quad (tid % C4) -> tot[g][2][C] (floats), fixed order
@@ -247,7 +219,7 @@ __global__ __launch_bounds__(BF_NT, 2) void bn_fused_fwd_kernel(BnFusedArgs a) {
     for (int u = u0; u < u1; ++u) {
         const int n = u / a.upi, r0 = (u - n * a.upi) * a.RU;
         const int nr = min(a.RU, a.H - r0);
-        const int g = bf_group_of(a, n);
+        const int g = bn_group_of(a.G, a.nstart, n);
         if (g != cur_g) {
             if (cur_g >= 0) bf_flush(red, tot, cur_g, C, s, q);
             cur_g = g;
@@ -274,66 +246,31 @@ __global__ __launch_bounds__(BF_NT, 2) void bn_fused_fwd_kernel(BnFusedArgs a) {
     else __syncthreads();
     for (int o = tid; o < (GC2 >> 2); o += BF_NT) bf_store_sc1(a.rec, (size_t)BF_NB * GC2 * 4, (b * GC2 + o * 4) * 4, *(const f32x4*)(tot + o * 4));
     bf_grid_barrier(a.bar, BF_NB);
-    // ---- phase 2: totals of all workgroups, finalize (bn.hip: bn_finalize_vals / bn_finalize_apply_kernel) ----
+    // ---- phase 2: totals of all workgroups, finalize ----
     bf_totals(a.rec, GC2, red, totd, BF_NB);
     if (a.world > 0) bf_exchange(a, GC2, totd);
-    const int GC = a.G * C;
-    for (int i = tid; i < GC; i += BF_NT) {
-        const int g = i / C, c = i - g * C;
-        const double M = a.counts[g];
-        const double mu = totd[(g * 2 + 0) * C + c] / M;
-        double var = totd[(g * 2 + 1) * C + c] / M - mu * mu;
-        if (var < 0.0) var = 0.0;
-        const float m = (float)mu, iv = (float)(1.0 / sqrt(var + (double)a.eps));
-        const float sc = a.gamma[c] * iv, sh = a.beta[c] - m * sc;
-        s_sc[i] = sc;
-        s_sh[i] = sh;
-        if (b == 0) {
-            a.mean[i] = m;
-            a.invstd[i] = iv;
-            a.scale[i] = sc;
-            a.shift[i] = sh;
-        }
-    }
-    if (b == 0 && a.update_running) {
-        if (tid == 0 && a.nbt) *a.nbt += a.G;
-        for (int c = tid; c < C; c += BF_NT) {
-            float rm = a.running_mean[c], rv = a.running_var[c];
-            for (int g = 0; g < a.G; ++g) {          // group after group, as the reference's successive calls
-                const double M = a.counts[g];
-                const double mu = totd[(g * 2 + 0) * C + c] / M;
-                double var = totd[(g * 2 + 1) * C + c] / M - mu * mu;
-                if (var < 0.0) var = 0.0;
-                const double unb = M > 1.0 ? var * M / (M - 1.0) : var;
-                rm = (1.f - a.momentum) * rm + a.momentum * (float)mu;
-                rv = (1.f - a.momentum) * rv + a.momentum * (float)unb;
-            }
-            a.running_mean[c] = rm;
-            a.running_var[c] = rv;
-        }
-    }
+    bn_fwd_tables<BF_NT>(totd, a, b == 0, s_sc, s_sh);
     __syncthreads();
     // ---- phase 3: normalise (+ 2x2 mean) out of LDS ----
     const int c4 = tid % C4;
     for (int u = u0; u < u1; ++u) {
         const int n = u / a.upi, r0 = (u - n * a.upi) * a.RU;
         const int nr = min(a.RU, a.H - r0);
-        const int g = bf_group_of(a, n);
+        const int g = bn_group_of(a.G, a.nstart, n);
         const f32x4 sc = *(const f32x4*)(s_sc + g * C + c4 * 4), sh = *(const f32x4*)(s_sh + g * C + c4 * 4);
         const f32x4* src = (const f32x4*)(data + (size_t)(u - u0) * a.unit_fl);
         if (!a.pool) {
             f32x4* dst = (f32x4*)(a.out + ((size_t)n * a.H + r0) * a.W * C);
             const int cnt4 = nr * a.W * C4;
-            for (int e = tid; e < cnt4; e += BF_NT) dst[e] = src[e] * sc + sh;
+            for (int e = tid; e < cnt4; e += BF_NT) dst[e] = bn_fwd_elem(src[e], sc, sh);
         } else {
             const int p = r0 >> 1;                    // RU == 2: the unit is one row pair
             if (nr == 2 && p < a.Ho) {
                 f32x4* dst = (f32x4*)(a.out + ((size_t)n * a.Ho + p) * a.Wo * C);
                 for (int o = tid; o < a.Wo * C4; o += BF_NT) {
                     const int xo = o / C4;
-                    const f32x4 v00 = src[(2 * xo) * C4 + c4], v01 = src[(2 * xo + 1) * C4 + c4];
-                    const f32x4 v10 = src[(a.W + 2 * xo) * C4 + c4], v11 = src[(a.W + 2 * xo + 1) * C4 + c4];
-                    dst[o] = (((v00 + v01) + (v10 + v11)) * 0.25f) * sc + sh;
+                    const f32x4* w = src + (2 * xo) * C4 + c4;          // the 2x2 window: rows W * C4 apart
+                    dst[o] = bn_fwd_elem(bn_pool2x2(w[0], w[C4], w[a.W * C4], w[a.W * C4 + C4]), sc, sh);
                 }
             }
         }
@@ -360,13 +297,13 @@ __global__ __launch_bounds__(BF_NT, 2) void bn_fused_bwd_kernel(BnFusedArgs a) {
     for (int u = u0; u < u1; ++u) {
         const int n = u / a.upi, r0 = (u - n * a.upi) * a.RU;
         const int nr = min(a.RU, a.H - r0);
-        const int g = bf_group_of(a, n);
+        const int g = bn_group_of(a.G, a.nstart, n);
         if (g != cur_g) {
             if (cur_g >= 0) bf_flush(red, tot, cur_g, C, s1, s2);
             cur_g = g;
             s1 = s2 = (f32x4){0.f, 0.f, 0.f, 0.f};
-            mu = *(const f32x4*)(a.mean + g * C + c4 * 4);
-            iv = *(const f32x4*)(a.invstd + g * C + c4 * 4);
+            mu = *(const f32x4*)(a.mean_in + g * C + c4 * 4);
+            iv = *(const f32x4*)(a.invstd_in + g * C + c4 * 4);
         }
         const f32x4* src = (const f32x4*)(a.y + ((size_t)n * a.H + r0) * a.W * C);
         f32x4* dy = (f32x4*)(data + (size_t)(u - u0) * ustride);
@@ -424,33 +361,18 @@ __global__ __launch_bounds__(BF_NT, 2) void bn_fused_bwd_kernel(BnFusedArgs a) {
     else __syncthreads();
     for (int o = tid; o < (GC2 >> 2); o += BF_NT) bf_store_sc1(a.rec, (size_t)BF_NB * GC2 * 4, (b * GC2 + o * 4) * 4, *(const f32x4*)(tot + o * 4));
     bf_grid_barrier(a.bar, BF_NB);
-    // ---- phase 2: coefficients (bn.hip: bn_bwd_finalize_apply_kernel) ----
+    // ---- phase 2: coefficients ----
     bf_totals(a.rec, GC2, red, totd, BF_NB);
     if (a.world > 0) bf_exchange(a, GC2, totd);
-    for (int i = tid; i < GC2; i += BF_NT) {
-        const int g = i / (2 * C);
-        const float k = (float)(totd[i] / a.counts[g]);
-        s_k[i] = k;
-        if (b == 0) a.coef[i] = k;
-    }
-    if (b == 0)
-        for (int c = tid; c < C; c += BF_NT) {
-            double dgm = 0.0, dbt = 0.0;
-            for (int g = 0; g < a.G; ++g) {
-                dbt += totd[(g * 2 + 0) * C + c];
-                dgm += totd[(g * 2 + 1) * C + c];
-            }
-            a.dgamma[c] = (float)dgm;
-            a.dbeta[c] = (float)dbt;
-        }
+    bn_bwd_tables<BF_NT>(totd, a.counts.c, a.G, C, b == 0, s_k, a.coef, a.dgamma, a.dbeta);
     __syncthreads();
     // ---- phase 3: dpre = scale (g - k1 - xhat k2) act'(y) ----
     for (int u = u0; u < u1; ++u) {
         const int n = u / a.upi, r0 = (u - n * a.upi) * a.RU;
         const int nr = min(a.RU, a.H - r0);
-        const int g = bf_group_of(a, n);
-        const f32x4 m = *(const f32x4*)(a.mean + g * C + c4 * 4), v_iv = *(const f32x4*)(a.invstd + g * C + c4 * 4);
-        const f32x4 sc = *(const f32x4*)(a.scale + g * C + c4 * 4);
+        const int g = bn_group_of(a.G, a.nstart, n);
+        const f32x4 m = *(const f32x4*)(a.mean_in + g * C + c4 * 4), v_iv = *(const f32x4*)(a.invstd_in + g * C + c4 * 4);
+        const f32x4 sc = *(const f32x4*)(a.scale_in + g * C + c4 * 4);
         const f32x4 k1 = *(const f32x4*)(s_k + (g * 2 + 0) * C + c4 * 4), k2 = *(const f32x4*)(s_k + (g * 2 + 1) * C + c4 * 4);
         const f32x4* dy = (const f32x4*)(data + (size_t)(u - u0) * ustride);
         const f32x4* dg = dy + (a.unit_fl >> 2);
@@ -466,11 +388,7 @@ __global__ __launch_bounds__(BF_NT, 2) void bn_fused_bwd_kernel(BnFusedArgs a) {
                 const int x = (e / C4) % a.W, xo = x >> 1;
                 if (prow && xo < a.Wo) gg = dg[xo * C4 + c4];
             }
-            const f32x4 xh = (yv - m) * v_iv;
-            f32x4 d = sc * (gg - k1 - xh * k2);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) d[k] *= act_grad_from_output(yv[k], a.act, a.slope);
-            dst[e] = d;
+            dst[e] = bn_bwd_elem(yv, gg, m, v_iv, sc, k1, k2, a.act, a.slope);
         }
     }
 }
@@ -528,6 +446,10 @@ bool aesr_bn_fused1_ok(int N, int H, int W, int C, int pool, int G, int backward
 
 int aesr_launch_bn_fused(BnFusedArgs a, int backward, hipStream_t st) {
     size_t shmem = 0;
+    if (a.world > 0) {
+        const char* e = getenv("AESR_P2P_SPINS");             // tests shorten the wait for a peer that never comes (default P2P_SPIN_LIMIT: ~7 s -- the peer-skew tolerance of AESR_SYNCBN=p2p)
+        a.p2p_spins = e && atoi(e) > 0 ? atoi(e) : P2P_SPIN_LIMIT;
+    }
     if (!bf_plan(a, backward, &shmem) || !bf_device_ok()) {
         aesr_set_error("bn_fused: %d x %d x %d x %d (%d groups) does not fit the one-launch form (aesr_bn_fused1_supported)", a.N, a.H, a.W, a.C, a.G);
         return AESR_ERR_UNSUPPORTED;
@@ -536,26 +458,6 @@ int aesr_launch_bn_fused(BnFusedArgs a, int backward, hipStream_t st) {
     else hipLaunchKernelGGL(bn_fused_fwd_kernel, dim3(a.nb), dim3(BF_NT), shmem, st, a);
     AESR_LAUNCH_CHECK(backward ? "bn_fused_bwd" : "bn_fused_fwd");
     return AESR_OK;
-}
-
-int aesr_bn_fused_run(const float* y, const float* gout, float* out, float* rec, unsigned* bar, const float* gamma, const float* beta,
-                      float* running_mean, float* running_var, long long* nbt, float* mean, float* invstd, float* scale, float* shift, float* coef,
-                      float* dgamma, float* dbeta, int N, int H, int W, int C, int pool, int G, const int* nstart, const double* counts,
-                      float momentum, float eps, int update_running, int act, float slope, int backward, const BnP2P* p2p, hipStream_t st) {
-    BnFusedArgs a = {};
-    if (p2p) {
-        const char* e = getenv("AESR_P2P_SPINS");             // tests shorten the wait for a peer that never comes (default P2P_SPIN_LIMIT: ~7 s -- the peer-skew tolerance of AESR_SYNCBN=p2p)
-        a.p2p_spins = e && atoi(e) > 0 ? atoi(e) : P2P_SPIN_LIMIT;
-        a.world = p2p->world; a.rank = p2p->rank; a.slot = p2p->slot; a.gen = p2p->gen;
-        for (int r = 0; r < 8; ++r) a.peers[r] = r < p2p->world ? (unsigned char*)p2p->peers[r] : nullptr;
-    }
-    a.y = y; a.gout = gout; a.out = out; a.rec = rec; a.bar = bar; a.gamma = gamma; a.beta = beta; a.running_mean = running_mean;
-    a.running_var = running_var; a.nbt = nbt; a.mean = mean; a.invstd = invstd; a.scale = scale; a.shift = shift; a.coef = coef;
-    a.dgamma = dgamma; a.dbeta = dbeta; a.N = N; a.H = H; a.W = W; a.C = C; a.pool = pool; a.Ho = pool ? H / 2 : H; a.Wo = pool ? W / 2 : W;
-    a.G = G; a.update_running = update_running; a.act = act; a.momentum = momentum; a.eps = eps; a.slope = slope;
-    for (int g = 0; g < 4; ++g) a.counts[g] = g < G ? counts[g] : 1.0;
-    for (int g = 0; g <= 4; ++g) a.nstart[g] = g <= G ? nstart[g] : nstart[G];
-    return aesr_launch_bn_fused(a, backward, st);
 }
 
 // the step generation of the peer exchange: advanced once per step on every rank (a graph node like any other kernel)

@@ -57,7 +57,7 @@ __device__ __forceinline__ float wino_slope(int act, float slope) { return act =
 // co0 + nb * 16 + 4 g of each of its NB accumulator sets.  okn: the lane has a tile (false: nothing is read or stored);
 // so: byte offset of a channel split's slab, on the plain and the 2x2-summing stores (the POST forms take no split).
 // POST: eval-mode BatchNorm (a per-channel affine behind the activation) and the AvgPool2d(2) that follows it -- a lane's 2 x 2
-// tile IS one pooling window.
+// tile IS one pooling window.  It restates bn_math.h's order of operations (bn_pool2x2, bn_fwd_elem) on its own registers.
 // From the enclosing scope: a (WinoArgs), acc[16][NB], rs_out, rs_ys, outH, outW, nslope, mslope, sigm.
 #define WINO_STORE_TILE(NB, MASK, POST, okn, n, y0, x0, co0, g, so)                                                                          \
     {                                                                                                                                        \

@@ -597,31 +597,26 @@ class SequentialRunner:
             hit = cache.get(id(bn))
             if hit is not None and hit[0] == key and not torch.cuda.is_current_stream_capturing():
                 return dict(hit[1])
-        sums = counts = None
+        sums = None
+        counts = [float((nstart[g + 1] - nstart[g]) * H * W) * self.count_scale for g in range(G)] if use_batch else None   # host values
+        st["counts"] = counts
         if use_batch:
             partial = torch.empty((G * _hip.BN_NWG * 2 * C,), device=dev, dtype=torch.float32)
-            counts = [float((nstart[g + 1] - nstart[g]) * H * W) * self.count_scale for g in range(G)]   # host values
-            st["counts"] = counts
-            if (self.sync_bn is None and out is not None and bn_fused_enabled() and bn_fused_pays(N, H, W, C)
-                    and lib.aesr_bn_fused1_supported(N, H, W, C, run_mode, G, 0)):
-                # small batch: statistics, finalize and apply in ONE launch, the layer resident in LDS in between
+            local = (self.sync_bn is None and out is not None and bn_fused_enabled() and bn_fused_pays(N, H, W, C)
+                     and lib.aesr_bn_fused1_supported(N, H, W, C, run_mode, G, 0))
+            if local or (self.sync_bn is not None and out is not None and self._p2p_fits(N, H, W, C, run_mode, G, 0)):
+                # small batch: statistics, finalize and apply in ONE launch, the layer resident in LDS in between.  Data parallel with the peer
+                # exchange: the same launch; workgroup 0 writes this rank's sums into every rank's region and every workgroup adds all
+                # ranks' sums in rank order before it normalises
                 ws = torch.empty((lib.aesr_bn_fused1_workspace_floats(C, G),), device=dev, dtype=torch.float32)
-                check(lib.aesr_bn_fused1_fwd(ptr(y), ptr(out), ptr(ws), ptr(self._bn_barrier(dev)), _hip.double_array(counts), ptr(bn.weight),
-                                             ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked),
-                                             ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]), ptr(st["shift"]), N, H, W, C, run_mode, G,
-                                             _hip.int_array(nstart), momentum, float(bn.eps), int(update), stream()), "aesr_bn_fused1_fwd")
-                st["applied"] = True
-                return st
-            if self.sync_bn is not None and out is not None and self._p2p_fits(N, H, W, C, run_mode, G, 0):
-                # data parallel, peer exchange: the same ONE launch; workgroup 0 writes this rank's sums into every rank's region and
-                # every workgroup adds all ranks' sums in rank order before it normalises
-                p = self.sync_p2p
-                ws = torch.empty((lib.aesr_bn_fused1_workspace_floats(C, G),), device=dev, dtype=torch.float32)
-                check(lib.aesr_bn_fused1_fwd_p2p(ptr(y), ptr(out), ptr(ws), ptr(self._bn_barrier(dev)), _hip.double_array(counts), ptr(bn.weight),
-                                                 ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked),
-                                                 ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]), ptr(st["shift"]), N, H, W, C, run_mode, G,
-                                                 _hip.int_array(nstart), momentum, float(bn.eps), int(update), p.peers, p.world, p.rank,
-                                                 p.next_slot(), ptr(p.gen), stream()), "aesr_bn_fused1_fwd_p2p")
+                args = (ptr(y), ptr(out), ptr(ws), ptr(self._bn_barrier(dev)), _hip.double_array(counts), ptr(bn.weight), ptr(bn.bias),
+                        ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked), ptr(st["mean"]), ptr(st["invstd"]),
+                        ptr(st["scale"]), ptr(st["shift"]), N, H, W, C, run_mode, G, _hip.int_array(nstart), momentum, float(bn.eps), int(update))
+                if local:
+                    check(lib.aesr_bn_fused1_fwd(*args, stream()), "aesr_bn_fused1_fwd")
+                else:
+                    p = self.sync_p2p
+                    check(lib.aesr_bn_fused1_fwd_p2p(*args, p.peers, p.world, p.rank, p.next_slot(), ptr(p.gen), stream()), "aesr_bn_fused1_fwd_p2p")
                 st["applied"] = True
                 return st
             if self.sync_bn is None:        # single process: statistics -> finalize without the sums round trip
@@ -636,7 +631,6 @@ class SequentialRunner:
                   "aesr_bn_stats")
             self.sync_bn(sums)
             if out is not None and lib.aesr_bn_fused_supported(C, G):
-                st["counts"] = counts
                 check(lib.aesr_bn_finalize_apply(ptr(sums), _hip.double_array(counts), ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
                                                  ptr(bn.running_var), ptr(bn.num_batches_tracked), ptr(st["mean"]), ptr(st["invstd"]),
                                                  ptr(st["scale"]), ptr(st["shift"]), ptr(y), ptr(out), N, H, W, C, run_mode, G,
@@ -644,7 +638,6 @@ class SequentialRunner:
                       "aesr_bn_finalize_apply")
                 st["applied"] = True
                 return st
-        st["counts"] = counts
         check(lib.aesr_bn_finalize(ptr(sums), _hip.double_array(counts) if counts else None, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
                                    ptr(bn.running_var), ptr(bn.num_batches_tracked), ptr(st["mean"]), ptr(st["invstd"]),
                                    ptr(st["scale"]), ptr(st["shift"]), C, G, momentum, float(bn.eps), int(use_batch),
@@ -857,19 +850,18 @@ class SequentialRunner:
                 dgamma, dbeta = self._grad_dst(s.mod.weight, grads), self._grad_dst(s.mod.bias, grads)
                 dpre = _empty((N, H, W, C), y)
                 _pb("bn_bwd", 0.0, 4.0 * (g.numel() + 2.0 * N * H * W * C))
-                if (self.sync_bn is None and bn_fused_enabled() and bn_fused_pays(N, H, W, C)
-                        and lib.aesr_bn_fused1_supported(N, H, W, C, s.run_mode, G, 1)):
+                local = (self.sync_bn is None and bn_fused_enabled() and bn_fused_pays(N, H, W, C)
+                         and lib.aesr_bn_fused1_supported(N, H, W, C, s.run_mode, G, 1))
+                if local or (self.sync_bn is not None and self._p2p_fits(N, H, W, C, s.run_mode, G, 1)):
                     ws = torch.empty((lib.aesr_bn_fused1_workspace_floats(C, G),), device=dev, dtype=torch.float32)
-                    check(lib.aesr_bn_fused1_bwd(ptr(g), ptr(y), ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]), ptr(ws),
-                                                 ptr(self._bn_barrier(dev)), _hip.double_array(st["counts"][:G]), ptr(coef), ptr(dgamma), ptr(dbeta),
-                                                 ptr(dpre), N, H, W, C, s.run_mode, prev.act, prev.slope, G, nsa, stream()), "aesr_bn_fused1_bwd")
-                elif self.sync_bn is not None and self._p2p_fits(N, H, W, C, s.run_mode, G, 1):
-                    p = self.sync_p2p
-                    ws = torch.empty((lib.aesr_bn_fused1_workspace_floats(C, G),), device=dev, dtype=torch.float32)
-                    check(lib.aesr_bn_fused1_bwd_p2p(ptr(g), ptr(y), ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]), ptr(ws),
-                                                     ptr(self._bn_barrier(dev)), _hip.double_array(st["counts"][:G]), ptr(coef), ptr(dgamma),
-                                                     ptr(dbeta), ptr(dpre), N, H, W, C, s.run_mode, prev.act, prev.slope, G, nsa, p.peers, p.world,
-                                                     p.rank, p.next_slot(), ptr(p.gen), stream()), "aesr_bn_fused1_bwd_p2p")
+                    args = (ptr(g), ptr(y), ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]), ptr(ws), ptr(self._bn_barrier(dev)),
+                            _hip.double_array(st["counts"][:G]), ptr(coef), ptr(dgamma), ptr(dbeta), ptr(dpre), N, H, W, C, s.run_mode, prev.act,
+                            prev.slope, G, nsa)
+                    if local:
+                        check(lib.aesr_bn_fused1_bwd(*args, stream()), "aesr_bn_fused1_bwd")
+                    else:
+                        p = self.sync_p2p
+                        check(lib.aesr_bn_fused1_bwd_p2p(*args, p.peers, p.world, p.rank, p.next_slot(), ptr(p.gen), stream()), "aesr_bn_fused1_bwd_p2p")
                 elif self.sync_bn is None:
                     check(lib.aesr_bn_bwd(ptr(g), ptr(y), ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]), ptr(partial),
                                           _hip.double_array(st["counts"][:G]), ptr(coef), ptr(dgamma), ptr(dbeta), ptr(dpre), N, H, W,

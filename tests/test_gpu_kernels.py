@@ -442,6 +442,69 @@ def test_bn_groups_fwd_bwd(hip, mode, shape):
         assert torch.equal(got, want)
 
 
+@pytest.mark.parametrize("mode", [0, 1])
+def test_bn_tables_too_large_for_the_prologue(hip, mode):
+    """G * C = 2048 > 1024: the finalize-inside-apply kernels have no room for their LDS tables.  aesr_bn_finalize_apply refuses (and
+    writes nothing), aesr_bn_bwd_apply takes the separate bn_bwd_finalize launch and then bn_bwd_apply -- the one route through those two
+    kernels with more than one group.  Both groups, forward and backward, against nn.BatchNorm2d evaluated in float64 on the CPU."""
+    N, H, W, C, G = 4, 3, 3, 1024, 2
+    nstart = [0, 2, 4]
+    g = torch.Generator().manual_seed(7 + mode)
+    y = F.leaky_relu(torch.randn(N, C, H, W, generator=g), 0.01)
+    y64 = y.double().requires_grad_(True)
+    bn = torch.nn.BatchNorm2d(C)
+    with torch.no_grad():
+        bn.weight.normal_(generator=g)
+        bn.bias.normal_(generator=g)
+    gam, bet = D(bn.weight.detach().clone()), D(bn.bias.detach().clone())
+    bn = bn.double().train()
+    post = (lambda t: F.avg_pool2d(t, 2)) if mode == 1 else (lambda t: t)
+    ref = torch.cat([post(bn(y64[a:b])) for a, b in zip(nstart[:-1], nstart[1:])])       # group after group: the running statistics
+    gout = torch.randn(ref.shape, generator=g)
+    (ref * gout.double()).sum().backward()
+    L = hip.lib
+    assert L.aesr_bn_fused_supported(C, G) == 0
+    yd, god = D(nhwc(y)), D(nhwc(gout))
+    ns = hip.int_array(nstart)
+    counts = hip.double_array([2 * H * W, 2 * H * W])
+    partial = torch.empty(G * hip.BN_NWG * 2 * C, device="cuda")
+    sums = torch.empty((G, 2, C), dtype=torch.float64, device="cuda")
+    hip.check(L.aesr_bn_stats(hip.ptr(yd), hip.ptr(partial), hip.ptr(sums), H * W, C, G, ns, hip.stream()), "stats")
+    Ho, Wo = ref.shape[2:]
+    # the refusal: every output poisoned beforehand and untouched afterwards
+    poison = [torch.full((G, C), 7.0, device="cuda") for _ in range(4)] + [torch.full((C,), 7.0, device="cuda") for _ in range(2)]
+    pout, pnbt = torch.full((N, Ho, Wo, C), 7.0, device="cuda"), torch.full((), 7, dtype=torch.int64, device="cuda")
+    rc = L.aesr_bn_finalize_apply(hip.ptr(sums), counts, hip.ptr(gam), hip.ptr(bet), hip.ptr(poison[4]), hip.ptr(poison[5]), hip.ptr(pnbt),
+                                  *[hip.ptr(t) for t in poison[:4]], hip.ptr(yd), hip.ptr(pout), N, H, W, C, mode, G, ns, 0.1, 1e-5, 1, hip.stream())
+    torch.cuda.synchronize()
+    assert rc != 0 and "aesr_bn_finalize_apply" in hip.last_error()
+    assert all(bool((t == 7.0).all()) for t in poison + [pout]) and int(pnbt) == 7
+    # the three-launch sequence of the data-parallel path
+    rm, rv, nbt = torch.zeros(C, device="cuda"), torch.ones(C, device="cuda"), torch.zeros((), dtype=torch.int64, device="cuda")
+    st = [torch.full((G, C), float("nan"), device="cuda") for _ in range(4)]
+    hip.check(L.aesr_bn_finalize(hip.ptr(sums), counts, hip.ptr(gam), hip.ptr(bet), hip.ptr(rm), hip.ptr(rv), hip.ptr(nbt),
+                                 *[hip.ptr(t) for t in st], C, G, 0.1, 1e-5, 1, 1, hip.stream()), "finalize")
+    out = torch.full((N, Ho, Wo, C), float("nan"), device="cuda")
+    hip.check(L.aesr_bn_apply(hip.ptr(yd), hip.ptr(st[2]), hip.ptr(st[3]), hip.ptr(out), N, H, W, C, mode, G, ns, hip.stream()), "apply")
+    sums2 = torch.empty((G, 2, C), dtype=torch.float64, device="cuda")
+    hip.check(L.aesr_bn_bwd_reduce(hip.ptr(god), hip.ptr(yd), hip.ptr(st[0]), hip.ptr(st[1]), hip.ptr(partial), hip.ptr(sums2), N, H, W, C,
+                                   mode, G, ns, hip.stream()), "bwd_reduce")
+    coef = torch.full((G, 2, C), float("nan"), device="cuda")
+    dgam, dbet = torch.full((C,), float("nan"), device="cuda"), torch.full((C,), float("nan"), device="cuda")
+    dpre = torch.full((N, H, W, C), float("nan"), device="cuda")
+    hip.check(L.aesr_bn_bwd_apply(hip.ptr(god), hip.ptr(yd), hip.ptr(st[0]), hip.ptr(st[1]), hip.ptr(st[2]), hip.ptr(sums2), counts,
+                                  hip.ptr(coef), hip.ptr(dgam), hip.ptr(dbet), hip.ptr(dpre), N, H, W, C, mode, 1, 0.01, G, ns,
+                                  hip.stream()), "bwd_apply")
+    torch.cuda.synchronize()
+    errs = dict(out=rel_l2(nchw(out), ref.detach()), running_mean=rel_l2(rm, bn.running_mean), running_var=rel_l2(rv, bn.running_var),
+                dpre=rel_l2(nchw(dpre), y64.grad * torch.where(y64.detach() > 0, 1.0, 0.01)), dgamma=rel_l2(dgam, bn.weight.grad),
+                dbeta=rel_l2(dbet, bn.bias.grad))
+    print("bn_tables_too_large mode %d: %s" % (mode, ", ".join("%s %.2e" % kv for kv in errs.items())))
+    assert int(nbt) == 2
+    assert errs["out"] < 1e-5 and errs["running_mean"] < 1e-5 and errs["running_var"] < 1e-5
+    assert errs["dpre"] < 2e-5 and errs["dgamma"] < 2e-5 and errs["dbeta"] < 2e-5
+
+
 def test_lerp_mse_act_adam(hip):
     L = hip.lib
     g = torch.Generator().manual_seed(3)
