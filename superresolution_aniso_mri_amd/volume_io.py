@@ -22,10 +22,18 @@ _MET_NAMES = {np.dtype(v).str[1:]: k for k, v in _MET_TYPES.items()}
 
 
 class Volume:
-    """array [z,y,x] or [t,z,y,x]; spacing (x,y,z[,t]); ``meta`` = format-specific header state used when writing back."""
+    """array [z,y,x] or [t,z,y,x]; spacing (x,y,z[,t]); ``meta`` = format-specific header state used when writing back.
 
-    def __init__(self, array, spacing, fmt, meta):
+    ``origin`` (float64 [3], (x, y, z) in mm) and ``direction`` (float64 [3, 3], COLUMNS = the cosines of the x, y and z voxel axes) place
+    the volume in the patient, in SimpleITK's LPS convention: voxel index (i, j, k) sits at ``origin + direction @ (spacing * (i, j, k))``.
+    Both default to zeros / identity; a 4-D file contributes its leading 3-vector and 3x3 block."""
+
+    def __init__(self, array, spacing, fmt, meta, origin=None, direction=None):
         self.array, self.spacing, self.fmt, self.meta = array, tuple(float(s) for s in spacing), fmt, meta
+        self.origin = np.zeros(3) if origin is None else np.array(origin, dtype=np.float64).reshape(-1)[:3].copy()
+        self.direction = np.eye(3) if direction is None else np.array(direction, dtype=np.float64)[:3, :3].copy()
+        if self.origin.shape != (3,) or self.direction.shape != (3, 3):
+            raise ValueError("origin must have 3 entries and direction must be 3x3 (got %s, %s)" % (self.origin.shape, self.direction.shape))
 
     @property
     def num_frames(self):
@@ -62,7 +70,39 @@ def _read_nifti(path):
     if slope not in (0.0, 1.0) or inter != 0.0:
         if slope != 0.0:
             data = data.astype(np.float32) * np.float32(slope) + np.float32(inter)
-    return Volume(data, pixdim[1:1 + nd], "nifti", {"header": bytes(raw[:vox_offset]), "endian": end})
+    origin, direction = _nifti_geometry(path, raw, end, pixdim)
+    return Volume(data, pixdim[1:1 + nd], "nifti", {"header": bytes(raw[:vox_offset]), "endian": end}, origin, direction)
+
+
+def _nifti_geometry(path, raw, end, pixdim):
+    """(origin, direction) in LPS from a NIfTI-1 header, whose own frame is RAS.  The qform when ``qform_code > 0`` (quaternion b, c, d,
+    ``qoffset_*``, ``qfac`` = the sign of ``pixdim[0]``: -1 flips the z axis); else the sform when ``sform_code > 0`` (direction = its
+    normalised columns; their norms must agree with ``pixdim`` to 1e-4 relative, or the header contradicts the spacing this module
+    reports); else zeros and identity.  RAS -> LPS negates the x and y ROWS of both."""
+    qform_code, sform_code = struct.unpack(end + "2h", raw[252:256])
+    lps = np.array([-1.0, -1.0, 1.0])
+    if qform_code > 0:
+        b, c, d, qx, qy, qz = (float(v) for v in struct.unpack(end + "6f", raw[256:280]))
+        a2 = 1.0 - (b * b + c * c + d * d)
+        if a2 < 1e-7:          # a rotation by (almost) pi: a = 0 and (b, c, d) is made a unit vector, as the NIfTI-1 reference code does
+            s = 1.0 / np.sqrt(b * b + c * c + d * d)
+            b, c, d, a = b * s, c * s, d * s, 0.0
+        else:
+            a = np.sqrt(a2)
+        R = np.array([[a * a + b * b - c * c - d * d, 2 * (b * c - a * d), 2 * (b * d + a * c)],
+                      [2 * (b * c + a * d), a * a + c * c - b * b - d * d, 2 * (c * d - a * b)],
+                      [2 * (b * d - a * c), 2 * (c * d + a * b), a * a + d * d - c * c - b * b]])
+        if pixdim[0] < 0:
+            R[:, 2] = -R[:, 2]
+        return lps * np.array([qx, qy, qz]), lps[:, None] * R
+    if sform_code > 0:
+        A = np.array(struct.unpack(end + "12f", raw[280:328]), dtype=np.float64).reshape(3, 4)
+        norms = np.sqrt((A[:, :3] ** 2).sum(axis=0))
+        for i in range(3):
+            if not abs(norms[i] - pixdim[1 + i]) <= 1e-4 * abs(pixdim[1 + i]) or norms[i] == 0:
+                raise ValueError("%s: the sform's column %d has length %.6g but pixdim[%d] = %.6g" % (path, i, norms[i], 1 + i, pixdim[1 + i]))
+        return lps * A[:, 3], lps[:, None] * (A[:, :3] / norms)
+    return np.zeros(3), np.eye(3)
 
 
 def _write_nifti(path, vol, array, spacing):
@@ -137,7 +177,31 @@ def _read_meta(path):
         blob = zlib.decompress(blob)
     n = int(np.prod(shape))
     data = np.frombuffer(blob, dtype=dt, count=n).reshape(shape[::-1]).astype(dt.newbyteorder("="))
-    return Volume(data, spacing, "meta", {"fields": fields, "order": order})
+    origin, direction = _meta_geometry(path, fields, nd)
+    return Volume(data, spacing, "meta", {"fields": fields, "order": order}, origin, direction)
+
+
+def _meta_geometry(path, fields, nd):
+    """(origin, direction) of a MetaImage header, which is LPS already.  ``Offset`` (or its synonyms ``Position`` / ``Origin``) is the
+    origin.  ``TransformMatrix`` (or ``Rotation`` / ``Orientation``) holds NDims x NDims numbers; the convention implemented here is ITK's
+    MetaImageIO: it writes element [j][i] of the direction matrix at position i * NDims + j, so the numbers read row-major are the
+    TRANSPOSE of the direction matrix -- each run of NDims numbers is one voxel axis' cosines, i.e. one COLUMN of ``direction``."""
+    origin, direction = np.zeros(3), np.eye(3)
+    for key in ("Offset", "Position", "Origin"):
+        if key in fields:
+            vals = [float(t) for t in fields[key].split()]
+            if len(vals) < 3:
+                raise ValueError("%s: %s has %d entries, expected %d" % (path, key, len(vals), nd))
+            origin = np.array(vals[:3])
+            break
+    for key in ("TransformMatrix", "Rotation", "Orientation"):
+        if key in fields:
+            vals = [float(t) for t in fields[key].split()]
+            if len(vals) != nd * nd:
+                raise ValueError("%s: %s has %d entries, expected %d" % (path, key, len(vals), nd * nd))
+            direction = np.array(vals).reshape(nd, nd).T[:3, :3].copy()
+            break
+    return origin, direction
 
 
 def _write_meta(path, vol, array, spacing):

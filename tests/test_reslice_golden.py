@@ -1,0 +1,386 @@
+"""not gpu: reslicing a short-axis stack into a long-axis scan's geometry against the reference's own results (tests/golden/reslice.npz,
+written by tests/make_golden_reslice.py: the reference's ``make_lax_identity_grid`` / ``make_transform`` on float32 matrices and torch's
+CPU ``grid_sample``) and against a float64 numpy restatement kept in this file (it shares no code with the package).
+
+- The restatement of the AFFINE path (``affine_matrix``: ``inv(T_s R_s S_s) @ (T_l R_l S_l)`` in float64; ``affine_coordinates``;
+  ``trilinear``: eight corners, a corner outside the source contributes nothing, the products summed in the order dz, dy, dx in double, one
+  rounding to fp32) against the reference's output.  The reference chains six float32 matrix products, so its coordinates drift; the bound
+  is derived per case from the fixture: trilinear interpolation of the zero-padded volume is Lipschitz, |dv| <= (|dx| + |dy| + |dz|) * L
+  with L the largest difference between adjacent voxels (the zero outside counts) and d the difference between the fixture's unnormalised
+  grid and the float64 coordinates, voxel by voxel.
+- The restatement evaluated on the fixture's OWN grid against torch's output: 1e-6 absolute on [0, 1] data, the bound of the sibling kernels.
+- Nearest: equal to torch's ``mode='nearest'`` wherever every coordinate is farther than 1e-4 from a half-integer (fp32 against fp64
+  unnormalisation can round such a coordinate either way); at most 1 % of the voxels may be excluded.
+- ``make_identity_grid`` / ``make_lax_identity_grid`` / ``make_transform`` of the package equal the fixture's grids within 1e-6;
+  ``affine_between`` equals the restatement's matrix.
+- include/aesr_hip_reslice.h == ``_hip.SIGNATURES_RESLICE`` == the library's exports, disjoint from the other five tables, and partitioned
+  by GUARDED_ENTRIES / EXEMPT of tests/test_gpu_reslice.py; every refusal that is decided on the host."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+Q = 1024.0          # the fixture's volumes are uint16 counts of 1/1024 (exact in fp32)
+# tag -> (SAX [z, y, x], LAX [z, y, x], frames)
+CASES = {"oblique": ((13, 40, 36), (3, 33, 47), 1), "oblique4d": ((13, 40, 36), (3, 33, 47), 3), "odd": ((5, 9, 11), (2, 7, 13), 1),
+         "outside": ((13, 40, 36), (3, 33, 47), 1)}
+TOL = 1e-6                  # fp32 evaluation of the same coordinates on [0, 1] data: the bound of the sibling kernels
+HALF_MARGIN = 1e-4          # nearest: coordinates this close to a half-integer are not compared
+MAX_EXCLUDED = 0.01
+_FX = {}
+
+
+def fixture():
+    if not _FX:
+        _FX.update(np.load(os.path.join(HERE, "golden", "reslice.npz")))
+    return _FX
+
+
+def case_volume(tag):
+    """float32 [Z, Y, X] (or [T, Z, Y, X])"""
+    return (fixture()["%s/vol" % tag] / Q).astype(np.float32)
+
+
+def case_matrices(tag):
+    """float64 [6, 4, 4]: S_lax, R_lax, T_lax, S_sax, R_sax, T_sax"""
+    return fixture()["%s/matrices" % tag]
+
+
+# ---- the restatement ---------------------------------------------------------------------------------------------------------------
+def affine_matrix(mats):
+    """float64 [4, 4]: LAX voxel index (x, y, z, 1) -> SAX voxel index"""
+    S_l, R_l, T_l, S_s, R_s, T_s = (np.asarray(m, dtype=np.float64) for m in mats)
+    return np.linalg.inv(T_s @ R_s @ S_s) @ (T_l @ R_l @ S_l)
+
+
+def affine_coordinates(M, lax_shape):
+    """float64 [z, y, x, 3]: ((m0 * xo + m1 * yo) + m2 * zo) + m3 per row of M, the operation order of the kernel"""
+    zo, yo, xo = np.meshgrid(*[np.arange(s, dtype=np.float64) for s in lax_shape], indexing="ij")
+    return np.stack([((M[a, 0] * xo + M[a, 1] * yo) + M[a, 2] * zo) + M[a, 3] for a in range(3)], axis=-1)
+
+
+def grid_coordinates(grid, sax_shape):
+    """float64 [z, y, x, 3]: the fp32 grid converted first, then (g + 1) / 2 * (size - 1)"""
+    size = np.array(sax_shape[::-1], dtype=np.float64)
+    return (grid.astype(np.float64) + 1.0) / 2.0 * (size - 1.0)
+
+
+def trilinear(vol, c):
+    """vol float32 [Z, Y, X], c float64 [..., 3] = (x, y, z) -> float32 [...]: zero padding, a corner outside contributes nothing"""
+    Z, Y, X = vol.shape
+    v64 = vol.astype(np.float64)
+    f = np.floor(c)
+    i0 = f.astype(np.int64)
+    w = [(f + 1.0) - c, c - f]          # w[d][..., axis]
+    acc = np.zeros(c.shape[:-1])
+    for dz in (0, 1):
+        for dy in (0, 1):
+            for dx in (0, 1):
+                ix, iy, iz = i0[..., 0] + dx, i0[..., 1] + dy, i0[..., 2] + dz
+                ok = (ix >= 0) & (ix < X) & (iy >= 0) & (iy < Y) & (iz >= 0) & (iz < Z)
+                s = v64[np.clip(iz, 0, Z - 1), np.clip(iy, 0, Y - 1), np.clip(ix, 0, X - 1)]
+                weight = (w[dz][..., 2] * w[dy][..., 1]) * w[dx][..., 0]
+                acc = acc + np.where(ok, weight * s, 0.0)
+    return acc.astype(np.float32)
+
+
+def nearest(vol, c):
+    Z, Y, X = vol.shape
+    r = np.rint(c).astype(np.int64)          # halves to even
+    ok = (r[..., 0] >= 0) & (r[..., 0] < X) & (r[..., 1] >= 0) & (r[..., 1] < Y) & (r[..., 2] >= 0) & (r[..., 2] < Z)
+    s = vol[np.clip(r[..., 2], 0, Z - 1), np.clip(r[..., 1], 0, Y - 1), np.clip(r[..., 0], 0, X - 1)]
+    return np.where(ok, s, np.float32(0)).astype(np.float32)
+
+
+def per_frame(fn, vol, c):
+    return np.stack([fn(v, c) for v in vol]) if vol.ndim == 4 else fn(vol, c)
+
+
+def lipschitz(vol):
+    """the largest difference between adjacent voxels of a [Z, Y, X] volume, the zero outside included"""
+    p = np.pad(vol.astype(np.float64), 1)
+    return max(float(np.abs(np.diff(p, axis=a)).max()) for a in range(3))
+
+
+def drift_bound(tag):
+    """float64 [z, y, x]: (|dx| + |dy| + |dz|) * L between the fixture's float32-chained grid and the float64 affine coordinates"""
+    sax_shape, lax_shape, _ = CASES[tag]
+    vol = case_volume(tag)
+    L = max(lipschitz(v) for v in vol) if vol.ndim == 4 else lipschitz(vol)
+    d = np.abs(grid_coordinates(fixture()["%s/grid" % tag], sax_shape) - affine_coordinates(affine_matrix(case_matrices(tag)), lax_shape))
+    return d.sum(axis=-1) * L, float(d.max()), L
+
+
+def away_from_halves(c):
+    """bool [...]: every coordinate farther than HALF_MARGIN from a half-integer"""
+    return (np.abs(c - np.floor(c) - 0.5) > HALF_MARGIN).all(axis=-1)
+
+
+# ---- fixture and restatement -----------------------------------------------------------------------------------------------------
+def test_fixture_is_what_the_issue_asked_for():
+    fx = fixture()
+    assert [str(t) for t in fx["tags"]] == list(CASES)
+    for tag, (sax_shape, lax_shape, frames) in CASES.items():
+        lead = (frames,) if frames > 1 else ()
+        assert fx["%s/vol" % tag].shape == lead + sax_shape and fx["%s/vol" % tag].dtype == np.uint16 and int(fx["%s/vol" % tag].max()) <= Q
+        assert fx["%s/matrices" % tag].shape == (6, 4, 4) and fx["%s/matrices" % tag].dtype == np.float64
+        assert tuple(fx["%s/sax_shape" % tag]) == sax_shape and tuple(fx["%s/lax_shape" % tag]) == lax_shape
+        assert fx["%s/grid" % tag].shape == lax_shape + (3,) and fx["%s/grid" % tag].dtype == np.float32
+        for mode in ("linear", "nearest"):
+            assert fx["%s/%s" % (tag, mode)].shape == lead + lax_shape and fx["%s/%s" % (tag, mode)].dtype == np.float32
+    assert all(s % 4 for s in CASES["odd"][0] + CASES["odd"][1])
+    # what the cases exercise: interior, the fading one-voxel border and the all-zero outside in `oblique`; nothing but outside in `outside`
+    c = grid_coordinates(fx["oblique/grid"], CASES["oblique"][0])
+    size = np.array(CASES["oblique"][0][::-1], dtype=np.float64)
+    inside = np.all((c >= 0) & (c <= size - 1), axis=-1)
+    reach = np.all((c > -1) & (c < size), axis=-1)
+    assert 0.5 < inside.mean() < 0.95 and (reach & ~inside).mean() > 0.05 and (~reach).sum() > 100
+    assert (fx["oblique/linear"][~reach] == 0).all() and (fx["oblique/linear"][inside] > 0).all()
+    assert not fx["outside/linear"].any() and not fx["outside/nearest"].any()
+    assert np.array_equal(fx["oblique/grid"], fx["oblique4d/grid"]) and not np.array_equal(fx["oblique4d/vol"][0], fx["oblique4d/vol"][1])
+    size = os.path.getsize(os.path.join(HERE, "golden", "reslice.npz"))
+    assert size < os.path.getsize(os.path.join(HERE, "golden", "z_expand.npz"))
+
+
+@pytest.mark.parametrize("tag", list(CASES))
+def test_affine_restatement_against_the_references_output(tag):
+    sax_shape, lax_shape, _ = CASES[tag]
+    got = per_frame(trilinear, case_volume(tag), affine_coordinates(affine_matrix(case_matrices(tag)), lax_shape))
+    want = fixture()["%s/linear" % tag]
+    bound, drift, L = drift_bound(tag)
+    err = np.abs(got.astype(np.float64) - want)
+    print("%-10s coordinate drift %.3g voxel, L = %.3g, largest bound %.3g, max |restatement - reference| = %.3g, worst err / bound %.3g"
+          % (tag, drift, L, float(bound.max()), float(err.max()), float((err / np.maximum(bound, 1e-300)).max()) if err.max() else 0.0))
+    assert got.shape == want.shape and got.dtype == np.float32
+    assert (err <= bound).all(), (tag, float(err.max()), float(bound.max()))
+    if tag == "outside":
+        assert not got.any()
+
+
+@pytest.mark.parametrize("tag", list(CASES))
+def test_restatement_on_the_fixtures_grid_against_torch(tag):
+    sax_shape = CASES[tag][0]
+    c = grid_coordinates(fixture()["%s/grid" % tag], sax_shape)
+    got = per_frame(trilinear, case_volume(tag), c)
+    err = float(np.abs(got.astype(np.float64) - fixture()["%s/linear" % tag]).max())
+    print("%-10s max |restatement on the grid - torch| = %.3g" % (tag, err))
+    assert err <= TOL, (tag, err)
+
+
+@pytest.mark.parametrize("tag", list(CASES))
+def test_nearest_restatement_against_torch(tag):
+    sax_shape = CASES[tag][0]
+    c = grid_coordinates(fixture()["%s/grid" % tag], sax_shape)
+    keep = away_from_halves(c)
+    got, want = per_frame(nearest, case_volume(tag), c), fixture()["%s/nearest" % tag]
+    print("%-10s excluded %.4f of the voxels, %d of them differ" % (tag, 1 - keep.mean(), int((got != want)[..., ~keep].sum())))
+    assert 1 - keep.mean() <= MAX_EXCLUDED, (tag, 1 - keep.mean())
+    assert np.array_equal(got[..., keep], want[..., keep]), tag
+
+
+def test_restatement_edge_cases():
+    vol = case_volume("odd")
+    ident = affine_coordinates(np.eye(4), vol.shape)
+    assert np.array_equal(trilinear(vol, ident), vol) and np.array_equal(nearest(vol, ident), vol)
+    assert np.array_equal(nearest(np.arange(4, dtype=np.float32).reshape(1, 1, 4) + 1, np.array([[0.5, 0, 0], [1.5, 0, 0], [2.5, 0, 0], [-0.5, 0, 0],
+                                                                                                 [3.5, 0, 0]])), np.array([1, 3, 3, 1, 0], np.float32))
+    # half a voxel outside a face: half the face value; a whole voxel outside: 0
+    one = np.ones((2, 2, 2), np.float32)
+    assert trilinear(one, np.array([[-0.5, 0.0, 0.0], [-1.0, 0.5, 0.5], [1.5, 1.0, 1.0], [2.0, 0.0, 0.0]])).tolist() == [0.5, 0.0, 0.5, 0.0]
+
+
+# ---- the package's host side -----------------------------------------------------------------------------------------------------
+def test_grid_functions_equal_the_references():
+    import torch
+    from evaluate.cardiac import resample_sax_to_lax as shim
+    from superresolution_aniso_mri_amd.evaluate.cardiac import resample_sax_to_lax as rs
+    assert shim.make_transform is rs.make_transform and shim.resample_sax_to_lax is rs.resample_sax_to_lax          # the root shim
+    fx = fixture()
+    lax_odd = CASES["odd"][1]
+    ident = rs.make_lax_identity_grid(lax_odd)
+    assert ident.dtype == torch.float32 and np.array_equal(ident.numpy(), fx["odd/ident"])
+    assert np.array_equal(rs.make_identity_grid(lax_odd, stackdim="first").numpy(), fx["odd/ident_first"])
+    assert np.array_equal(rs.make_identity_grid(lax_odd).numpy(), fx["odd/ident"][..., :3])
+    assert np.array_equal(rs.make_identity_grid(lax_odd, stackdim=0).numpy(), fx["odd/ident_first"])
+    with pytest.raises(ValueError, match="stackdim"):
+        rs.make_identity_grid(lax_odd, stackdim="middle")
+    for tag, (sax_shape, lax_shape, _) in CASES.items():
+        mats = [torch.from_numpy(m.astype(np.float32)) for m in case_matrices(tag)]
+        grid = rs.make_transform(rs.make_lax_identity_grid(lax_shape), lax_shape, sax_shape, *mats)
+        assert grid.dtype == torch.float32 and tuple(grid.shape) == lax_shape + (3,)
+        err = float(np.abs(grid.numpy().astype(np.float64) - fx["%s/grid" % tag]).max())
+        print("%-10s max |make_transform - reference grid| = %.3g" % (tag, err))
+        assert err <= 1e-6, (tag, err)
+    # float64 matrices give the float64 coordinates of the affine path
+    tag, (sax_shape, lax_shape, _) = "oblique", CASES["oblique"]
+    g64 = rs.make_transform(rs.make_lax_identity_grid(lax_shape).double(), lax_shape, sax_shape, *[torch.from_numpy(m) for m in case_matrices(tag)])
+    size = np.array(sax_shape[::-1], dtype=np.float64)
+    assert g64.dtype == torch.float64
+    assert np.abs((g64.numpy() + 1) / 2 * (size - 1) - affine_coordinates(affine_matrix(case_matrices(tag)), lax_shape)).max() <= 1e-9
+
+
+def test_make_transform_refuses_a_sax_side_of_one():
+    import torch
+    from superresolution_aniso_mri_amd.evaluate.cardiac import resample_sax_to_lax as rs
+    mats = [torch.from_numpy(m.astype(np.float32)) for m in case_matrices("odd")]
+    for sax_shape in ((1, 9, 11), (5, 1, 11), (5, 9, 1)):
+        with pytest.raises(ValueError, match="sax_shape"):
+            rs.make_transform(rs.make_lax_identity_grid((2, 7, 13)), (2, 7, 13), sax_shape, *mats)
+
+
+def test_geometry_and_affine_between():
+    from superresolution_aniso_mri_amd import volume_io
+    from superresolution_aniso_mri_amd.evaluate import reslice as rl
+    for tag in ("oblique", "odd"):
+        S_l, R_l, T_l, S_s, R_s, T_s = case_matrices(tag)
+        lax = rl.Geometry(np.diag(S_l)[:3], T_l[:3, 3], R_l[:3, :3])
+        sax = rl.Geometry(np.diag(S_s)[:3], T_s[:3, 3], R_s[:3, :3])
+        assert rl.index_to_world(lax).dtype == np.float64 and np.array_equal(rl.index_to_world(lax), T_l @ R_l @ S_l)
+        assert np.abs(rl.affine_between(sax, lax) - affine_matrix(case_matrices(tag))).max() <= 1e-12
+        assert np.abs(rl.affine_between(sax, sax) - np.eye(4)).max() <= 1e-12
+    vol = volume_io.Volume(np.zeros((2, 3, 4, 5), np.float32), (1.5, 1.25, 8.0, 30.0), "npy", {}, origin=(1, 2, 3), direction=R_l[:3, :3])
+    g = rl.Geometry.from_volume(vol)
+    assert g.spacing.tolist() == [1.5, 1.25, 8.0] and g.origin.tolist() == [1.0, 2.0, 3.0] and np.array_equal(g.direction, R_l[:3, :3])
+    with pytest.raises(ValueError, match="spacing"):
+        rl.Geometry((1.0, 0.0, 1.0))
+    with pytest.raises(ValueError, match="singular"):
+        rl.Geometry((1.0, 1.0, 1.0), direction=np.zeros((3, 3)))
+
+
+def test_python_interface_refusals(tmp_path, capsys):
+    import torch
+    from superresolution_aniso_mri_amd.evaluate import reslice as rl
+    from superresolution_aniso_mri_amd.evaluate.cardiac import resample_sax_to_lax as rs
+    g = rl.Geometry((1.0, 1.0, 1.0))
+    with pytest.raises(ValueError, match="interp"):
+        rl.reslice(np.zeros((3, 4, 5), np.float32), g, g, (3, 4, 5), interp="cubic")
+    with pytest.raises(ValueError, match="ref_shape"):
+        rl.reslice(np.zeros((3, 4, 5), np.float32), g, g, (4, 5))
+    with pytest.raises(ValueError, match="expected"):
+        rl.reslice(torch.zeros(4, 5), g, g, (3, 4, 5))
+    with pytest.raises(RuntimeError, match="GPU"):
+        rl.reslice(torch.zeros(3, 4, 5), g, g, (3, 4, 5))                         # a CPU tensor: no fallback
+    grid = torch.zeros(2, 7, 13, 3)
+    with pytest.raises(ValueError, match="target_shape"):
+        rs.resample_sax_to_lax(np.zeros((1, 5, 9, 11), np.float32), (2, 7, 13), grid)
+    with pytest.raises(ValueError, match="frames"):
+        rs.resample_sax_to_lax(np.zeros((2, 5, 9, 11), np.float32), (1, 2, 7, 13), grid)
+    with pytest.raises(ValueError, match="transformed_ident_grid"):
+        rs.resample_sax_to_lax(np.zeros((1, 5, 9, 11), np.float32), (1, 2, 7, 12), grid)
+    with pytest.raises(ValueError, match=r"\[T, Z, Y, X\]"):
+        rs.resample_sax_to_lax(np.zeros((5, 9, 11), np.float32), (1, 2, 7, 13), grid)
+    with pytest.raises(TypeError, match="sax_image"):
+        rs.resample_sax_to_lax("sax.nii.gz", (1, 2, 7, 13), grid)
+    np.save(str(tmp_path / "v.npy"), np.zeros((3, 4, 4), np.float32))
+    with pytest.raises(SystemExit) as e:
+        rs.main(["--sax", str(tmp_path / "v.npy"), "--lax", "l.nii.gz", "--out", str(tmp_path / "o.nii.gz")])
+    assert "no geometry" in str(e.value) and not (tmp_path / "o.nii.gz").exists()
+    with pytest.raises(SystemExit):
+        rs.parse_args(["--sax", "s.nii", "--lax", "l.nii", "--out", "o.nii", "--interp", "cubic"])
+    with pytest.raises(SystemExit):
+        rs.parse_args(["--sax", "s.nii", "--out", "o.nii"])
+    capsys.readouterr()
+    a = rs.parse_args(["--sax", "s.nii", "--lax", "l.nii", "--out", "o.nii"])
+    assert (a.sax, a.lax, a.out, a.interp) == ("s.nii", "l.nii", "o.nii", "linear")
+
+
+# ---- the sixth header ------------------------------------------------------------------------------------------------------------
+def _declared(header):
+    hdr = open(os.path.join(ROOT, "include", header)).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    return set(re.findall(r"\b(aesr_[a-z0-9_]+)\s*\(", hdr))
+
+
+def test_reslice_header_table_and_exports_agree():
+    from superresolution_aniso_mri_amd import _hip
+    declared = _declared("aesr_hip_reslice.h")
+    assert declared == set(_hip.SIGNATURES_RESLICE) == {"aesr_reslice_affine", "aesr_reslice_grid"}
+    others = (set(_hip.SIGNATURES) | set(_hip.SIGNATURES_PREPROC) | set(_hip.SIGNATURES_DATAPREP) | set(_hip.SIGNATURES_TRAIN)
+              | set(_hip.SIGNATURES_BASELINES))
+    for header in ("aesr_hip.h", "aesr_hip_preproc.h", "aesr_hip_dataprep.h", "aesr_hip_train.h", "aesr_hip_baselines.h"):
+        others |= _declared(header)
+    assert not declared & others
+    lib = ctypes.CDLL(_hip.LIB_PATH)
+    P, I = ctypes.c_void_p, ctypes.c_int
+    for name in declared:
+        assert getattr(lib, name, None) is not None, "%s is declared in include/aesr_hip_reslice.h but not exported" % name
+        res, args = _hip.SIGNATURES_RESLICE[name]
+        assert getattr(_hip.lib, name).argtypes == args and getattr(_hip.lib, name).restype == res
+    assert _hip.SIGNATURES_RESLICE["aesr_reslice_affine"] == (I, [P, P] + [I] * 7 + [_hip.DP, I, P])
+    assert _hip.SIGNATURES_RESLICE["aesr_reslice_grid"] == (I, [P, P, P] + [I] * 7 + [I, P])
+    hdr = open(os.path.join(ROOT, "include", "aesr_hip_reslice.h")).read()
+    assert (_hip.RESLICE_NEAREST, _hip.RESLICE_LINEAR) == tuple(
+        int(re.search(r"#define %s (\d+)" % n, hdr).group(1)) for n in ("AESR_RESLICE_NEAREST", "AESR_RESLICE_LINEAR")) == (0, 1)
+    # the modes of aesr_resample2_* keep their names and values
+    assert (_hip.RS_POOL, _hip.RS_NEAREST, _hip.RS_BILINEAR) == (1, 2, 3)
+
+
+def test_guard_band_cases_and_exemptions_partition_the_reslice_abi():
+    """The rule of tests/test_memguard_host.py::test_case_table_and_exemptions_partition_the_abi for the sixth table."""
+    import test_gpu_reslice as tg
+    from superresolution_aniso_mri_amd import _hip
+    covered, exempt, names = set(tg.GUARDED_ENTRIES), set(tg.EXEMPT), set(_hip.SIGNATURES_RESLICE)
+    assert not (covered & exempt) and covered | exempt == names, (sorted(names - covered - exempt), sorted((covered | exempt) - names))
+    for name, reason in tg.EXEMPT.items():
+        assert reason and name.endswith(("_bytes", "_size")), "%s is a launch entry point: it needs a case" % name
+    assert covered == {"aesr_reslice_affine", "aesr_reslice_grid"}
+    assert callable(tg.test_affine_guard_bands_poisons_and_offset_pointers) and callable(tg.test_grid_guard_bands_poisons_and_offset_pointers)
+
+
+# ---- refusals decided on the host ------------------------------------------------------------------------------------------------
+def test_entry_points_check_their_arguments_on_the_host():
+    """Every refusal comes before anything touches the device: callable without a GPU; the device pointers below are never dereferenced."""
+    from superresolution_aniso_mri_amd import _hip
+    P = ctypes.c_void_p
+    src, out, grid = P(1 << 20), P(1 << 24), P(1 << 28)
+    m = np.ascontiguousarray(np.eye(4)[:3], np.float64)
+    DA = lambda a: a.ctypes.data_as(_hip.DP)          # noqa: E731
+    names = ["src", "out", "N", "Zs", "Hs", "Ws", "Zo", "Ho", "Wo", "m_host", "interp", "stream"]
+    ok = [src, out, 2, 5, 9, 11, 2, 7, 13, DA(m), 1, None]
+    err = _hip.last_error
+
+    def affine(**over):
+        args = list(ok)
+        for k, v in over.items():
+            args[names.index(k)] = v
+        return _hip.lib.aesr_reslice_affine(*args)
+
+    def by_grid(**over):
+        args = dict(zip(names, ok))
+        args.update(over)
+        g = args.pop("grid", grid)
+        args.pop("m_host")
+        return _hip.lib.aesr_reslice_grid(args.pop("src"), g, *args.values())
+
+    for call, fn in ((affine, "aesr_reslice_affine"), (by_grid, "aesr_reslice_grid")):
+        assert call(src=None) == 1 and "src is a null" in err() and fn in err()
+        assert call(out=None) == 1 and "out is a null" in err()
+        assert call(src=P((1 << 20) + 2)) == 1 and "src is not 4-byte" in err()
+        assert call(out=P((1 << 24) + 1)) == 1 and "out is not 4-byte" in err()
+        assert call(N=0) == 1 and "N=0" in err() and call(N=-3) == 1
+        for dim in ("Zs", "Hs", "Ws"):
+            assert call(**{dim: 0}) == 1 and "Zs, Hs, Ws" in err() and call(**{dim: -4}) == 1
+        for dim in ("Zo", "Ho", "Wo"):
+            assert call(**{dim: 0}) == 1 and "Zo, Ho, Wo" in err() and call(**{dim: -4}) == 1
+        for bad in (2, -1, 3):
+            assert call(interp=bad) == 1 and "interp=%d" % bad in err()
+        assert call(N=2, Zs=1024, Hs=1024, Ws=1024) == 1 and "2^31" in err() and "Zs" in err()
+        assert call(N=2, Zo=1024, Ho=1024, Wo=1024) == 1 and "2^31" in err() and "Zo" in err()
+        assert call(N=30, Zs=2048, Hs=2048, Ws=2048) == 1 and "2^31" in err()          # the product does not fit 64 bits of int either way
+        # out inside src, src inside out, out starting at the last element of src
+        assert call(out=P((1 << 20) + 4 * 100)) == 3 and "out overlaps src" in err()
+        assert call(out=P((1 << 20) - 4 * 100)) == 3 and "out overlaps src" in err()
+        assert call(out=P((1 << 20) + 4 * (2 * 5 * 9 * 11 - 1))) == 3 and "out overlaps src" in err()
+    assert affine(m_host=None) == 1 and "m_host is a null" in err()
+    for i, bad in ((0, np.nan), (7, np.inf), (11, -np.inf)):
+        mm = m.copy()
+        mm.reshape(-1)[i] = bad
+        assert affine(m_host=DA(mm)) == 1 and "m_host[%d]" % i in err()
+    assert by_grid(grid=None) == 1 and "grid is a null" in err()
+    assert by_grid(grid=P((1 << 28) + 2)) == 1 and "grid is not 4-byte" in err()
+    assert by_grid(grid=P((1 << 24) + 4 * 10)) == 3 and "out overlaps grid" in err()
+    assert by_grid(grid=P((1 << 24) - 12 * 2 * 7 * 13 + 4)) == 3 and "out overlaps grid" in err()
