@@ -1,5 +1,5 @@
 """ctypes binding of libaesr_hip.so (C ABI: include/aesr_hip.h, include/aesr_hip_preproc.h, include/aesr_hip_dataprep.h, include/aesr_hip_train.h,
-include/aesr_hip_baselines.h and include/aesr_hip_reslice.h).
+include/aesr_hip_baselines.h, include/aesr_hip_reslice.h and include/aesr_hip_seg.h).
 
 There is NO fallback: if the shared library is missing or an entry point is absent this module raises at
 import time, and every wrapper raises RuntimeError with the library's own message when a call fails.
@@ -201,6 +201,13 @@ SIGNATURES_RESLICE = {
     "aesr_reslice_affine": (c_int, [P, P] + [c_int] * 7 + [DP, c_int, P]),
     "aesr_reslice_grid": (c_int, [P, P, P] + [c_int] * 7 + [c_int, P]),
 }
+# the label-head ABI (include/aesr_hip_seg.h, same library): must list every symbol that header declares (checked by tests)
+SIGNATURES_SEG = {
+    "aesr_softmax_dice_workspace_floats": (c_size_t, [c_int] * 4),
+    "aesr_softmax_dice_fwd": (c_int, [P, P, c_size_t] + [P] * 5 + [c_int] * 4 + [P]),
+    "aesr_softmax_dice_bwd": (c_int, [P, P, c_size_t, P, P, P] + [c_int] * 4 + [P]),
+}
+SEG_MIN_CLASSES, SEG_MAX_CLASSES = 2, 8
 RESLICE_NEAREST, RESLICE_LINEAR = 0, 1          # AESR_RESLICE_* (RS_* below are the modes of aesr_resample2_*)
 ZX_ALIGN_ITK, ZX_ALIGN_GRID, ZX_CLAMP, ZX_MIRROR = 0, 1, 0, 1
 ZX_MAX_FACTOR, ZX_MAX_TAPS = 16, 10          # ZX_MAXF, ZX_MAXT of csrc/z_expand.hip
@@ -225,7 +232,8 @@ def _load():
             "superresolution_aniso_mri_amd/csrc`). The HIP extension is mandatory: there is no CPU/eager fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_PREPROC.items()) + list(SIGNATURES_DATAPREP.items())
-                                   + list(SIGNATURES_TRAIN.items()) + list(SIGNATURES_BASELINES.items()) + list(SIGNATURES_RESLICE.items())):
+                                   + list(SIGNATURES_TRAIN.items()) + list(SIGNATURES_BASELINES.items()) + list(SIGNATURES_RESLICE.items())
+                                   + list(SIGNATURES_SEG.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             raise RuntimeError("libaesr_hip.so does not export %s (stale build?)" % name)

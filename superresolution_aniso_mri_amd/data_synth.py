@@ -41,6 +41,23 @@ def synthetic_batch(B, H, W, seed, brain=False):
     return batch
 
 
+def synthetic_labelled_batch(B, H, W, seed, nclasses=4):
+    """Two-channel triplets for the multi-channel (image + label map) trainers: ``image`` [2B, 2, H, W] and ``slice_between`` [B, 2, H, W]
+    with channel 0 the intensities of ``synthetic_batch(B, H, W, seed)`` and channel 1 class ids 0 ... nclasses - 1 as floats.  The labels
+    are a second smooth field of the same kind (its own seed), cut at the thresholds k / nclasses: regions with smooth borders that move
+    from the *from* slice over the slice between to the *to* slice as the intensities do.  CPU float32, deterministic in its arguments."""
+    if nclasses < 2:
+        raise ValueError("synthetic_labelled_batch needs at least 2 classes, got %d" % nclasses)
+    img = synthetic_batch(B, H, W, seed)
+    field = synthetic_batch(B, H, W, int(seed) + 7919)
+
+    def with_labels(key):
+        lab = torch.floor(field[key].clamp(0, 1) * nclasses).clamp_(max=nclasses - 1)
+        return torch.cat([img[key], lab], dim=1).contiguous()
+
+    return {"image": with_labels("image"), "slice_between": with_labels("slice_between"), "loss_mask": img["loss_mask"]}
+
+
 def shard_batch(batch, rank, world):
     """Data parallel: rank r keeps triplets [lo, hi) and rebuilds ``image`` so row i still pairs with row i + B_local."""
     B = batch["slice_between"].shape[0]

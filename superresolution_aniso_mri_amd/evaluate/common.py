@@ -74,36 +74,44 @@ def eval_on_different_patch_size(trainer, test_images, patch_size=(32, 32)):
 def create_super_volume(trainer, images, alpha_range=None, use_original=False, hierarchical=False, downsample_steps=None,
                         generate_inbetween_slices=False, train_patch_size=None, feature_dict=None, labels=None):
     """images [z,y,x] -> {'upsampled_image' [z',y,x] (CPU, clamped to [0,1]), 'upsampled_labels' None, 'pred_alphas'
-    [(z_kept-1)*n, 1, y, x]} with the reference's conventions (:134-235):
+    [(z_kept-1)*n, 1, y, x]} with the reference's conventions (:134-235).  ``labels`` [z,y,x] (class ids; a multi-channel model):
+    'upsampled_labels' [z',y,x] follows the same slot order -- reconstructed or original label maps at the kept slots, the decoded
+    arg-max maps in between, the ORIGINAL label maps of the remainder slices behind them (:220-231):
 
     * ``generate_inbetween_slices`` without ``downsample_steps`` sub-samples by ``len(alpha_range)+1``;
     * the last ``(z-1) % downsample_steps`` slices cannot be paired: they are cut before sub-sampling and, when in-between
       slices are generated, the ORIGINAL slices are appended after the synthesised stack;
     * ``alpha_range`` defaults to (0.25, 0.5, 0.75); alpha weights the LATER slice of each pair."""
-    if hierarchical or labels is not None:
-        raise NotImplementedError("hierarchical latents / label channels are outside the ae_combined path")
+    if hierarchical:
+        raise NotImplementedError("hierarchical latents are outside this build")
     if images.dim() != 3:
         raise ValueError("create_super_volume expects a [z, y, x] volume, got shape %s" % (tuple(images.shape),))
+    if labels is not None and tuple(labels.shape) != tuple(images.shape):
+        raise ValueError("labels %s do not match the images %s" % (tuple(labels.shape), tuple(images.shape)))
     if generate_inbetween_slices and downsample_steps is None:
         downsample_steps = int(len(alpha_range) + 1)
-    orig, remain = images, 0
+    orig, orig_labels, remain = images, labels, 0
     if not generate_inbetween_slices and downsample_steps is not None:
         print("WARNING !!! create_super_volume - downsample steps is not None but generate_inbetween_slices is False!")
     if downsample_steps is not None or generate_inbetween_slices:
         remain = (orig.shape[0] - 1) % downsample_steps
         if remain:
             images = images[:-remain]
+            labels = None if labels is None else labels[:-remain]
         images = images[::downsample_steps]
+        labels = None if labels is None else labels[::downsample_steps]
     if alpha_range is None:
         alpha_range = [0.25, 0.5, 0.75]
-    out = _ghv.create_super_volume(trainer, images, alpha_range, use_original=use_original)
-    new_volume = out["upsampled_image"]
+    out = _ghv.create_super_volume(trainer, images, alpha_range, use_original=use_original, labels=labels)
+    new_volume, new_labels = out["upsampled_image"], out["upsampled_labels"]
     if generate_inbetween_slices and remain:
         new_volume = torch.clamp(torch.cat([new_volume, orig[-remain:].float().cpu()]), min=0, max=1.)
+        if new_labels is not None:
+            new_labels = torch.cat([new_labels, orig_labels[-remain:].float().cpu()])       # int64 | float -> float, as in the reference
     pairs = images.shape[0] - 1
     alphas = torch.tensor([float(a) for a in alpha_range], dtype=torch.float32).repeat_interleave(pairs)
     pred_alphas = alphas[:, None, None, None].expand(-1, 1, images.shape[1], images.shape[2])
-    return {"upsampled_image": new_volume, "upsampled_labels": None, "pred_alphas": pred_alphas}
+    return {"upsampled_image": new_volume, "upsampled_labels": new_labels, "pred_alphas": pred_alphas}
 
 
 def create_simple_interpolation(images, spacing, new_spacing_z=None, expand_factor=None, interpol_filter=None,

@@ -20,7 +20,12 @@ volume crosses PCIe once each way.  Without the flag nothing changes.
 ``create_simple_interpolation``, evaluate/common.py:74-118): no model is loaded, the volume is expanded along z by
 ``num_interpolations + 1`` on the device (evaluate/z_interp.py, csrc/z_expand.hip) with its intensities as they are, and written with the
 z spacing divided by the same factor.  ``--align itk`` (default) is SimpleITK's ExpandImageFilter grid, ``--align grid`` the layout of the
-model's output."""
+model's output.
+
+``--labels_input_dir DIR`` (a multi-channel model, ``--dataset ACDCLBL``): every image has a label volume of the same file name in DIR; the
+label map goes through the network as the second channel and ``<name>_labels`` is written beside the super-resolved image -- the given
+labels at the kept slots, in between the arg-max maps decoded from the same mixed latents as the in-between slices -- as an unsigned
+8-bit volume with the image's new z spacing.  Such a model is refused without the flag."""
 import argparse
 import os
 from pathlib import Path
@@ -36,29 +41,67 @@ def _encode(trainer, x):
 
 
 def latent_space_interp(alpha, trainer, img1, img2, device=None, with_labels=False):
-    """One alpha: decode(alpha*enc(img1) + (1-alpha)*enc(img2)) (reference :72-101).  Returns CPU tensors."""
-    if with_labels:
-        raise NotImplementedError("label channels (ACDCLBL multi-channel models) are outside this build")
+    """One alpha: decode(alpha*enc(img1) + (1-alpha)*enc(img2)) (reference :72-101).  Returns CPU tensors.  ``with_labels``: the images
+    carry their label maps as channel 1 (a multi-channel model); ``inter_label`` is the arg-max map decoded from the same mixed latent."""
     dev = device or trainer.args["device"]
     z = torch.cat([_encode(trainer, img1.float().to(dev)), _encode(trainer, img2.float().to(dev))], dim=0)
     inter = trainer.decode(ops.lerp_mix(z, float(alpha), float(1 - alpha)), use_sr_model=True)
+    if with_labels:
+        return {"inter_image": inter["image"].detach().cpu().contiguous(), "inter_label": inter["pred_labels"].detach().cpu()}
+    _no_label_model(inter)
     return {"inter_image": inter.detach().cpu().contiguous(), "inter_label": None}
+
+
+def _no_label_model(decoded):
+    if isinstance(decoded, dict):
+        raise ValueError("this is a multi-channel model (image + label map): it needs the label volume too (labels=... / with_labels=True, "
+                         "generate_hr_volumes --labels_input_dir)")
+
+
+def _interleave(orig, synth, n, clamp):
+    """orig [Z, H, W], synth [n (Z - 1), H, W] (row k (Z - 1) + i) or None -> [(Z - 1)(n + 1) + 1, H, W]: slice i at slot i (n + 1), its n
+    synthesised successors behind it; ``clamp`` = (lo, hi)."""
+    Z, H, W = orig.shape
+    if orig.is_cuda and (H * W) % 4 == 0:
+        # interleave + clamp: one pass over the volume (a channel of a two-channel volume is gathered first)
+        return ops.interleave_clamp(orig.contiguous(), synth, n, clamp[0], clamp[1])
+    out = torch.empty(((Z - 1) * (n + 1) + 1, H, W), device=orig.device, dtype=torch.float32)
+    out[::n + 1] = orig
+    if synth is not None:
+        synth = synth.reshape(n, Z - 1, H, W)
+        for k in range(n):
+            out[k + 1::n + 1] = synth[k]
+    return out.clamp_(clamp[0], clamp[1])
 
 
 def create_super_volume(trainer, images, alpha_range, use_original=False, labels=None, to_cpu=True):
     """images [z,1,y,x] or [z,y,x] -> {'upsampled_image': [(z-1)(n+1)+1, y, x] (CPU, clamped), 'upsampled_labels': None}.
-    ``to_cpu=False`` leaves the result in HBM (callers that go on working on the device; bench.py times it that way)."""
-    if labels is not None:
-        raise NotImplementedError("label channels (ACDCLBL multi-channel models) are outside this build")
+    ``to_cpu=False`` leaves the result in HBM (callers that go on working on the device; bench.py times it that way).
+
+    ``labels`` [z,1,y,x] or [z,y,x] (class ids; a multi-channel model, reference :23-69): the label maps go in as channel 1 and
+    'upsampled_labels' [(z-1)(n+1)+1, y, x] holds the original (``use_original``: float, as given) or reconstructed (int64) label maps
+    at the kept slots and, in between, the arg-max maps decoded from the SAME mixed latents as the in-between slices."""
     if images.dim() == 3:
         images = torch.unsqueeze(images, dim=1)
+    with_labels = labels is not None
+    if with_labels and labels.dim() == 3:
+        labels = torch.unsqueeze(labels, dim=1)
     dev = trainer.args["device"]
     vol = images.float().to(dev)
+    if with_labels:
+        if tuple(labels.shape) != tuple(images.shape):
+            raise ValueError("labels %s do not match the images %s" % (tuple(labels.shape), tuple(images.shape)))
+        vol = torch.cat([vol, labels.float().to(dev)], dim=1)
     Z, _, H, W = vol.shape
     n = len(alpha_range)
+    out_labels = None
     with torch.no_grad():
         lat = _encode(trainer, vol)                                   # every slice encoded exactly once
         recon = vol if use_original else trainer.decode(lat, use_sr_model=True)
+        if with_labels and not use_original and not isinstance(recon, dict):
+            raise ValueError("labels were given, but this model has no label head (MultiChannelAE is the one that has)")
+        if not with_labels:
+            _no_label_model(recon)
         dec = None
         if Z > 1 and n > 0:
             model = trainer._use_sr_model(True)
@@ -68,21 +111,23 @@ def create_super_volume(trainer, images, alpha_range, use_original=False, labels
                 zpair = torch.cat([lat[1:], lat[:-1]], dim=0)         # rows i / i+(Z-1): later slice / earlier slice
                 mixes = torch.cat([ops.lerp_mix(zpair, float(a), float(1 - a)) for a in alpha_range], dim=0)
                 dec = trainer.decode(mixes, use_sr_model=True)        # ONE decoder pass over all (Z-1)*n latents
-        if vol.is_cuda and (H * W) % 4 == 0:
-            out = ops.interleave_clamp(recon[:, 0], dec, n, 0.0, 1.0)        # interleave + clamp: one pass over the volume
-        else:
-            out = torch.empty(((Z - 1) * (n + 1) + 1, H, W), device=vol.device, dtype=torch.float32)
-            out[::n + 1] = recon[:, 0]
-            if dec is not None:
-                dec = dec.reshape(n, Z - 1, H, W)
-                for k in range(n):
-                    out[k + 1::n + 1] = dec[k]
-            out.clamp_(0, 1.)
+            if with_labels and not isinstance(dec, dict):
+                raise ValueError("labels were given, but this model has no label head (MultiChannelAE is the one that has)")
+        if with_labels:
+            kept = vol[:, 1] if use_original else recon["pred_labels"][:, 0].float()
+            synth = None if dec is None else dec["pred_labels"][:, 0].float()
+            out_labels = _interleave(kept, synth, n, (-3.0e38, 3.0e38))          # small integers: exact as floats
+            if not use_original:
+                out_labels = out_labels.long()
+            recon = vol[:, 0:1] if use_original else recon["image"]
+            dec = None if dec is None else dec["image"]
+        out = _interleave(recon[:, 0], dec, n, (0.0, 1.0))
     if to_cpu:
         out = out.cpu()
+        out_labels = None if out_labels is None else out_labels.cpu()
         if vol.is_cuda:
             _hip.check_device_watchdogs("create_super_volume")       # the volume leaves the device here: never a silent garbage volume
-    return {"upsampled_image": out, "upsampled_labels": None}
+    return {"upsampled_image": out, "upsampled_labels": out_labels}
 
 
 # ---- I/O around the path (SimpleITK is optional; .npy volumes work everywhere) -----------------------------------------
@@ -127,12 +172,31 @@ def load_images(input_dir, suffix=".nii*"):
     return [(f, np.load(str(f))) for f in files]
 
 
-def upsample_volume(trainer, vol_np, num_interpolations):
-    """[z,y,x] or [t,z,y,x] numpy -> through-plane upsampled numpy with the same leading layout."""
+def upsample_volume(trainer, vol_np, num_interpolations, labels_np=None):
+    """[z,y,x] or [t,z,y,x] numpy -> through-plane upsampled numpy with the same leading layout.  ``labels_np`` (same shape, class ids; a
+    multi-channel model): returns (volume, label volume as uint8) instead."""
     alpha_range = np.linspace(0, 1, num_interpolations + 2, endpoint=True)[1:-1]
+    if labels_np is not None and tuple(labels_np.shape) != tuple(vol_np.shape):
+        raise ValueError("the label volume %s does not match the image volume %s" % (tuple(labels_np.shape), tuple(vol_np.shape)))
     if vol_np.ndim == 3:
-        return create_super_volume(trainer, array_to_torch(vol_np), alpha_range, use_original=True)["upsampled_image"].numpy()
-    return np.stack([upsample_volume(trainer, v, num_interpolations) for v in vol_np])
+        if labels_np is None:
+            return create_super_volume(trainer, array_to_torch(vol_np), alpha_range, use_original=True)["upsampled_image"].numpy()
+        lab = torch.from_numpy(np.ascontiguousarray(labels_np, dtype=np.float32)).unsqueeze(dim=1)
+        out = create_super_volume(trainer, array_to_torch(vol_np), alpha_range, use_original=True, labels=lab)
+        return out["upsampled_image"].numpy(), np.rint(out["upsampled_labels"].numpy()).astype(np.uint8)
+    if labels_np is None:
+        return np.stack([upsample_volume(trainer, v, num_interpolations) for v in vol_np])
+    pairs = [upsample_volume(trainer, v, num_interpolations, l) for v, l in zip(vol_np, labels_np)]
+    return np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
+
+
+def labels_name(name):
+    """vol0.npy -> vol0_labels.npy, p1.nii.gz -> p1_labels.nii.gz"""
+    name = str(name)
+    for ext in (".nii.gz", ".nii", ".mha", ".mhd", ".npy"):
+        if name.endswith(ext):
+            return name[:-len(ext)] + "_labels" + ext
+    return name + "_labels"
 
 
 def normalize_on_device(x, perc=(1, 99)):
@@ -213,6 +277,9 @@ def main(argv=None):
     p.add_argument("--model_nbr", type=int, default=None)
     p.add_argument("--num_interpolations", type=int, default=6)
     p.add_argument("--data_input_dir", type=str, default=None)
+    p.add_argument("--labels_input_dir", type=str, default=None,
+                   help="label volumes (class ids) with the same file names as the images: needs a multi-channel model; writes <name>_labels "
+                        "beside every super-resolved image, an integer volume with the image's new z spacing")
     p.add_argument("--output_dir", type=str, default=None)
     p.add_argument("--save", action="store_true")
     args = p.parse_args(argv)
@@ -222,6 +289,8 @@ def main(argv=None):
         p.error("--method ae needs --exper_dir")
     if args.output_dir is None and args.exper_dir is None:
         p.error("--output_dir is needed when there is no --exper_dir")
+    if args.labels_input_dir is not None and (args.method != "ae" or args.resample):
+        p.error("--labels_input_dir belongs to --method ae without --resample (label maps are not resampled in-plane)")
     from .kwatsch.get_trainer import get_trainer_dynamic
     out_dir = Path(args.output_dir if args.output_dir is not None else os.path.join(args.exper_dir, "ni0{}".format(args.num_interpolations)))
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -232,11 +301,30 @@ def main(argv=None):
     trainer = None
     if args.method == "ae":
         trainer, _ = get_trainer_dynamic(src_path=args.exper_dir, model_nbr=args.model_nbr, model_nbr_sr=None, eval_mode=True)
+        multi = hasattr(trainer.model, "decoder_head2")
+        if multi and args.labels_input_dir is None:
+            p.error("this experiment holds a multi-channel model (image + label map): give the label volumes with --labels_input_dir DIR")
+        if not multi and args.labels_input_dir is not None:
+            p.error("--labels_input_dir needs a multi-channel model (--dataset ACDCLBL); this experiment's model has no label head")
+    label_files = {}
+    if args.labels_input_dir is not None:
+        label_files = {f.name: lab for f, lab in load_images(Path(args.labels_input_dir))}
+        missing = [f.name for f, _ in images if f.name not in label_files]
+        if missing:
+            p.error("--labels_input_dir holds no label volume named %s" % ", ".join(missing))
     sitk = _sitk()
     results = []
     from . import volume_io
 
-    def upsample(arr, spacing_yx):
+    def label_array(fname):
+        lab = label_files[fname.name]
+        if isinstance(lab, volume_io.Volume):
+            return lab.array
+        return lab if isinstance(lab, np.ndarray) else sitk.GetArrayFromImage(lab)
+
+    def upsample(arr, spacing_yx, fname=None):
+        if label_files:
+            return upsample_volume(trainer, arr, args.num_interpolations, label_array(fname))
         if args.method != "ae":
             return expand_volume(arr, args.num_interpolations, args.method, args.align, args.lanczos_radius)
         if not args.resample:
@@ -245,20 +333,31 @@ def main(argv=None):
 
     for fname, img in images:
         if isinstance(img, volume_io.Volume):
-            hr = upsample(img.array, (img.spacing[1], img.spacing[0]))
+            hr = upsample(img.array, (img.spacing[1], img.spacing[0]), fname)
+            hr, hr_labels = hr if label_files else (hr, None)
             spacing = list(img.spacing)
             spacing[2] = spacing[2] / (args.num_interpolations + 1)
             results.append((out_dir / fname.name, hr))
             if args.save:
                 volume_io.write_volume(out_dir / fname.name, img, hr.astype(np.float32), spacing)
+            if hr_labels is not None:
+                results.append((out_dir / labels_name(fname.name), hr_labels))
+                if args.save:
+                    volume_io.write_volume(out_dir / labels_name(fname.name), img, hr_labels, spacing)
         elif isinstance(img, np.ndarray):
-            hr = upsample(img, args.spacing)
+            hr = upsample(img, args.spacing, fname)
+            hr, hr_labels = hr if label_files else (hr, None)
             results.append((out_dir / fname.name, hr))
             if args.save:
                 np.save(str(out_dir / fname.name), hr)
+            if hr_labels is not None:
+                results.append((out_dir / labels_name(fname.name), hr_labels))
+                if args.save:
+                    np.save(str(out_dir / labels_name(fname.name)), hr_labels)
         else:
             arr = sitk.GetArrayFromImage(img)
-            hr = upsample(arr, (img.GetSpacing()[1], img.GetSpacing()[0]))
+            hr = upsample(arr, (img.GetSpacing()[1], img.GetSpacing()[0]), fname)
+            hr, hr_labels = hr if label_files else (hr, None)
             spacing = list(img.GetSpacing())
             zi = 2 if arr.ndim == 3 else 2
             spacing[zi] = spacing[zi] / (args.num_interpolations + 1)
@@ -272,6 +371,14 @@ def main(argv=None):
             results.append((out_dir / fname.name, out))
             if args.save:
                 sitk.WriteImage(out, str(out_dir / fname.name))
+            if hr_labels is not None:
+                lab = sitk.JoinSeries([sitk.GetImageFromArray(v, False) for v in hr_labels]) if hr_labels.ndim == 4 else sitk.GetImageFromArray(hr_labels)
+                lab.SetOrigin(img.GetOrigin())
+                lab.SetDirection(img.GetDirection())
+                lab.SetSpacing(spacing)
+                results.append((out_dir / labels_name(fname.name), lab))
+                if args.save:
+                    sitk.WriteImage(lab, str(out_dir / labels_name(fname.name)))
         print("Processed {}".format(fname))
     return results
 

@@ -7,12 +7,15 @@ from .acai_utils import make_grid
 
 
 def latent_space_interp(alpha, trainer, img1, img2, device=None, hierarchical=False, with_labels=False):
-    """decode(alpha*enc(img1) + (1-alpha)*enc(img2)) (reference :57-89)."""
-    if hierarchical or with_labels:
-        raise NotImplementedError("hierarchical / labelled latents are outside the ae_combined path")
+    """decode(alpha*enc(img1) + (1-alpha)*enc(img2)) (reference :57-89).  ``with_labels``: two-channel images of a multi-channel model;
+    ``inter_label`` is the arg-max map decoded from the same mixed latent."""
+    if hierarchical:
+        raise NotImplementedError("hierarchical latents are outside this build")
     dev = device or trainer.args["device"]
     z = torch.cat([trainer.encode(img1.float().to(dev), use_sr_model=True), trainer.encode(img2.float().to(dev), use_sr_model=True)])
     inter = trainer.decode(ops.lerp_mix(z, float(alpha), float(1 - alpha)), use_sr_model=True)
+    if with_labels:
+        return {"inter_image": inter["image"].detach().cpu().contiguous(), "inter_label": inter["pred_labels"].detach().cpu()}
     return {"inter_image": inter.detach().cpu().contiguous(), "inter_label": None}
 
 

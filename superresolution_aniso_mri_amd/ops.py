@@ -409,3 +409,121 @@ class HipAdam(torch.optim.Adam):
             off += k
         self._init_state(step)
         self._host_step = int(step)
+
+
+# ---- the label head: softmax + soft Dice + arg-max (csrc/seg_head.hip, include/aesr_hip_seg.h) ------------------------------------------
+def _label_view(labels, N, H, W):
+    """(tensor that owns the memory, per-sample stride in floats) of class-id labels [N, H, W] / [N, 1, H, W] as fp32.  A channel of an
+    NCHW batch (``x[:, 1]``: rows and columns contiguous, samples C * H * W apart) is read in place; anything else is made contiguous."""
+    if labels.dim() == 4:
+        if labels.shape[1] != 1:
+            raise ValueError("labels must be [N, H, W] or [N, 1, H, W], got %s" % (tuple(labels.shape),))
+        labels = labels[:, 0]
+    if tuple(labels.shape) != (N, H, W):
+        raise ValueError("labels %s do not match the logits [%d, %d, %d, K]" % (tuple(labels.shape), N, H, W))
+    if labels.dtype != torch.float32:
+        labels = labels.float()
+    if not labels.is_cuda:
+        raise RuntimeError("labels must live on the GPU (got %s): the HIP path has no CPU fallback" % labels.device)
+    if not (labels.stride(2) == 1 and labels.stride(1) == W and (N == 1 or labels.stride(0) >= H * W)):
+        labels = labels.contiguous()
+    return labels, (labels.stride(0) if N > 1 else H * W)
+
+
+def _seg_check_logits(logits_nhwc):
+    _hip.require_gpu_tensor(logits_nhwc, "logits")
+    if logits_nhwc.dim() != 4:
+        raise ValueError("logits must be NHWC [N, H, W, K], got %s" % (tuple(logits_nhwc.shape),))
+    K = logits_nhwc.shape[3]
+    if not _hip.SEG_MIN_CLASSES <= K <= _hip.SEG_MAX_CLASSES:
+        raise ValueError("softmax_dice supports %d to %d classes, got %d" % (_hip.SEG_MIN_CLASSES, _hip.SEG_MAX_CLASSES, K))
+    return tuple(int(v) for v in logits_nhwc.shape)
+
+
+class _SoftmaxDiceFn(torch.autograd.Function):
+    """(loss, probs, argmax) from the logits in one pass; the backward writes d(logits) in one pass.  Only ``loss`` carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, label_stride, want_argmax):
+        N, H, W, K = logits.shape
+        dev = logits.device
+        probs = torch.empty_like(logits)
+        argmax = torch.empty((N, H, W), device=dev, dtype=torch.int32) if want_argmax else None
+        partial = torch.empty(lib.aesr_softmax_dice_workspace_floats(N, H, W, K), device=dev, dtype=torch.float32)
+        sums = torch.empty((N, 3, K), device=dev, dtype=torch.float64)
+        loss = torch.empty(1, device=dev, dtype=torch.float32)
+        _pb("softmax_dice", 0.0, 4.0 * (2 * logits.numel() + N * H * W * (2 if want_argmax else 1)))
+        check(lib.aesr_softmax_dice_fwd(ptr(logits), ptr(labels), int(label_stride), ptr(probs), ptr(argmax), ptr(partial), ptr(sums), ptr(loss),
+                                        N, H, W, K, stream()), "aesr_softmax_dice_fwd")
+        _pe()
+        ctx.save_for_backward(probs, labels, sums)
+        ctx.label_stride = int(label_stride)
+        ctx.set_materialize_grads(False)
+        out = (loss.reshape(()), probs, sums) + ((argmax,) if want_argmax else ())
+        ctx.mark_non_differentiable(*out[1:])
+        return out
+
+    @staticmethod
+    def backward(ctx, g, *_unused):
+        if g is None:
+            return None, None, None, None
+        probs, labels, sums = ctx.saved_tensors
+        N, H, W, K = probs.shape
+        g = g.reshape(1).contiguous().float()
+        d = torch.empty_like(probs)
+        _pb("softmax_dice", 0.0, 4.0 * (2 * probs.numel() + N * H * W))
+        check(lib.aesr_softmax_dice_bwd(ptr(probs), ptr(labels), ctx.label_stride, ptr(sums), ptr(g), ptr(d), N, H, W, K, stream()),
+              "aesr_softmax_dice_bwd")
+        _pe()
+        return d, None, None, None
+
+
+def softmax_dice(logits_nhwc, labels, want_argmax=False, return_sums=False):
+    """The label head's loss from the LOGITS: softmax over the last (class) dimension of ``logits_nhwc`` [N, H, W, K], the soft-Dice loss
+    of kwatsch/dice_loss.py against ``labels`` (class ids as floats, [N, H, W] or [N, 1, H, W]; a channel view of an NCHW batch is read in
+    place) and optionally the arg-max map.  Returns (loss 0-dim, probs [N, H, W, K], argmax int32 [N, H, W] or None[, sums fp64
+    [N, 3, K] = I, R, P]); only ``loss`` carries a gradient (to the logits).  A label outside [0, K) or not integral belongs to no
+    class (torch's scatter_ would raise).  No host sync."""
+    N, H, W, K = _seg_check_logits(logits_nhwc)
+    lab, stride = _label_view(labels, N, H, W)
+    out = _SoftmaxDiceFn.apply(logits_nhwc, lab, stride, bool(want_argmax))
+    res = (out[0], out[1], out[3] if want_argmax else None)
+    return res + (out[2],) if return_sums else res
+
+
+def _softmax_argmax_raw(logits_nhwc, want_argmax):
+    N, H, W, K = _seg_check_logits(logits_nhwc)
+    probs = torch.empty_like(logits_nhwc)
+    argmax = torch.empty((N, H, W), device=logits_nhwc.device, dtype=torch.int32) if want_argmax else None
+    check(lib.aesr_softmax_dice_fwd(ptr(logits_nhwc), None, 0, ptr(probs), ptr(argmax), None, None, None, N, H, W, K, stream()),
+          "aesr_softmax_dice_fwd")
+    return probs, argmax
+
+
+class _SoftmaxFn(torch.autograd.Function):
+    """Class softmax of NHWC logits for callers that put a loss of their OWN on the probabilities (``MultiChannelAE.decode`` under
+    autograd, ``DiceLoss.forward``): the forward is the kernel, the backward the three-term formula in tensor operations -- the trainers
+    never take this path, they differentiate ``softmax_dice``."""
+
+    @staticmethod
+    def forward(ctx, logits):
+        probs, _ = _softmax_argmax_raw(logits, False)
+        ctx.save_for_backward(probs)
+        return probs
+
+    @staticmethod
+    def backward(ctx, g):
+        (p,) = ctx.saved_tensors
+        return p * (g - (p * g).sum(dim=3, keepdim=True))
+
+
+def softmax_nhwc(logits_nhwc):
+    """softmax over the class dimension of [N, H, W, K] logits (differentiable)."""
+    if logits_nhwc.requires_grad and torch.is_grad_enabled():
+        return _SoftmaxFn.apply(logits_nhwc)
+    return _softmax_argmax_raw(logits_nhwc.detach(), False)[0]
+
+
+def softmax_argmax(logits_nhwc):
+    """Inference: (probs [N, H, W, K], argmax int32 [N, H, W]; ties go to the lowest class) in one pass, no gradient."""
+    return _softmax_argmax_raw(logits_nhwc.detach(), True)

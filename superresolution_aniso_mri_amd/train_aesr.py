@@ -3,7 +3,8 @@ train_brain_aesr.py:137-206) for the MI355X build: same flags, output layout (se
 log_images/, loss*.npz) and epoch bookkeeping (iters starts at 1, validate when (iters+1) % num_it_per_epoch == 0).
 
 Data: the reference's SimpleITK/NIfTI dataset readers and numpy augmentations are host-side I/O outside this build's
-hot path; ``--synthetic`` feeds device-resident synthetic triplets in the same batch layout, ``--volumes_dir``
+hot path; ``--synthetic`` feeds device-resident synthetic triplets in the same batch layout (``--dataset ACDCLBL``: two-channel triplets, image +
+label map, for the multi-channel trainers; ``--ae_class`` then defaults to MultiChannelAE), ``--volumes_dir``
 feeds the volumes of a directory through the on-device augmenters of data_device.py (cardiac datasets: ``TripletAugmenter``; OASIS /
 dHCP / ADNI: thick slices simulated on the device, then ``BrainTripletAugmenter``).  Launch under
 ``python -m torch.distributed.run --nproc-per-node N`` for data parallel training (one process per GPU, RCCL)."""
@@ -13,7 +14,7 @@ from shutil import rmtree
 import numpy as np
 import torch
 
-from .data_synth import shard_batch, synthetic_batch
+from .data_synth import shard_batch, synthetic_batch, synthetic_labelled_batch
 from .kwatsch.arguments import parse_args
 from .kwatsch.common import saveExperimentSettings
 from .kwatsch.get_trainer import get_trainer_dynamic
@@ -58,6 +59,13 @@ def generate_epoch_range(args_dict):
 
 def main(argv=None, brain=False):
     args, args_dict = parse_args(argv)
+    labelled = args_dict["dataset"] == "ACDCLBL"
+    if labelled and args_dict["ae_class"] == "VanillaACAI":
+        args_dict["ae_class"] = "MultiChannelAE"        # the two-headed network is the only one the multi-channel trainers can drive
+    if labelled and args_dict.get("volumes_dir"):
+        raise NotImplementedError("--dataset ACDCLBL with --volumes_dir: the label-aware augmenter (image and label map cropped and rotated "
+                                  "together, intensity curve on the image only) is not built; train with --synthetic or feed "
+                                  "trainer.train() two-channel batches from your own loader")
     cfg = NetworkConfig(args_dict["model"], dataset=args_dict["dataset"], ae_class=args_dict["ae_class"])
     args_dict = merge_args_architecture(args_dict, cfg.architecture)
     if not args_dict.get("synthetic") and not args_dict.get("volumes_dir"):
@@ -108,6 +116,11 @@ def main(argv=None, brain=False):
 
     synth_pool = {}       # --synthetic: a small pool of device-resident batches made BEFORE the loop (rendering one on the host costs tens of ms)
 
+    def synth(n, seed):
+        if labelled:
+            return synthetic_labelled_batch(n, size, size, seed=seed, nclasses=args_dict["nclasses"])
+        return synthetic_batch(n, size, size, seed=seed, brain=brain)
+
     def make_batch(seed, n, training=True):
         if brain_volumes:
             # as below; the validation batch goes through the brain TEST transform (padding only, no intensity curve: raw=True), padded
@@ -123,12 +136,12 @@ def main(argv=None, brain=False):
         elif training:
             key = (n, int(seed) % max(1, int(args_dict.get("synthetic_pool") or 8)))
             if key not in synth_pool:
-                b = synthetic_batch(n, size, size, seed=args_dict["seed"] + key[1], brain=brain)
+                b = synth(n, args_dict["seed"] + key[1])
                 b = shard_batch(b, dp.rank, dp.world) if dp.active else b
                 synth_pool[key] = {k: (v.to(args_dict["device"]) if torch.is_tensor(v) else v) for k, v in b.items()}
             return synth_pool[key]
         else:
-            b = synthetic_batch(n, size, size, seed=seed, brain=brain)
+            b = synth(n, seed)
         return shard_batch(b, dp.rank, dp.world) if dp.active else b
 
     trainer = get_trainer_dynamic(args_dict, model_file=args_dict["model_filename"])

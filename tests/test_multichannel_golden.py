@@ -1,0 +1,272 @@
+"""No GPU: the multi-channel (image + label map) auto-encoder against fixtures of the reference's own ``MultiChannelAE`` / ``DiceLoss``
+(tests/make_golden_multichannel.py -> tests/golden/mc_ae_small_*.npz).
+
+- the modules import through the paths ``NetworkConfig("ae_combined", "ACDCLBL", "MultiChannelAE")`` hands out and through the resolver
+  of ``get_trainer_dynamic``;
+- state-dict keys and order, ``named_parameters()`` order, shapes and the same-seed initial parameters equal the fixture bit for bit;
+- include/aesr_hip_seg.h == ``_hip.SIGNATURES_SEG`` == the library's exports, disjoint from the other six tables;
+- ``softmax_dice_f64`` below -- softmax with the row maximum subtracted, the soft-Dice loss and its CLOSED-FORM gradient in float64, the
+  reference every device test of csrc/seg_head.hip compares against -- reproduces what the reference's ``nn.Softmax`` + ``DiceLoss`` and
+  autograd give in float64 on the fixture's logits (``ref64/*``) to 1e-12;
+- ``nclasses = 3`` raises ValueError; the entry points refuse bad arguments on the host.
+"""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+SMALL = ("40x36", "28x28")
+DICE_EPS = 1.0e-6
+
+
+def softmax_dice_f64(logits_nchw, labels, g=1.0):
+    """float64 restatement of the label head.  logits [N, K, H, W]; labels [N, H, W] class ids (any type); g the upstream gradient.
+    Returns dict(probs [N, K, H, W], I, R, P [N, K], loss, dprobs = dL/dp, dlogits), gradients in closed form:
+        dL/dp = -(g / (N K)) (2 onehot / D - 2 I / D^2),  D = R + P + 1e-6;   dlogit_k = p_k (dL/dp_k - sum_j p_j dL/dp_j).
+    A label outside [0, K) or not integral belongs to no class."""
+    x = torch.as_tensor(logits_nchw).double()
+    lab = torch.as_tensor(labels).double()
+    N, K = x.shape[0], x.shape[1]
+    e = torch.exp(x - x.max(dim=1, keepdim=True).values)
+    p = e / e.sum(dim=1, keepdim=True)
+    onehot = (lab[:, None] == torch.arange(K, dtype=torch.float64).view(1, K, 1, 1)).double()
+    I, R, P = (onehot * p).sum(dim=(2, 3)), onehot.sum(dim=(2, 3)), p.sum(dim=(2, 3))
+    D = R + P + DICE_EPS
+    loss = -(2 * I / D).mean()
+    c = float(g) / (N * K)
+    dp = -c * (2 * onehot / D[:, :, None, None] - (2 * I / D ** 2)[:, :, None, None])
+    dlogits = p * (dp - (p * dp).sum(dim=1, keepdim=True))
+    return dict(probs=p, I=I, R=R, P=P, loss=loss, dprobs=dp, dlogits=dlogits)
+
+
+def small_args(size, **over):
+    a = dict(width=28 if size == "28x28" else 32, latent_width=7 if size == "28x28" else 8, depth=8, latent=16, colors=2, nclasses=4,
+             device="cpu", use_batchnorm=True, use_sigmoid=True, n_res_block=None)
+    a.update(over)
+    return a
+
+
+def load(name):
+    return dict(np.load(os.path.join(GOLDEN, name)))
+
+
+# ---- import paths ------------------------------------------------------------------------------------------------------------------
+def test_modules_import_through_the_configured_paths():
+    from importlib import import_module
+    from networks.net_config import NetworkConfig
+    from superresolution_aniso_mri_amd.kwatsch.get_trainer import _module_name
+    for model, cls in (("ae_combined", "MultiChannelCAISRTrainer"), ("ae", "MultiChannelTrainer")):
+        arch = NetworkConfig(model, "ACDCLBL", "MultiChannelAE").architecture
+        assert arch["module_network_path"] == "networks/acai_multi_channel.py" and arch["colors"] == 2 and arch["nclasses"] == 4
+        assert arch["module_trainer_path"] == "kwatsch/sr_multi_channel/trainer_ae.py" and arch["trainer_class"] == cls
+        net = import_module(_module_name(arch["module_network_path"]))
+        tr = import_module(_module_name(arch["module_trainer_path"]))
+        import superresolution_aniso_mri_amd.kwatsch.sr_multi_channel.trainer_ae as impl
+        import superresolution_aniso_mri_amd.networks.acai_multi_channel as net_impl
+        assert net.MultiChannelAE is net_impl.MultiChannelAE and getattr(tr, cls) is getattr(impl, cls)
+        assert issubclass(getattr(tr, cls), tr.MultiChannelBaseTrainer)
+    import kwatsch.dice_loss as dl
+    import superresolution_aniso_mri_amd.kwatsch.dice_loss as dl_impl
+    assert dl.DiceLoss is dl_impl.DiceLoss and dl.soft_dice_score is dl_impl.soft_dice_score
+
+
+def test_get_trainer_dynamic_builds_both_trainers():
+    from superresolution_aniso_mri_amd.kwatsch.get_trainer import get_trainer_dynamic
+    from superresolution_aniso_mri_amd.networks.net_config import NetworkConfig
+    for model, cls in (("ae_combined", "MultiChannelCAISRTrainer"), ("ae", "MultiChannelTrainer")):
+        args = dict(model=model, dataset="ACDCLBL", device="cpu", lr=1e-3, weight_decay=0.0, epochs=3, width=32, latent_width=8, depth=8,
+                    latent=16, ex_loss_weight1=0.05, use_percept_loss=False, get_masks=False, use_loss_annealing=False, epoch_threshold=100,
+                    ae_class="MultiChannelAE", image_mix_loss_func="mse")
+        for k, v in NetworkConfig(model, dataset="ACDCLBL", ae_class="MultiChannelAE").architecture.items():
+            args.setdefault(k, v)
+        tr = get_trainer_dynamic(args)
+        assert type(tr).__name__ == cls and type(tr.model).__name__ == "MultiChannelAE" and tr.nclasses == 4
+        assert type(tr.mask_loss).__name__ == "DiceLoss" and tr.mask_loss.n_classes == 4
+
+
+# ---- the network: layout and initialisation ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("size", SMALL)
+def test_state_dict_layout_and_same_seed_initialisation(size):
+    from superresolution_aniso_mri_amd.networks.acai_multi_channel import MultiChannelAE
+    rec = load("mc_ae_small_%s.npz" % size)
+    torch.manual_seed(1000 + int(size.split("x")[0]))
+    model = MultiChannelAE(small_args(size))
+    sd = model.state_dict()
+    assert list(sd.keys()) == [str(k) for k in rec["state_keys"]]
+    assert [k for k, _ in model.named_parameters()] == [str(k) for k in rec["param_names"]]
+    heads = [k for k in sd if k.startswith("decoder_head")]
+    assert heads[0] == "decoder_head1.0.weight" and {k.split(".")[1] for k in heads if k.startswith("decoder_head2")} == {"0", "2", "3"}
+    for k, v in sd.items():
+        want = rec["p0/" + k]
+        assert tuple(v.shape) == want.shape and v.numpy().dtype == want.dtype, k
+        assert np.array_equal(v.numpy(), want), k
+    # BatchNorm layers at scales = 2
+    bn = [n for n, m in model.named_modules() if isinstance(m, torch.nn.BatchNorm2d)]
+    assert bn == ["enc.5", "enc.11", "dec.2", "dec.7", "dec.13", "decoder_head2.2"]
+    assert isinstance(model.decoder_head2[4], torch.nn.Softmax) and isinstance(model.decoder_head1[1], torch.nn.Sigmoid)
+    assert model.dec[-2].out_channels == 8 and isinstance(model.dec[-1], torch.nn.LeakyReLU)
+
+
+def test_the_four_stacks_compile_and_the_softmax_stays_out():
+    from superresolution_aniso_mri_amd.networks.acai_multi_channel import STACKS, MultiChannelAE
+    model = MultiChannelAE(small_args("40x36"))
+    assert STACKS == ("enc", "dec", "decoder_head1", "decoder_head2")
+    kinds = {n: [s.kind for s in model._runner(n).steps] for n in STACKS}
+    assert kinds["decoder_head1"] == ["conv"] and kinds["decoder_head2"] == ["conv", "bn", "conv"]
+    assert len(model._runner("decoder_head2").seq) == 4 and len(model.decoder_head2) == 5
+    assert model._runner("decoder_head2").params == list(model.decoder_head2.parameters())
+    n_before = len(list(model.parameters()))
+    assert len(list(model.parameters())) == n_before and "_runners" not in dict(model.named_modules())
+    # the largest activation of a decode pass covers the heads
+    per = model.max_elems_per_image("decode", (16, 8, 8))
+    assert per >= 8 * 32 * 32 and model.max_elems_per_image("forward", (2, 32, 32)) >= per
+    with pytest.raises(NotImplementedError, match="single-process"):
+        model.set_sync_bn(lambda s: s)
+
+
+@pytest.mark.parametrize("nclasses", [3, 5, 12])
+def test_unsupported_class_counts_raise(nclasses):
+    from superresolution_aniso_mri_amd.networks.acai_multi_channel import MultiChannelAE
+    with pytest.raises(ValueError, match="nclasses=%d" % nclasses):
+        MultiChannelAE(small_args("40x36", nclasses=nclasses))
+
+
+# ---- the restatement against the reference's float64 ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("size", SMALL)
+def test_float64_restatement_reproduces_the_reference(size):
+    rec = load("mc_ae_small_%s.npz" % size)
+    x = rec["x"]
+    r = softmax_dice_f64(rec["logits"], x[:, 1])
+    assert float((r["probs"] - torch.from_numpy(rec["ref64/soft_probs"])).abs().max()) <= 1e-12
+    assert abs(float(r["loss"]) - float(rec["ref64/loss_label"])) <= 1e-12
+    assert float((r["dprobs"] - torch.from_numpy(rec["ref64/dsoft_probs"])).abs().max()) <= 1e-12
+    assert float((r["dlogits"] - torch.from_numpy(rec["ref64/dlogits"])).abs().max()) <= 1e-12
+    # and the fp32 run of the reference within fp32 rounding of it: the loss, and the gradient that reached soft_probs (0.1 * Dice)
+    assert abs(float(r["loss"]) - float(rec["loss_label"])) <= 2e-6 * abs(float(rec["loss_label"]))
+    assert float((r["probs"] - torch.from_numpy(rec["soft_probs"]).double()).abs().max()) <= 1e-6
+    w = float(rec["label_weight"])
+    d32 = torch.from_numpy(rec["dsoft_probs"]).double()
+    assert float((w * r["dprobs"] - d32).norm() / d32.norm()) <= 1e-5
+    # the upstream gradient scales both gradients
+    r2 = softmax_dice_f64(rec["logits"], x[:, 1], g=w)
+    assert torch.equal(r2["loss"], r["loss"]) and float((r2["dlogits"] - w * r["dlogits"]).abs().max()) <= 1e-18
+    # the census the fixture promises: every class occurs, one sample lacks a class
+    R = r["R"]
+    assert bool((R.sum(0) > 0).all()) and bool((R == 0).any()) and float(R.sum()) == x[:, 1].size
+
+
+def test_restatement_gives_foreign_labels_to_no_class():
+    logits = torch.randn(2, 4, 3, 5, generator=torch.Generator().manual_seed(1))
+    labels = torch.randint(0, 4, (2, 3, 5), generator=torch.Generator().manual_seed(2)).float()
+    labels[0, 0, 0], labels[0, 1, 1], labels[1, 2, 2] = 4.0, -1.0, 1.5
+    r = softmax_dice_f64(logits, labels)
+    assert float(r["R"].sum()) == 2 * 3 * 5 - 3
+    assert abs(float(r["P"].sum()) - 30.0) < 1e-12          # every pixel still adds its probabilities
+    with pytest.raises(RuntimeError):                      # the reference's scatter_ raises instead
+        torch.zeros(2, 4, 3, 5).scatter_(1, labels.long().unsqueeze(1), 1)
+
+
+@pytest.mark.parametrize("size", SMALL)
+def test_dice_loss_module_on_soft_probabilities(size):
+    from superresolution_aniso_mri_amd.kwatsch.dice_loss import DiceLoss, soft_dice_score
+    rec = load("mc_ae_small_%s.npz" % size)
+    sp = torch.from_numpy(rec["soft_probs"]).requires_grad_(True)
+    target = torch.from_numpy(rec["x"][:, 1]).to(torch.int64)
+    loss = DiceLoss(4)(sp, target)
+    assert abs(float(loss) - float(rec["loss_label"])) <= 2e-6 * abs(float(rec["loss_label"]))
+    (float(rec["label_weight"]) * loss).backward()
+    d32 = torch.from_numpy(rec["dsoft_probs"]).double()
+    assert float((sp.grad.double() - d32).norm() / d32.norm()) <= 1e-5
+    one_hot = torch.zeros(sp.shape).scatter_(1, target.unsqueeze(1), 1)
+    assert torch.equal(soft_dice_score(sp.detach(), one_hot), loss.detach())
+    assert DiceLoss(4).n_classes == 4
+
+
+# ---- the seventh header ------------------------------------------------------------------------------------------------------------
+def _declared(header):
+    hdr = open(os.path.join(ROOT, "include", header)).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    return set(re.findall(r"\b(aesr_[a-z0-9_]+)\s*\(", hdr))
+
+
+SEG_NAMES = {"aesr_softmax_dice_workspace_floats", "aesr_softmax_dice_fwd", "aesr_softmax_dice_bwd"}
+OTHER_HEADERS = ("aesr_hip.h", "aesr_hip_preproc.h", "aesr_hip_dataprep.h", "aesr_hip_train.h", "aesr_hip_baselines.h", "aesr_hip_reslice.h")
+
+
+def test_seg_header_table_and_exports_agree():
+    from superresolution_aniso_mri_amd import _hip
+    declared = _declared("aesr_hip_seg.h")
+    assert declared == set(_hip.SIGNATURES_SEG) == SEG_NAMES
+    others = (set(_hip.SIGNATURES) | set(_hip.SIGNATURES_PREPROC) | set(_hip.SIGNATURES_DATAPREP) | set(_hip.SIGNATURES_TRAIN)
+              | set(_hip.SIGNATURES_BASELINES) | set(_hip.SIGNATURES_RESLICE))
+    for header in OTHER_HEADERS:
+        others |= _declared(header)
+    assert not declared & others
+    lib = ctypes.CDLL(_hip.LIB_PATH)
+    P, I, S = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+    for name in declared:
+        assert getattr(lib, name, None) is not None, "%s is declared in include/aesr_hip_seg.h but not exported" % name
+        res, args = _hip.SIGNATURES_SEG[name]
+        assert getattr(_hip.lib, name).argtypes == args and getattr(_hip.lib, name).restype == res
+    assert _hip.SIGNATURES_SEG["aesr_softmax_dice_workspace_floats"] == (S, [I] * 4)
+    assert _hip.SIGNATURES_SEG["aesr_softmax_dice_fwd"] == (I, [P, P, S, P, P, P, P, P, I, I, I, I, P])
+    assert _hip.SIGNATURES_SEG["aesr_softmax_dice_bwd"] == (I, [P, P, S, P, P, P, I, I, I, I, P])
+    # the source and the header are wired into the build
+    mk = open(os.path.join(ROOT, "superresolution_aniso_mri_amd", "csrc", "Makefile")).read()
+    assert re.search(r"^SRCS = .*\bseg_head\.hip\b", mk, flags=re.M) and mk.count("../../include/aesr_hip_seg.h") == 2
+
+
+def test_guard_band_cases_and_exemptions_partition_the_seg_abi():
+    """The rule of tests/test_memguard_host.py::test_case_table_and_exemptions_partition_the_abi for the seventh table."""
+    import test_gpu_multichannel as tg
+    covered, exempt = set(tg.GUARDED_ENTRIES), set(tg.EXEMPT)
+    assert not (covered & exempt) and covered | exempt == SEG_NAMES
+    for name, reason in tg.EXEMPT.items():
+        assert reason and name.endswith("_floats"), "%s is a launch entry point: it needs a case" % name
+    assert covered == {"aesr_softmax_dice_fwd", "aesr_softmax_dice_bwd"}
+
+
+def test_entry_points_check_their_arguments_on_the_host():
+    """Every refusal comes before anything touches the device: callable without a GPU; the pointers below are never dereferenced."""
+    from superresolution_aniso_mri_amd import _hip
+    P = ctypes.c_void_p
+    lib, err = _hip.lib, _hip.last_error
+    ws = lib.aesr_softmax_dice_workspace_floats
+    assert ws(3, 64, 65, 4) == 3 * 5 * 12 and ws(1, 1, 1, 3) == 9 and ws(2, 32, 32, 8) == 2 * 1 * 24
+    assert ws(1, 4, 4, 9) == 0 and ws(1, 4, 4, 1) == 0 and ws(0, 4, 4, 4) == 0 and ws(2, 32768, 32768, 4) == 0
+    logits, labels, probs, amax, part, sums, loss, g = (P((i + 1) << 24) for i in range(8))
+    fnames = ["logits", "labels", "label_stride", "probs", "argmax", "partial", "sums", "loss", "N", "H", "W", "K", "stream"]
+    fok = [logits, labels, 2 * 12, probs, amax, part, sums, loss, 2, 3, 4, 4, None]
+    bnames = ["probs", "labels", "label_stride", "sums", "gloss", "dlogits", "N", "H", "W", "K", "stream"]
+    bok = [probs, labels, 2 * 12, sums, g, logits, 2, 3, 4, 4, None]
+
+    def call(fn, names, ok, **over):
+        args = list(ok)
+        for k, v in over.items():
+            args[names.index(k)] = v
+        return fn(*args)
+
+    for fn, names, ok in ((lib.aesr_softmax_dice_fwd, fnames, fok), (lib.aesr_softmax_dice_bwd, bnames, bok)):
+        for bad in (dict(K=1), dict(K=9), dict(N=0), dict(H=-1), dict(W=0), dict(N=1 << 20, H=1 << 10, W=1 << 10), dict(label_stride=11),
+                    dict(probs=None), dict(probs=P((1 << 20) + 2)), dict(sums=P((1 << 21) + 4))):
+            assert call(fn, names, ok, **bad) == 1, bad
+            assert "aesr_softmax_dice" in err()
+    assert call(lib.aesr_softmax_dice_fwd, fnames, fok, K=9) == 1 and "K=9" in err()
+    assert call(lib.aesr_softmax_dice_fwd, fnames, fok, sums=None) == 1 and "labels are given" in err()
+    assert call(lib.aesr_softmax_dice_bwd, bnames, bok, gloss=None) == 1 and "null" in err()
+    # outputs that overlap inputs are refused as unsupported
+    assert call(lib.aesr_softmax_dice_fwd, fnames, fok, probs=logits) == 3 and "overlaps" in err()
+    assert call(lib.aesr_softmax_dice_bwd, bnames, bok, dlogits=probs) == 3 and "overlaps" in err()
+
+
+def test_host_wrappers_refuse_what_the_device_path_cannot_take():
+    from superresolution_aniso_mri_amd import ops
+    with pytest.raises(RuntimeError, match="GPU"):
+        ops.softmax_dice(torch.zeros(1, 2, 2, 4), torch.zeros(1, 2, 2))
+    with pytest.raises(RuntimeError, match="GPU"):
+        ops.softmax_argmax(torch.zeros(1, 2, 2, 4))
