@@ -1,5 +1,5 @@
 """ctypes binding of libaesr_hip.so (C ABI: include/aesr_hip.h, include/aesr_hip_preproc.h, include/aesr_hip_dataprep.h, include/aesr_hip_train.h,
-include/aesr_hip_baselines.h, include/aesr_hip_reslice.h and include/aesr_hip_seg.h).
+include/aesr_hip_baselines.h, include/aesr_hip_reslice.h, include/aesr_hip_seg.h and include/aesr_hip_surface.h).
 
 There is NO fallback: if the shared library is missing or an entry point is absent this module raises at
 import time, and every wrapper raises RuntimeError with the library's own message when a call fails.
@@ -207,6 +207,14 @@ SIGNATURES_SEG = {
     "aesr_softmax_dice_fwd": (c_int, [P, P, c_size_t] + [P] * 5 + [c_int] * 4 + [P]),
     "aesr_softmax_dice_bwd": (c_int, [P, P, c_size_t, P, P, P] + [c_int] * 4 + [P]),
 }
+# the segmentation-score ABI (include/aesr_hip_surface.h, same library): must list every symbol that header declares (checked by tests)
+LLP = ctypes.POINTER(ctypes.c_longlong)     # host array of int64
+SIGNATURES_SURFACE = {
+    "aesr_surface_workspace_bytes": (c_size_t, [c_int] * 5),
+    "aesr_surface_borders": (c_int, [P, P, P, P] + [c_int] * 4 + [IP, c_int, c_int, c_int, P]),
+    "aesr_surface_distances": (c_int, [P, P, LLP, P, c_size_t, P] + [c_int] * 6 + [DP, P]),
+}
+SURFACE_MAX_CLASSES, SURFACE_COUNTS, SURFACE_MAX_W = 8, 7, 4096          # AESR_SURFACE_* of include/aesr_hip_surface.h
 SEG_MIN_CLASSES, SEG_MAX_CLASSES = 2, 8
 RESLICE_NEAREST, RESLICE_LINEAR = 0, 1          # AESR_RESLICE_* (RS_* below are the modes of aesr_resample2_*)
 ZX_ALIGN_ITK, ZX_ALIGN_GRID, ZX_CLAMP, ZX_MIRROR = 0, 1, 0, 1
@@ -233,7 +241,7 @@ def _load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_PREPROC.items()) + list(SIGNATURES_DATAPREP.items())
                                    + list(SIGNATURES_TRAIN.items()) + list(SIGNATURES_BASELINES.items()) + list(SIGNATURES_RESLICE.items())
-                                   + list(SIGNATURES_SEG.items())):
+                                   + list(SIGNATURES_SEG.items()) + list(SIGNATURES_SURFACE.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             raise RuntimeError("libaesr_hip.so does not export %s (stale build?)" % name)

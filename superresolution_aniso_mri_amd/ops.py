@@ -527,3 +527,68 @@ def softmax_nhwc(logits_nhwc):
 def softmax_argmax(logits_nhwc):
     """Inference: (probs [N, H, W, K], argmax int32 [N, H, W]; ties go to the lowest class) in one pass, no gradient."""
     return _softmax_argmax_raw(logits_nhwc.detach(), True)
+
+
+# ---- segmentation scores: overlap counts and surface distances (include/aesr_hip_surface.h, csrc/seg_metrics.hip) -----------------------
+def _surface_check_volumes(result, reference):
+    for t, name in ((result, "result"), (reference, "reference")):
+        _hip.require_gpu_tensor(t, name)
+    if result.dim() != 4 or tuple(result.shape) != tuple(reference.shape):
+        raise ValueError("result and reference must both be [N, Z, H, W] (got %s and %s)" % (tuple(result.shape), tuple(reference.shape)))
+    if result.device != reference.device:
+        raise RuntimeError("result and reference live on different devices")
+    return tuple(int(s) for s in result.shape)
+
+
+def surface_label_path(result, reference):
+    """Which label loads ``aesr_surface_borders`` takes for these tensors, by the rule of include/aesr_hip_surface.h: "vec16" when both
+    are 16-byte aligned and Z * H * W is a multiple of 4, else "scalar4".  The values do not depend on it."""
+    V = int(result[0].numel())
+    return "vec16" if result.data_ptr() % 16 == 0 and reference.data_ptr() % 16 == 0 and V % 4 == 0 else "scalar4"
+
+
+def surface_workspace_bytes(N, Z, H, W, C):
+    """Bytes of workspace both phases share for N volume pairs [Z, H, W] and C classes (0: a size the library refuses)."""
+    return int(lib.aesr_surface_workspace_bytes(int(N), int(Z), int(H), int(W), int(C)))
+
+
+def surface_borders(result, reference, classes, ndim=3, connectivity=1, workspace=None):
+    """Phase one.  result, reference: CUDA fp32 [N, Z, H, W] label volumes; classes: the class ids.  Returns (counts int64 [N, C, 7] on the
+    device = |A|, |B|, |A n B|, |A u B|, voxels, border voxels of A, of B; workspace, a uint8 tensor phase two reads).  No host sync."""
+    N, Z, H, W = _surface_check_volumes(result, reference)
+    classes = [int(c) for c in classes]
+    C = len(classes)
+    nbytes = surface_workspace_bytes(N, Z, H, W, C)
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 16), device=result.device, dtype=torch.uint8)
+    elif workspace.numel() < nbytes or not workspace.is_cuda or workspace.dtype != torch.uint8:
+        raise ValueError("workspace must be a CUDA uint8 tensor of at least %d bytes" % nbytes)
+    counts = torch.empty((N, max(C, 1), _hip.SURFACE_COUNTS), device=result.device, dtype=torch.int64)
+    check(lib.aesr_surface_borders(ptr(result), ptr(reference), ptr(workspace), ptr(counts), N, Z, H, W, _hip.int_array(classes), C, int(ndim),
+                                   int(connectivity), stream()), "aesr_surface_borders")
+    return counts, workspace
+
+
+def surface_list_lengths(counts_host):
+    """[N, C, 2] list lengths from the host copy of the counts: the border count of the source side, 0 where either mask is empty."""
+    c = np.asarray(counts_host, dtype=np.int64)
+    both = (c[..., 0] > 0) & (c[..., 1] > 0)
+    return np.where(both[..., None], c[..., 5:7], 0)
+
+
+def surface_distances(workspace, counts, shape, spacing, ndim=3, counts_host=None):
+    """Phase two, after ``surface_borders`` with the same shape / classes / ndim.  Returns (distances fp64 [sum of lengths] on the device,
+    packed in the order (n, class, direction), stats fp64 [N, C, 2, 2] = (sum, max) per list, lengths int64 numpy [N, C, 2]).  Copies
+    ``counts`` to the host unless ``counts_host`` is given -- the one synchronisation of a scoring call."""
+    N, Z, H, W = (int(s) for s in shape)
+    C = int(counts.shape[1])
+    if counts_host is None:
+        counts_host = counts.cpu().numpy()
+    counts_host = np.ascontiguousarray(counts_host, dtype=np.int64)
+    lengths = surface_list_lengths(counts_host)
+    total = int(lengths.sum())
+    distances = torch.empty(max(total, 1), device=counts.device, dtype=torch.float64)
+    stats = torch.empty((N, C, 2, 2), device=counts.device, dtype=torch.float64)
+    check(lib.aesr_surface_distances(ptr(workspace), ptr(counts), counts_host.ctypes.data_as(_hip.LLP), ptr(distances), total if total else 1,
+                                     ptr(stats), N, Z, H, W, C, int(ndim), _hip.double_array(spacing), stream()), "aesr_surface_distances")
+    return distances[:total], stats, lengths
