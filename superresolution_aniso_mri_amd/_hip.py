@@ -1,5 +1,6 @@
 """ctypes binding of libaesr_hip.so (C ABI: include/aesr_hip.h, include/aesr_hip_preproc.h, include/aesr_hip_dataprep.h, include/aesr_hip_train.h,
-include/aesr_hip_baselines.h, include/aesr_hip_reslice.h, include/aesr_hip_seg.h and include/aesr_hip_surface.h).
+include/aesr_hip_baselines.h, include/aesr_hip_reslice.h, include/aesr_hip_seg.h, include/aesr_hip_surface.h and
+include/aesr_hip_bnpool.h).
 
 There is NO fallback: if the shared library is missing or an entry point is absent this module raises at
 import time, and every wrapper raises RuntimeError with the library's own message when a call fails.
@@ -187,6 +188,14 @@ SIGNATURES_TRAIN = {
     "aesr_conv2d_cout1_bwd_workspace_floats": (c_size_t, [c_int]),
     "aesr_conv2d_cout1_bwd": (c_int, [P] * 8 + [c_int] * 5 + [c_float, c_int, c_float, P]),
 }
+# BatchNorm + AvgPool2d(2) pooled once in the statistics pass (include/aesr_hip_bnpool.h, same library): must list every symbol that header
+# declares (checked by tests)
+SIGNATURES_BNPOOL = {
+    "aesr_bn_pool_supported": (c_int, [c_int] * 5),
+    "aesr_bn_pool_stats_finalize": (c_int, [P, P, P, DP] + [P] * 9 + [c_int] * 5 + [IP, c_float, c_float, c_int, P]),
+    "aesr_bn_pool_apply": (c_int, [P, P, P, P] + [c_int] * 5 + [IP, P]),
+    "aesr_bn_pool_bwd": (c_int, [P] * 7 + [DP] + [P] * 4 + [c_int] * 5 + [c_float, c_int, IP, P]),
+}
 # the conventional through-plane interpolation ABI (include/aesr_hip_baselines.h, same library): must list every symbol that header declares
 # (checked by tests)
 SIGNATURES_BASELINES = {
@@ -241,7 +250,7 @@ def _load():
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_PREPROC.items()) + list(SIGNATURES_DATAPREP.items())
                                    + list(SIGNATURES_TRAIN.items()) + list(SIGNATURES_BASELINES.items()) + list(SIGNATURES_RESLICE.items())
-                                   + list(SIGNATURES_SEG.items()) + list(SIGNATURES_SURFACE.items())):
+                                   + list(SIGNATURES_SEG.items()) + list(SIGNATURES_SURFACE.items()) + list(SIGNATURES_BNPOOL.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             raise RuntimeError("libaesr_hip.so does not export %s (stale build?)" % name)

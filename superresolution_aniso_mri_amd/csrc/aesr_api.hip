@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "../../include/aesr_hip.h"
+#include "../../include/aesr_hip_bnpool.h"
 #include "../../include/aesr_hip_dataprep.h"
 #include "../../include/aesr_hip_train.h"
 #include "aesr_kernels.h"
@@ -829,6 +830,64 @@ int aesr_bn_bwd(const float* gout, const float* y, const float* mean, const floa
                    "aesr_bn_bwd: bad arguments");
     AESR_CHECK_ARG((double)N * H * W < 2147483648.0, "aesr_bn_bwd: more than 2^31 pixels");
     if (int e = aesr_launch_bn_bwd_reduce(a, AESR_BN_NWG, (hipStream_t)stream)) return e;
+    if (int e = aesr_launch_bn_bwd_reduce_finalize(partial, AESR_BN_NWG, counts_host, coef, dgamma, dbeta, C, G, (hipStream_t)stream))
+        return e;
+    return aesr_launch_bn_bwd_apply(a, (hipStream_t)stream);
+}
+
+// ---- include/aesr_hip_bnpool.h: BatchNorm + AvgPool2d(2), pooled once in the statistics pass ------------------------------------------
+int aesr_bn_pool_supported(int N, int H, int W, int C, int G) {
+    if (C < 4 || C % 4 != 0 || C > 1024 || 256 % (C / 4) != 0) return 0;        // what the kernels' (channel quad, lane) layout takes
+    if (H < 2 || W < 2 || G < 1 || G > 4 || N < G) return 0;
+    return (double)N * H * W < 2147483648.0 ? 1 : 0;
+}
+
+// the shape and the group table of an entry point of this header: groups non-empty, in order, covering exactly the N images
+static bool bn_pool_groups(BnGroups* gr, int N, int H, int W, int C, int G, const int* nstart_host) {
+    if (!aesr_bn_pool_supported(N, H, W, C, G) || !fill_groups(gr, G, nstart_host)) return false;
+    if (gr->nstart[0] != 0 || gr->nstart[G] != N) return false;
+    for (int g = 0; g < G; ++g)
+        if (gr->nstart[g + 1] <= gr->nstart[g]) return false;
+    return true;
+}
+
+int aesr_bn_pool_stats_finalize(const float* y, float* m, float* partial, const double* counts_host, const float* gamma, const float* beta,
+                                float* running_mean, float* running_var, int64_t* num_batches_tracked, float* mean, float* invstd,
+                                float* scale, float* shift, int N, int H, int W, int C, int G, const int* nstart_host, float momentum,
+                                float eps, int update_running, void* stream) {
+    BnPoolStatsArgs a;
+    memset(&a, 0, sizeof(a));
+    AESR_CHECK_ARG(y && m && partial && counts_host && gamma && beta && mean && invstd && scale && shift,
+                   "aesr_bn_pool_stats_finalize: null pointer");
+    AESR_CHECK_ARG(bn_pool_groups(&a.gr, N, H, W, C, G, nstart_host),
+                   "aesr_bn_pool_stats_finalize: N=%d H=%d W=%d C=%d G=%d or the group table is not supported (aesr_bn_pool_supported)", N, H, W, C, G);
+    a.y = y; a.m = m; a.partial = partial; a.H = H; a.W = W; a.C = C; a.Ho = H / 2; a.Wo = W / 2;
+    if (int e = aesr_launch_bn_pool_stats(a, AESR_BN_NWG, (hipStream_t)stream)) return e;
+    return aesr_launch_bn_reduce_finalize(partial, AESR_BN_NWG, counts_host, gamma, beta, running_mean, running_var,
+                                          (long long*)num_batches_tracked, mean, invstd, scale, shift, C, G, momentum, eps,
+                                          update_running && running_mean && running_var, (hipStream_t)stream);
+}
+
+int aesr_bn_pool_apply(const float* m, const float* scale, const float* shift, float* out, int N, int Ho, int Wo, int C, int G,
+                       const int* nstart_host, void* stream) {
+    BnGroups gr;
+    AESR_CHECK_ARG(m && scale && shift && out, "aesr_bn_pool_apply: null pointer");
+    AESR_CHECK_ARG(Ho >= 1 && Wo >= 1 && (double)Ho * Wo < 536870912.0 && bn_pool_groups(&gr, N, 2 * Ho, 2 * Wo, C, G, nstart_host),
+                   "aesr_bn_pool_apply: N=%d Ho=%d Wo=%d C=%d G=%d or the group table is not supported (aesr_bn_pool_supported)", N, Ho, Wo, C, G);
+    return aesr_launch_bn_pool_apply(m, scale, shift, out, Ho * Wo, C, gr, (hipStream_t)stream);
+}
+
+int aesr_bn_pool_bwd(const float* gout, const float* y, const float* m, const float* mean, const float* invstd, const float* scale,
+                     float* partial, const double* counts_host, float* coef, float* dgamma, float* dbeta, float* dpre, int N, int H, int W,
+                     int C, int act, float slope, int G, const int* nstart_host, void* stream) {
+    BnBwdArgs a;
+    AESR_CHECK_ARG(gout && y && m && mean && invstd && scale && partial && counts_host && coef && dgamma && dbeta && dpre,
+                   "aesr_bn_pool_bwd: null pointer");
+    AESR_CHECK_ARG(act >= ACT_NONE && act <= ACT_SIGMOID, "aesr_bn_pool_bwd: unknown activation code %d", act);
+    AESR_CHECK_ARG(bn_bwd_args(&a, gout, y, mean, invstd, scale, coef, partial, dpre, N, H, W, C, AESR_BN_POOL, act, slope, G, nstart_host) &&
+                       bn_pool_groups(&a.gr, N, H, W, C, G, nstart_host),
+                   "aesr_bn_pool_bwd: N=%d H=%d W=%d C=%d G=%d or the group table is not supported (aesr_bn_pool_supported)", N, H, W, C, G);
+    if (int e = aesr_launch_bn_pool_bwd_reduce(gout, m, mean, invstd, partial, a.Ho * a.Wo, C, a.gr, AESR_BN_NWG, (hipStream_t)stream)) return e;
     if (int e = aesr_launch_bn_bwd_reduce_finalize(partial, AESR_BN_NWG, counts_host, coef, dgamma, dbeta, C, G, (hipStream_t)stream))
         return e;
     return aesr_launch_bn_bwd_apply(a, (hipStream_t)stream);

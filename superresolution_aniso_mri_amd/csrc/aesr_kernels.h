@@ -228,6 +228,20 @@ int aesr_launch_bn_finalize_apply(const double* sums, const double* counts, cons
                                   float eps, int update_running, int G, const BnApplyArgs& a, hipStream_t st);
 int aesr_launch_bn_bwd_finalize_apply(const double* sums, const double* counts, float* coef, float* dgamma, float* dbeta, int G,
                                       const BnBwdArgs& a, hipStream_t st);
+// BatchNorm + AvgPool2d(2), pool once (include/aesr_hip_bnpool.h): the statistics pass writes the 2x2 means m [N][H/2][W/2][C]; the forward
+// apply and the backward reduce stream m (and the pooled gradient) instead of y
+struct BnPoolStatsArgs {
+    const float* y; float* m; float* partial;
+    int H, W, C, Ho, Wo;
+    BnGroups gr;
+    unsigned long long m_win, m_wo;   // exact-division constants for Ho*Wo and Wo (filled by the launcher)
+    int k_win, k_wo;
+};
+int aesr_launch_bn_pool_stats(const BnPoolStatsArgs& a, int nwg, hipStream_t st);
+int aesr_launch_bn_pool_apply(const float* m, const float* scale, const float* shift, float* out, int HoWo, int C, const BnGroups& gr,
+                              hipStream_t st);
+int aesr_launch_bn_pool_bwd_reduce(const float* gout, const float* m, const float* mean, const float* invstd, float* partial, int HoWo, int C,
+                                   const BnGroups& gr, int nwg, hipStream_t st);
 
 int aesr_launch_lerp_fwd(const float* z, const float* af, const float* at, float* zmix, int B, size_t per, hipStream_t st);
 int aesr_launch_lerp_bwd(const float* dmix, const float* af, const float* at, float* dz, int B, size_t per, hipStream_t st);

@@ -366,6 +366,152 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_apply_kernel(const double
     bn_bwd_apply_loop<MODE>(a, s_k);
 }
 
+// ---- BatchNorm + AvgPool2d(2), pool once (include/aesr_hip_bnpool.h) ------------------------------------------------
+// The fourth launch form, for the three-launch route in POOL mode.  The statistics pass has every 2x2 window in registers anyway: it also
+// writes the window's mean m [N][Ho][Wo][C], and the two other streaming passes that needed y only through that mean read m instead:
+//   forward   bn_stats_kernel_pool -> bn_reduce_finalize_kernel -> bn_apply_kernel_pooled          out = scale * m + shift
+//   backward  bn_bwd_reduce_kernel_pooled -> bn_bwd_reduce_finalize_kernel -> bn_bwd_apply_kernel<BN_MODE_POOL>
+// Every pixel of a window carries the gradient g_pool / 4 and the pixels the pooling leaves out (odd H / W) carry none, so
+//   sum g = sum_windows g_pool        sum g * xhat = sum_windows g_pool * ((m - mean) * invstd).
+// m, and out / dpre for given tables, are bit for bit the three-launch route's (the same expressions of bn_math.h); the per-channel sums are
+// taken over windows instead of pixels, which moves them by summation order only.
+
+// partial[g][wg][2][C] as bn_stats_kernel; grid = (nwg, G).  A thread owns (channel quad, 2x2 window): four independent 16-byte loads per trip.
+// ODD: H or W is odd, the pooling leaves a row / column out (even sizes compile without that loop).
+template <bool ODD>
+__global__ __launch_bounds__(256) void bn_stats_kernel_pool(BnPoolStatsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float red[];   // [PL][2][C]
+    const int C = a.C, C4 = C >> 2, PL = 256 / C4;
+    const int c4 = threadIdx.x % C4, pl = threadIdx.x / C4;
+    const int g = blockIdx.y;
+    const unsigned HoWo = a.Ho * a.Wo;                            // host checks N*H*W < 2^31
+    f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
+    if (pl < PL) {
+        const unsigned S = gridDim.x * PL;
+        const size_t row = (size_t)a.W * C;
+        const unsigned w1 = a.gr.nstart[g + 1] * HoWo;
+        for (unsigned w = a.gr.nstart[g] * HoWo + blockIdx.x * PL + pl; w < w1; w += S) {
+            const unsigned n = bn_fastdiv(w, a.m_win, a.k_win);
+            const unsigned rem = w - n * HoWo;
+            const unsigned py = bn_fastdiv(rem, a.m_wo, a.k_wo), px = rem - py * a.Wo;
+            const float* b = a.y + (((size_t)n * a.H + 2 * py) * a.W + 2 * px) * C + c4 * 4;
+            const f32x4 v00 = *(const f32x4*)b, v01 = *(const f32x4*)(b + C);
+            const f32x4 v10 = *(const f32x4*)(b + row), v11 = *(const f32x4*)(b + row + C);
+            s += (v00 + v01) + (v10 + v11);
+            q += (v00 * v00 + v01 * v01) + (v10 * v10 + v11 * v11);
+            *(f32x4*)(a.m + (size_t)w * C + c4 * 4) = bn_pool2x2(v00, v01, v10, v11);
+        }
+        // what the pooling leaves out still counts for the statistics: the last column (odd W: H pixels per image), then the rest of the
+        // last row (odd H: 2 * Wo pixels)
+        const unsigned Tc = (a.W & 1) ? a.H : 0, T = Tc + ((a.H & 1) ? 2 * a.Wo : 0);
+        if (ODD && T) {
+            const unsigned t1 = a.gr.nstart[g + 1] * T;
+            for (unsigned t = a.gr.nstart[g] * T + blockIdx.x * PL + pl; t < t1; t += S) {
+                const unsigned n = t / T, r = t - n * T;
+                const unsigned yy = r < Tc ? r : a.H - 1, x = r < Tc ? a.W - 1 : r - Tc;
+                const f32x4 v = *(const f32x4*)(a.y + (((size_t)n * a.H + yy) * a.W + x) * C + c4 * 4);
+                s += v;
+                q += v * v;
+            }
+        }
+        *(f32x4*)(red + (pl * 2 + 0) * C + c4 * 4) = s;
+        *(f32x4*)(red + (pl * 2 + 1) * C + c4 * 4) = q;
+    }
+    __syncthreads();
+    for (int o = threadIdx.x; o < 2 * C; o += 256) {
+        float t = 0.f;
+        for (int k = 0; k < PL; ++k) t += red[k * 2 * C + o];
+        a.partial[((size_t)g * gridDim.x + blockIdx.x) * 2 * C + o] = t;
+    }
+}
+
+// out = scale * m + shift, flat over the pooled tensor; per = vectors per image.  The stride is a multiple of 256 and 256 one of C/4, so a
+// thread keeps its channel quad; the group follows from the groups' first vectors (nstart is padded with N behind the last group).
+// U independent vectors in flight per thread.
+template <int U>
+__global__ __launch_bounds__(256) void bn_apply_kernel_pooled(const float* __restrict__ m, const float* __restrict__ scale,
+                                                              const float* __restrict__ shift, float* __restrict__ out, size_t per, int C,
+                                                              BnGroups gr) {
+    const int c4 = threadIdx.x % (C >> 2);
+    const size_t total = gr.nstart[gr.G] * per, b1 = gr.nstart[1] * per, b2 = gr.nstart[2] * per, b3 = gr.nstart[3] * per;
+    const size_t S = (size_t)gridDim.x * 256;
+    size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    for (; idx + (U - 1) * S < total; idx += U * S) {
+        f32x4 v[U], sc[U], sh[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const size_t i = idx + u * S;
+            const int g = (int)(i >= b1) + (int)(i >= b2) + (int)(i >= b3);
+            v[u] = *(const f32x4*)(m + i * 4);
+            sc[u] = *(const f32x4*)(scale + g * C + c4 * 4);
+            sh[u] = *(const f32x4*)(shift + g * C + c4 * 4);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) *(f32x4*)(out + (idx + u * S) * 4) = bn_fwd_elem(v[u], sc[u], sh[u]);
+    }
+    for (; idx < total; idx += S) {
+        const int g = (int)(idx >= b1) + (int)(idx >= b2) + (int)(idx >= b3);
+        const f32x4 sc = *(const f32x4*)(scale + g * C + c4 * 4);
+        const f32x4 sh = *(const f32x4*)(shift + g * C + c4 * 4);
+        *(f32x4*)(out + idx * 4) = bn_fwd_elem(*(const f32x4*)(m + idx * 4), sc, sh);
+    }
+}
+
+// partial[g][wg][2][C] as bn_bwd_reduce_kernel; grid = (nwg, G).  Both operands are read flat, U windows in flight per thread.
+template <int U>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel_pooled(const float* __restrict__ gout, const float* __restrict__ m,
+                                                                   const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                   float* __restrict__ partial, unsigned HoWo, int C, BnGroups gr) {
+    extern __shared__ __attribute__((aligned(16))) float red[];
+    const int C4 = C >> 2, PL = 256 / C4;
+    const int c4 = threadIdx.x % C4, pl = threadIdx.x / C4;
+    const int g = blockIdx.y;
+    const unsigned w1 = gr.nstart[g + 1] * HoWo;
+    const f32x4 mu = *(const f32x4*)(mean + g * C + c4 * 4);
+    const f32x4 iv = *(const f32x4*)(invstd + g * C + c4 * 4);
+    f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+    if (pl < PL) {
+        const unsigned S = gridDim.x * PL;
+        unsigned w = gr.nstart[g] * HoWo + blockIdx.x * PL + pl;
+        f32x4 a1[U], a2[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) a1[u] = a2[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (; w + (U - 1) * S < w1; w += U * S) {
+            f32x4 mv[U], gq[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const size_t o = (size_t)(w + u * S) * C + c4 * 4;
+                gq[u] = *(const f32x4*)(gout + o);
+                mv[u] = *(const f32x4*)(m + o);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                a1[u] += gq[u];
+                a2[u] += gq[u] * ((mv[u] - mu) * iv);
+            }
+        }
+        for (; w < w1; w += S) {
+            const size_t o = (size_t)w * C + c4 * 4;
+            const f32x4 gg = *(const f32x4*)(gout + o);
+            s1 += gg;
+            s2 += gg * ((*(const f32x4*)(m + o) - mu) * iv);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            s1 += a1[u];
+            s2 += a2[u];
+        }
+        *(f32x4*)(red + (pl * 2 + 0) * C + c4 * 4) = s1;
+        *(f32x4*)(red + (pl * 2 + 1) * C + c4 * 4) = s2;
+    }
+    __syncthreads();
+    for (int o = threadIdx.x; o < 2 * C; o += 256) {
+        float t = 0.f;
+        for (int k = 0; k < PL; ++k) t += red[k * 2 * C + o];
+        partial[((size_t)g * gridDim.x + blockIdx.x) * 2 * C + o] = t;
+    }
+}
+
 // ---- launchers ----------------------------------------------------------------------------------------------
 static int bn_check_c(int C, const char* who) {
     if (C % 4 != 0 || 256 % (C / 4) != 0 || C > 1024) {
@@ -506,5 +652,39 @@ int aesr_launch_bn_bwd_finalize_apply(const double* sums, const double* counts, 
     BN_LAUNCH_MODE(bn_bwd_finalize_apply_kernel, a.mode, bn_stream_grid((size_t)a.N * a.H * a.W, a.C), 0, st, sums, bn_counts(counts, G), coef,
                    dgamma, dbeta, G, a);
     AESR_LAUNCH_CHECK("bn_bwd_finalize_apply");
+    return AESR_OK;
+}
+
+// BatchNorm + AvgPool2d(2), pool once.  (Last in the file, and the kernels templates: their instantiations follow the older ones, whose
+// listings keep their label numbers -- scripts/isa_same.py compares them line by line.)
+int aesr_launch_bn_pool_stats(const BnPoolStatsArgs& a_in, int nwg, hipStream_t st) {
+    BnPoolStatsArgs a = a_in;
+    if (int e = bn_check_c(a.C, "bn_pool_stats")) return e;
+    bn_magic((unsigned)(a.Ho * a.Wo), &a.m_win, &a.k_win);
+    bn_magic((unsigned)a.Wo, &a.m_wo, &a.k_wo);
+    const int PL = 256 / (a.C / 4);
+    const size_t shm = (size_t)PL * 2 * a.C * sizeof(float);
+    if ((a.H | a.W) & 1) hipLaunchKernelGGL(bn_stats_kernel_pool<true>, dim3(nwg, a.gr.G), dim3(256), shm, st, a);
+    else hipLaunchKernelGGL(bn_stats_kernel_pool<false>, dim3(nwg, a.gr.G), dim3(256), shm, st, a);
+    AESR_LAUNCH_CHECK("bn_pool_stats");
+    return AESR_OK;
+}
+
+int aesr_launch_bn_pool_apply(const float* m, const float* scale, const float* shift, float* out, int HoWo, int C, const BnGroups& gr,
+                              hipStream_t st) {
+    if (int e = bn_check_c(C, "bn_pool_apply")) return e;
+    hipLaunchKernelGGL(bn_apply_kernel_pooled<2>, bn_stream_grid((size_t)gr.nstart[gr.G] * HoWo, C), dim3(256), 0, st, m, scale, shift, out,
+                       (size_t)HoWo * (C / 4), C, gr);
+    AESR_LAUNCH_CHECK("bn_pool_apply");
+    return AESR_OK;
+}
+
+int aesr_launch_bn_pool_bwd_reduce(const float* gout, const float* m, const float* mean, const float* invstd, float* partial, int HoWo, int C,
+                                   const BnGroups& gr, int nwg, hipStream_t st) {
+    if (int e = bn_check_c(C, "bn_pool_bwd_reduce")) return e;
+    const int PL = 256 / (C / 4);
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel_pooled<4>, dim3(nwg, gr.G), dim3(256), (size_t)PL * 2 * C * sizeof(float), st, gout, m, mean, invstd,
+                       partial, (unsigned)HoWo, C, gr);
+    AESR_LAUNCH_CHECK("bn_pool_bwd_reduce");
     return AESR_OK;
 }

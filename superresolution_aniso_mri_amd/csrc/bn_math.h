@@ -1,7 +1,9 @@
-// The arithmetic of nn.BatchNorm2d, stated ONCE for the three launch forms (device-inline only; included by bn.hip and bn_fused.hip):
+// The arithmetic of nn.BatchNorm2d, stated ONCE for the launch forms (device-inline only; included by bn.hip and bn_fused.hip):
 //   three launches   bn.hip: statistics -> [reduce +] finalize -> apply            (backward: reduce -> [reduce +] finalize -> apply)
 //   SyncBN           bn.hip: ... all-reduce of the sums, then finalize inside the apply launch  (bn_finalize_apply, bn_bwd_finalize_apply)
 //   one launch       bn_fused.hip: the layer resident in LDS, one grid barrier
+//   pooled once      bn.hip: the three launches with AvgPool2d(2) behind them; the statistics pass writes the 2x2 means, which the apply and the
+//                    backward reduction stream instead of the activation (include/aesr_hip_bnpool.h)
 // The forms differ in how the sums are reduced and in where the tables live; everything from the sums on is here.  The Makefile compiles
 // with -ffp-contract=off, so an expression means the same operations in the same order wherever it is inlined: the forms agree bit for bit
 // wherever they are given the same sums (tests/test_gpu_kernels.py: test_bn_groups_fwd_bwd).

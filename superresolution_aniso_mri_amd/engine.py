@@ -64,6 +64,11 @@ FUSE_STEM = os.environ.get("AESR_FUSE_STEM", "1") != "0"      # fold the encoder
 # input (aesr_conv2d_cout1_bwd, include/aesr_hip_train.h) instead of aesr_act_bwd + aesr_conv2d_cout1_wgrad + aesr_conv2d_cout1_dgrad_pre:
 # two launches for five, the largest activation of the step read once instead of twice, bit-identical results; =0 keeps the three calls
 FUSE_COUT1_BWD = os.environ.get("AESR_FUSE_COUT1_BWD", "1") != "0"
+# train-mode BatchNorm + AvgPool2d(2) on the single-process three-launch route: the statistics pass also writes the 2x2 means m, and the
+# forward apply and the backward reduction stream m (a quarter of the activation) instead of the activation (include/aesr_hip_bnpool.h);
+# m is kept with the activation for the backward pass.  Sums over windows instead of pixels: results move by summation order only.
+# =0 keeps aesr_bn_stats_finalize + aesr_bn_apply / aesr_bn_bwd
+BN_POOL_ONCE = os.environ.get("AESR_BN_POOL_ONCE", "1") != "0"
 # 3x3 / padding-1 convolutions with enough channels run in Winograd F(2x2,3x3) form (csrc/conv_wino.hip: 2.25x fewer MFMA flops,
 # results equal to the implicit GEMM within 2-4e-7); AESR_WINO=0 keeps every layer on the exact-fp32 fma-chain implicit GEMM
 USE_WINO = os.environ.get("AESR_WINO", "1") != "0"
@@ -508,8 +513,9 @@ class SequentialRunner:
                 bn = s.mod
                 Ho, Wo = s.out_hw(H, W)
                 out = _empty((N, Ho, Wo, C), x)
-                _pb("bn_fwd", 0.0, 4.0 * (cur.numel() + out.numel()))
-                st = self._bn_forward_stats(bn, cur, N, H, W, C, nstart, train, out, s.run_mode)
+                m = _empty((N, Ho, Wo, C), x) if self._bn_pool_once(bn, N, H, W, C, s.run_mode, G, train) else None
+                _pb("bn_fwd", 0.0, 4.0 * (cur.numel() + out.numel() + (0 if m is None else m.numel())))
+                st = self._bn_forward_stats(bn, cur, N, H, W, C, nstart, train, out, s.run_mode, m)
                 if not st.pop("applied", False):
                     check(lib.aesr_bn_apply(ptr(cur), ptr(st["scale"]), ptr(st["shift"]), ptr(out), N, H, W, C, s.run_mode, G,
                                             _hip.int_array(nstart), stream()), "aesr_bn_apply")
@@ -576,9 +582,22 @@ class SequentialRunner:
     sync_bn = None      # optional callable(sums[G,2,C] double) -> all-reduced in place across ranks (data parallel SyncBN)
     count_scale = 1.0   # data parallel: global / local sub-batch size (B_global / B_local of this rank)
 
-    def _bn_forward_stats(self, bn, y, N, H, W, C, nstart, train, out=None, run_mode=0):
+    def _bn_one_launch(self, N, H, W, C, run_mode, G, backward):
+        """Single process: does this BatchNorm call take the one-launch kernel (csrc/bn_fused.hip)?"""
+        return bool(self.sync_bn is None and bn_fused_enabled() and bn_fused_pays(N, H, W, C)
+                    and lib.aesr_bn_fused1_supported(N, H, W, C, run_mode, G, backward))
+
+    def _bn_pool_once(self, bn, N, H, W, C, run_mode, G, train):
+        """Does this forward call pool once in its statistics pass (``BN_POOL_ONCE``)?  Only the single-process three-launch route with batch
+        statistics and AvgPool2d(2) behind it; SyncBN, the one-launch form, eval mode and the other modes stay as they are."""
+        if not BN_POOL_ONCE or run_mode != _hip.BN_POOL or self.sync_bn is not None or not (train or bn.running_mean is None):
+            return False
+        return not self._bn_one_launch(N, H, W, C, run_mode, G, 0) and bool(lib.aesr_bn_pool_supported(N, H, W, C, G))
+
+    def _bn_forward_stats(self, bn, y, N, H, W, C, nstart, train, out=None, run_mode=0, m=None):
         """Statistics of a BatchNorm call -> {mean, invstd, scale, shift, counts}.  Data parallel (``sync_bn``) with ``out`` given: the
-        finalize runs inside the apply launch (``"applied": True`` in the result -- the caller must not apply again)."""
+        finalize runs inside the apply launch (``"applied": True`` in the result -- the caller must not apply again).  ``m`` (the caller asked
+        ``_bn_pool_once``): the pooled-once route, which fills ``m`` and ``out``; ``m`` stays in the result for the backward pass."""
         G = len(nstart) - 1
         dev = y.device
         st = {k: torch.empty((G, C), device=dev, dtype=torch.float32) for k in ("mean", "invstd", "scale", "shift")}
@@ -602,8 +621,7 @@ class SequentialRunner:
         st["counts"] = counts
         if use_batch:
             partial = torch.empty((G * _hip.BN_NWG * 2 * C,), device=dev, dtype=torch.float32)
-            local = (self.sync_bn is None and out is not None and bn_fused_enabled() and bn_fused_pays(N, H, W, C)
-                     and lib.aesr_bn_fused1_supported(N, H, W, C, run_mode, G, 0))
+            local = out is not None and self._bn_one_launch(N, H, W, C, run_mode, G, 0)
             if local or (self.sync_bn is not None and out is not None and self._p2p_fits(N, H, W, C, run_mode, G, 0)):
                 # small batch: statistics, finalize and apply in ONE launch, the layer resident in LDS in between.  Data parallel with the peer
                 # exchange: the same launch; workgroup 0 writes this rank's sums into every rank's region and every workgroup adds all
@@ -617,6 +635,18 @@ class SequentialRunner:
                 else:
                     p = self.sync_p2p
                     check(lib.aesr_bn_fused1_fwd_p2p(*args, p.peers, p.world, p.rank, p.next_slot(), ptr(p.gen), stream()), "aesr_bn_fused1_fwd_p2p")
+                st["applied"] = True
+                return st
+            if m is not None:               # single process, AvgPool2d(2) behind: the statistics pass pools, the apply streams the means
+                nsa = _hip.int_array(nstart)
+                check(lib.aesr_bn_pool_stats_finalize(ptr(y), ptr(m), ptr(partial), _hip.double_array(counts), ptr(bn.weight), ptr(bn.bias),
+                                                      ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked),
+                                                      ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]), ptr(st["shift"]), N, H, W, C,
+                                                      G, nsa, momentum, float(bn.eps), int(update), stream()),
+                      "aesr_bn_pool_stats_finalize")
+                check(lib.aesr_bn_pool_apply(ptr(m), ptr(st["scale"]), ptr(st["shift"]), ptr(out), N, H // 2, W // 2, C, G, nsa, stream()),
+                      "aesr_bn_pool_apply")
+                st["m"] = m
                 st["applied"] = True
                 return st
             if self.sync_bn is None:        # single process: statistics -> finalize without the sums round trip
@@ -849,9 +879,10 @@ class SequentialRunner:
                 coef = torch.empty((G, 2, C), device=dev, dtype=torch.float32)
                 dgamma, dbeta = self._grad_dst(s.mod.weight, grads), self._grad_dst(s.mod.bias, grads)
                 dpre = _empty((N, H, W, C), y)
-                _pb("bn_bwd", 0.0, 4.0 * (g.numel() + 2.0 * N * H * W * C))
-                local = (self.sync_bn is None and bn_fused_enabled() and bn_fused_pays(N, H, W, C)
-                         and lib.aesr_bn_fused1_supported(N, H, W, C, s.run_mode, G, 1))
+                local = self._bn_one_launch(N, H, W, C, s.run_mode, G, 1)
+                # the forward pass pooled once and kept the means: the reduction streams them and the pooled gradient instead of y
+                m = st.get("m") if (self.sync_bn is None and not local and lib.aesr_bn_pool_supported(N, H, W, C, G)) else None
+                _pb("bn_bwd", 0.0, 4.0 * (g.numel() + 2.0 * N * H * W * C + (0 if m is None else g.numel())))
                 if local or (self.sync_bn is not None and self._p2p_fits(N, H, W, C, s.run_mode, G, 1)):
                     ws = torch.empty((lib.aesr_bn_fused1_workspace_floats(C, G),), device=dev, dtype=torch.float32)
                     args = (ptr(g), ptr(y), ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]), ptr(ws), ptr(self._bn_barrier(dev)),
@@ -862,6 +893,10 @@ class SequentialRunner:
                     else:
                         p = self.sync_p2p
                         check(lib.aesr_bn_fused1_bwd_p2p(*args, p.peers, p.world, p.rank, p.next_slot(), ptr(p.gen), stream()), "aesr_bn_fused1_bwd_p2p")
+                elif m is not None:
+                    check(lib.aesr_bn_pool_bwd(ptr(g), ptr(y), ptr(m), ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]), ptr(partial),
+                                               _hip.double_array(st["counts"][:G]), ptr(coef), ptr(dgamma), ptr(dbeta), ptr(dpre), N, H, W,
+                                               C, prev.act, prev.slope, G, nsa, stream()), "aesr_bn_pool_bwd")
                 elif self.sync_bn is None:
                     check(lib.aesr_bn_bwd(ptr(g), ptr(y), ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]), ptr(partial),
                                           _hip.double_array(st["counts"][:G]), ptr(coef), ptr(dgamma), ptr(dbeta), ptr(dpre), N, H, W,
