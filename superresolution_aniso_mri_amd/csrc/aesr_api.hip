@@ -608,7 +608,7 @@ int aesr_bn_stats(const float* y, float* partial, double* sums, int HW, int C, i
     BnGroups gr;
     AESR_CHECK_ARG(y && partial && sums && fill_groups(&gr, G, nstart_host), "aesr_bn_stats: bad arguments");
     if (int e = aesr_launch_bn_stats(y, partial, HW, C, gr, AESR_BN_NWG, (hipStream_t)stream)) return e;
-    return aesr_launch_bn_reduce(partial, sums, AESR_BN_NWG, C, G, (hipStream_t)stream);
+    return aesr_launch_bn_reduce_pivot(partial, sums, AESR_BN_NWG, C, y, HW, gr, (hipStream_t)stream);
 }
 
 int aesr_bn_finalize(const double* sums, const double* counts_host, const float* gamma, const float* beta, float* running_mean,
@@ -630,8 +630,8 @@ int aesr_bn_stats_finalize(const float* y, float* partial, const double* counts_
     AESR_CHECK_ARG(y && partial && counts_host && fill_groups(&gr, G, nstart_host), "aesr_bn_stats_finalize: bad arguments");
     AESR_CHECK_ARG(gamma && beta && mean && invstd && scale && shift, "aesr_bn_stats_finalize: null pointer");
     if (int e = aesr_launch_bn_stats(y, partial, HW, C, gr, AESR_BN_NWG, (hipStream_t)stream)) return e;
-    return aesr_launch_bn_reduce_finalize(partial, AESR_BN_NWG, counts_host, gamma, beta, running_mean, running_var,
-                                          (long long*)num_batches_tracked, mean, invstd, scale, shift, C, G, momentum, eps,
+    return aesr_launch_bn_reduce_finalize(partial, AESR_BN_NWG, y, HW, gr, counts_host, gamma, beta, running_mean, running_var,
+                                          (long long*)num_batches_tracked, mean, invstd, scale, shift, C, momentum, eps,
                                           update_running && running_mean && running_var, (hipStream_t)stream);
 }
 
@@ -863,8 +863,8 @@ int aesr_bn_pool_stats_finalize(const float* y, float* m, float* partial, const 
                    "aesr_bn_pool_stats_finalize: N=%d H=%d W=%d C=%d G=%d or the group table is not supported (aesr_bn_pool_supported)", N, H, W, C, G);
     a.y = y; a.m = m; a.partial = partial; a.H = H; a.W = W; a.C = C; a.Ho = H / 2; a.Wo = W / 2;
     if (int e = aesr_launch_bn_pool_stats(a, AESR_BN_NWG, (hipStream_t)stream)) return e;
-    return aesr_launch_bn_reduce_finalize(partial, AESR_BN_NWG, counts_host, gamma, beta, running_mean, running_var,
-                                          (long long*)num_batches_tracked, mean, invstd, scale, shift, C, G, momentum, eps,
+    return aesr_launch_bn_reduce_finalize(partial, AESR_BN_NWG, y, H * W, a.gr, counts_host, gamma, beta, running_mean, running_var,
+                                          (long long*)num_batches_tracked, mean, invstd, scale, shift, C, momentum, eps,
                                           update_running && running_mean && running_var, (hipStream_t)stream);
 }
 

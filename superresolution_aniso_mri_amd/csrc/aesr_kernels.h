@@ -208,12 +208,13 @@ bool aesr_bn_fused1_ok(int N, int H, int W, int C, int pool, int G, int backward
 unsigned aesr_bn_fused_timeouts_impl();
 int aesr_launch_bn_stats(const float* y, float* partial, int HW, int C, const BnGroups& gr, int nwg, hipStream_t st);
 int aesr_launch_bn_reduce(const float* partial, double* sums, int nwg, int C, int G, hipStream_t st);
+int aesr_launch_bn_reduce_pivot(const float* partial, double* sums, int nwg, int C, const float* y, int HW, const BnGroups& gr, hipStream_t st);
 int aesr_launch_bn_finalize(const double* sums, const double* counts, const float* gamma, const float* beta, float* rm, float* rv,
                             long long* nbt, float* mean, float* invstd, float* scale, float* shift, int C, int G, float momentum,
                             float eps, int train, int update_running, hipStream_t st);
-int aesr_launch_bn_reduce_finalize(const float* partial, int nwg, const double* counts, const float* gamma, const float* beta,
-                                   float* running_mean, float* running_var, long long* nbt, float* mean, float* invstd,
-                                   float* scale, float* shift, int C, int G, float momentum, float eps, int update_running,
+int aesr_launch_bn_reduce_finalize(const float* partial, int nwg, const float* y, int HW, const BnGroups& gr, const double* counts,
+                                   const float* gamma, const float* beta, float* running_mean, float* running_var, long long* nbt, float* mean,
+                                   float* invstd, float* scale, float* shift, int C, float momentum, float eps, int update_running,
                                    hipStream_t st);
 int aesr_launch_bn_bwd_reduce_finalize(const float* partial, int nwg, const double* counts, float* coef, float* dgamma,
                                        float* dbeta, int C, int G, hipStream_t st);

@@ -4,12 +4,18 @@
 // exactly as if the reference had called the network once per sub-batch (running statistics are
 // updated group after group, in order).
 //
-//   stats    : per-channel sum / sum of squares partials  -> bn_reduce -> double [G][2][C]
+//   stats    : per-channel sum / sum of squares partials (about a pivot, below) -> bn_reduce_pivot -> double [G][2][C] about 0
 //              (under data parallel these sums are all-reduced across ranks = SyncBN)
 //   finalize : mean, biased var -> invstd, scale = gamma*invstd, shift = beta - mean*scale; running stats
 //              with momentum (unbiased var), num_batches_tracked (nn.BatchNorm2d semantics)
 //   apply    : out = scale*pool_or_up(y) + shift          (affine commutes with the 2x2 mean)
 //   backward : reduce sum(g), sum(g*xhat) -> apply dy = scale*(g - s1/M - xhat*s2/M) * act'(y)
+//
+// How the sums are taken: about a per-channel pivot K[g][c], the mean of eight pixels of the group in this call's y -- threads accumulate d = v - K,
+// sum d and sum d * d in fp32, a workgroup's lanes meet in fp64, the partials are fp32, and the launch that turns them into fp64 totals
+// (bn_reduce_pivot_kernel, bn_reduce_finalize_kernel) converts them to sums about 0 there (bn_math.h: bn_unpivot).  Sums about 0 in fp32 lose
+// (mean / sigma)^2 roundings in var = E[x^2] - mean^2: a bias-dominated channel (10 +- 0.01) would get a random invstd, a constant one a
+// variance.  sums[g][2][C], what SyncBN all-reduces, and everything behind it are as before; tests/test_gpu_bn_conditioning.py.
 //
 // Replaces nn.BatchNorm2d + nn.AvgPool2d / nn.Upsample of networks/acai_vanilla.py:58-59,90-92.
 // The arithmetic from the sums on is in bn_math.h (shared with bn_fused.hip); this file adds the reductions and the streaming loops.
@@ -18,7 +24,7 @@
 enum { BN_MODE_NONE = 0, BN_MODE_POOL = 1, BN_MODE_UP = 2 };
 
 // ---- forward statistics ---------------------------------------------------------------------------------
-// partial[g][wg][2][C]; grid = (nwg, G)
+// partial[g][wg][2][C], about the group's pivot; grid = (nwg, G)
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ y, float* __restrict__ partial, int HW,
                                                        int C, BnGroups gr) {
     extern __shared__ __attribute__((aligned(16))) float red[];   // [PL][2][C]
@@ -27,20 +33,22 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
     const int g = blockIdx.y;
     const size_t p0 = (size_t)gr.nstart[g] * HW, p1 = (size_t)gr.nstart[g + 1] * HW;
     f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 K = bn_pivot_block(y, p0, p1, C, red);          // sums about the group's pivot (bn_math.h)
     if (pl < PL) {
         for (size_t p = p0 + (size_t)blockIdx.x * PL + pl; p < p1; p += (size_t)gridDim.x * PL) {
-            const f32x4 v = *(const f32x4*)(y + p * C + c4 * 4);
-            s += v;
-            q += v * v;
+            const f32x4 d = *(const f32x4*)(y + p * C + c4 * 4) - K;
+            s += d;
+            q += d * d;
         }
         *(f32x4*)(red + (pl * 2 + 0) * C + c4 * 4) = s;
         *(f32x4*)(red + (pl * 2 + 1) * C + c4 * 4) = q;
     }
     __syncthreads();
+    // the lanes meet in fp64 (up to 128 of them: an fp32 chain would cost sqrt(PL) roundings of the variance), one rounding into the partial
     for (int o = threadIdx.x; o < 2 * C; o += 256) {
-        float t = 0.f;
-        for (int k = 0; k < PL; ++k) t += red[k * 2 * C + o];
-        partial[((size_t)g * gridDim.x + blockIdx.x) * 2 * C + o] = t;
+        double t = 0.0;
+        for (int k = 0; k < PL; ++k) t += (double)red[k * 2 * C + o];
+        partial[((size_t)g * gridDim.x + blockIdx.x) * 2 * C + o] = (float)t;
     }
 }
 
@@ -79,6 +87,55 @@ __global__ __launch_bounds__(1024) void bn_reduce_kernel(const float* __restrict
 #pragma unroll
         for (int k = 0; k < 16; ++k) t += red[k][col];
         sums[o] = t;
+    }
+}
+
+// The same for the forward statistics, whose partials are sums about the groups' pivots in y: a thread owns both columns of a (group,
+// channel) and stores the sums about 0 (bn_math.h: bn_unpivot) -- what the all-reduce of SyncBN adds across ranks.  block = 64 x 16 as above.
+__global__ __launch_bounds__(1024) void bn_reduce_pivot_kernel(const float* __restrict__ partial, double* __restrict__ sums, int nwg, int C,
+                                                               const float* __restrict__ y, int HW, BnGroups gr) {
+    __shared__ double red[2][16][64];
+    const int col = threadIdx.x & 63, rl = threadIdx.x >> 6;
+    const int o = blockIdx.x * 64 + col;
+    const int n = gr.G * C;
+    const int g = o < n ? o / C : 0, c = o - g * C;
+    double s = 0.0, q = 0.0;
+    if (o < n) {
+        const float* base = partial + (size_t)g * nwg * 2 * C + c;
+        const size_t rs = (size_t)2 * C;
+        double s0 = 0.0, s1 = 0.0, q0 = 0.0, q1 = 0.0;
+        int k = rl;
+        for (; k + 3 * 16 < nwg; k += 4 * 16) {             // 8 independent loads in flight per thread
+            float v[4], w[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                v[u] = base[(size_t)(k + u * 16) * rs];
+                w[u] = base[(size_t)(k + u * 16) * rs + C];
+            }
+            s0 += (double)v[0] + (double)v[2];
+            s1 += (double)v[1] + (double)v[3];
+            q0 += (double)w[0] + (double)w[2];
+            q1 += (double)w[1] + (double)w[3];
+        }
+        for (; k < nwg; k += 16) {
+            s0 += (double)base[(size_t)k * rs];
+            q0 += (double)base[(size_t)k * rs + C];
+        }
+        s = s0 + s1;
+        q = q0 + q1;
+    }
+    red[0][rl][col] = s;
+    red[1][rl][col] = q;
+    __syncthreads();
+    if (rl == 0 && o < n) {
+        double ts = 0.0, tq = 0.0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            ts += red[0][k][col];
+            tq += red[1][k][col];
+        }
+        const size_t p0 = (size_t)gr.nstart[g] * HW, p1 = (size_t)gr.nstart[g + 1] * HW;
+        bn_unpivot(ts, tq, (double)(p1 - p0), bn_pivot1(y, p0, p1, C, c), &sums[(g * 2 + 0) * C + c], &sums[(g * 2 + 1) * C + c]);
     }
 }
 
@@ -157,7 +214,9 @@ __device__ __forceinline__ void bn_all_totals(const float* __restrict__ partial,
 }
 
 // Statistics partials -> finalize in ONE launch (no SyncBN exchange in between).  block = 16 channels x 64 row-lanes.
-__global__ __launch_bounds__(1024) void bn_reduce_finalize_kernel(const float* __restrict__ partial, int nwg, BnFinArgs f) {
+// The partials are sums about the groups' pivots in y (HW pixels per image, groups gr): back to sums about 0 in fp64 (bn_math.h: bn_unpivot).
+__global__ __launch_bounds__(1024) void bn_reduce_finalize_kernel(const float* __restrict__ partial, int nwg, const float* __restrict__ y,
+                                                                  int HW, BnGroups gr, BnFinArgs f) {
     __shared__ double red[BNR_RL][BNR_COLS];
     __shared__ double tot[8][BNR_COLS];
     const int col = threadIdx.x % BNR_COLS, rl = threadIdx.x / BNR_COLS;
@@ -166,7 +225,12 @@ __global__ __launch_bounds__(1024) void bn_reduce_finalize_kernel(const float* _
     if (c == 0 && rl == 0 && f.update_running && f.nbt) *f.nbt += f.G;
     bn_all_totals(partial, nwg, f.C, f.G, c, live, red, tot, col, rl);
     if (rl == 0 && live)
-        for (int g = 0; g < f.G; ++g) bn_finalize_one(f, c, g, tot[2 * g][col], tot[2 * g + 1][col]);      // group order: running stats
+        for (int g = 0; g < f.G; ++g) {                                                                     // group order: running stats
+            const size_t p0 = (size_t)gr.nstart[g] * HW, p1 = (size_t)gr.nstart[g + 1] * HW;
+            double s0, s1;
+            bn_unpivot(tot[2 * g][col], tot[2 * g + 1][col], (double)(p1 - p0), bn_pivot1(y, p0, p1, f.C, c), &s0, &s1);
+            bn_finalize_one(f, c, g, s0, s1);
+        }
 }
 
 // ---- forward apply (+pool / +upsample) ----------------------------------------------------------------
@@ -386,6 +450,8 @@ __global__ __launch_bounds__(256) void bn_stats_kernel_pool(BnPoolStatsArgs a) {
     const int g = blockIdx.y;
     const unsigned HoWo = a.Ho * a.Wo;                            // host checks N*H*W < 2^31
     f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
+    const size_t HW = (size_t)a.H * a.W;
+    const f32x4 K = bn_pivot_block(a.y, a.gr.nstart[g] * HW, a.gr.nstart[g + 1] * HW, C, red);      // sums about the group's pivot
     if (pl < PL) {
         const unsigned S = gridDim.x * PL;
         const size_t row = (size_t)a.W * C;
@@ -397,8 +463,9 @@ __global__ __launch_bounds__(256) void bn_stats_kernel_pool(BnPoolStatsArgs a) {
             const float* b = a.y + (((size_t)n * a.H + 2 * py) * a.W + 2 * px) * C + c4 * 4;
             const f32x4 v00 = *(const f32x4*)b, v01 = *(const f32x4*)(b + C);
             const f32x4 v10 = *(const f32x4*)(b + row), v11 = *(const f32x4*)(b + row + C);
-            s += (v00 + v01) + (v10 + v11);
-            q += (v00 * v00 + v01 * v01) + (v10 * v10 + v11 * v11);
+            const f32x4 d00 = v00 - K, d01 = v01 - K, d10 = v10 - K, d11 = v11 - K;
+            s += (d00 + d01) + (d10 + d11);
+            q += (d00 * d00 + d01 * d01) + (d10 * d10 + d11 * d11);
             *(f32x4*)(a.m + (size_t)w * C + c4 * 4) = bn_pool2x2(v00, v01, v10, v11);
         }
         // what the pooling leaves out still counts for the statistics: the last column (odd W: H pixels per image), then the rest of the
@@ -409,19 +476,19 @@ __global__ __launch_bounds__(256) void bn_stats_kernel_pool(BnPoolStatsArgs a) {
             for (unsigned t = a.gr.nstart[g] * T + blockIdx.x * PL + pl; t < t1; t += S) {
                 const unsigned n = t / T, r = t - n * T;
                 const unsigned yy = r < Tc ? r : a.H - 1, x = r < Tc ? a.W - 1 : r - Tc;
-                const f32x4 v = *(const f32x4*)(a.y + (((size_t)n * a.H + yy) * a.W + x) * C + c4 * 4);
-                s += v;
-                q += v * v;
+                const f32x4 d = *(const f32x4*)(a.y + (((size_t)n * a.H + yy) * a.W + x) * C + c4 * 4) - K;
+                s += d;
+                q += d * d;
             }
         }
         *(f32x4*)(red + (pl * 2 + 0) * C + c4 * 4) = s;
         *(f32x4*)(red + (pl * 2 + 1) * C + c4 * 4) = q;
     }
     __syncthreads();
-    for (int o = threadIdx.x; o < 2 * C; o += 256) {
-        float t = 0.f;
-        for (int k = 0; k < PL; ++k) t += red[k * 2 * C + o];
-        a.partial[((size_t)g * gridDim.x + blockIdx.x) * 2 * C + o] = t;
+    for (int o = threadIdx.x; o < 2 * C; o += 256) {          // in fp64, as bn_stats_kernel
+        double t = 0.0;
+        for (int k = 0; k < PL; ++k) t += (double)red[k * 2 * C + o];
+        a.partial[((size_t)g * gridDim.x + blockIdx.x) * 2 * C + o] = (float)t;
     }
 }
 
@@ -551,6 +618,13 @@ int aesr_launch_bn_reduce(const float* partial, double* sums, int nwg, int C, in
     return AESR_OK;
 }
 
+// the partials of aesr_launch_bn_stats over the same y / HW / groups -> sums about 0
+int aesr_launch_bn_reduce_pivot(const float* partial, double* sums, int nwg, int C, const float* y, int HW, const BnGroups& gr, hipStream_t st) {
+    hipLaunchKernelGGL(bn_reduce_pivot_kernel, dim3(ceil_div(gr.G * C, 64)), dim3(1024), 0, st, partial, sums, nwg, C, y, HW, gr);
+    AESR_LAUNCH_CHECK("bn_reduce_pivot");
+    return AESR_OK;
+}
+
 static BnFinArgs bn_fin_args(const double* counts, const float* gamma, const float* beta, float* running_mean, float* running_var,
                              long long* nbt, float* mean, float* invstd, float* scale, float* shift, int C, int G, float momentum,
                              float eps, int train, int update_running) {
@@ -573,13 +647,14 @@ int aesr_launch_bn_finalize(const double* sums, const double* counts, const floa
     return AESR_OK;
 }
 
-int aesr_launch_bn_reduce_finalize(const float* partial, int nwg, const double* counts, const float* gamma, const float* beta,
+// y / HW / gr: what the statistics launch that wrote the partials was given (the pivots are read back from y)
+int aesr_launch_bn_reduce_finalize(const float* partial, int nwg, const float* y, int HW, const BnGroups& gr, const double* counts,
+                                   const float* gamma, const float* beta,
                                    float* running_mean, float* running_var, long long* nbt, float* mean, float* invstd,
-                                   float* scale, float* shift, int C, int G, float momentum, float eps, int update_running,
-                                   hipStream_t st) {
-    const BnFinArgs f = bn_fin_args(counts, gamma, beta, running_mean, running_var, nbt, mean, invstd, scale, shift, C, G, momentum,
+                                   float* scale, float* shift, int C, float momentum, float eps, int update_running, hipStream_t st) {
+    const BnFinArgs f = bn_fin_args(counts, gamma, beta, running_mean, running_var, nbt, mean, invstd, scale, shift, C, gr.G, momentum,
                                     eps, 1, update_running);
-    hipLaunchKernelGGL(bn_reduce_finalize_kernel, dim3(ceil_div(C, BNR_COLS)), dim3(BNR_COLS * BNR_RL), 0, st, partial, nwg, f);
+    hipLaunchKernelGGL(bn_reduce_finalize_kernel, dim3(ceil_div(C, BNR_COLS)), dim3(BNR_COLS * BNR_RL), 0, st, partial, nwg, y, HW, gr, f);
     AESR_LAUNCH_CHECK("bn_reduce_finalize");
     return AESR_OK;
 }

@@ -8,7 +8,8 @@
 //   phase 1  workgroup b (of 256, one per CU, 512 threads) loads its units (a unit = RU rows of one image: 2 rows where the pooling
 //            follows, so that every 2x2 window is local) into LDS, accumulating per-channel sum / sum of squares per statistic group
 //            on the way (backward: sum g, sum g * xhat, with the gathered gradient in LDS too), and writes ONE record [G][2][C] of
-//            partial sums;
+//            partial sums -- forward: about the group's pivot, the mean of eight of its pixels (bn_math.h: how the sums are taken), turned into sums
+//            about 0 in fp64 behind bf_totals, before the ranks exchange them;
 //   barrier  grid-wide (below);
 //   phase 2  EVERY workgroup adds the 256 records in a fixed order (fp64) and finalizes scale / shift (backward: the two coefficients)
 //            into LDS -- 128 KB of L2 reads per workgroup instead of a third launch; workgroup 0 also writes mean / invstd / scale /
@@ -214,8 +215,10 @@ __global__ __launch_bounds__(BF_NT, 2) void bn_fused_fwd_kernel(BnFusedArgs a) {
     const int GC2 = a.G * 2 * C;
     for (int o = tid; o < GC2; o += BF_NT) tot[o] = 0.f;
     // ---- phase 1: units -> LDS, statistics ----
+    // (sums about the group's pivot K, the mean of eight of its pixels: bn_math.h.  A thread's elements tid + j * BF_NT all belong to channel quad tid % C4.)
     int cur_g = -1;
-    f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
+    const size_t HW = (size_t)a.H * a.W;
+    f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f}, K = s;
     for (int u = u0; u < u1; ++u) {
         const int n = u / a.upi, r0 = (u - n * a.upi) * a.RU;
         const int nr = min(a.RU, a.H - r0);
@@ -224,6 +227,7 @@ __global__ __launch_bounds__(BF_NT, 2) void bn_fused_fwd_kernel(BnFusedArgs a) {
             if (cur_g >= 0) bf_flush(red, tot, cur_g, C, s, q);
             cur_g = g;
             s = q = (f32x4){0.f, 0.f, 0.f, 0.f};
+            K = bn_pivot_block(a.y, a.nstart[g] * HW, a.nstart[g + 1] * HW, C, red);
         }
         const f32x4* src = (const f32x4*)(a.y + ((size_t)n * a.H + r0) * a.W * C);
         f32x4* dst = (f32x4*)(data + (size_t)(u - u0) * a.unit_fl);
@@ -237,8 +241,9 @@ __global__ __launch_bounds__(BF_NT, 2) void bn_fused_fwd_kernel(BnFusedArgs a) {
             for (int k = 0; k < 8; ++k)
                 if (e0 + k * BF_NT < cnt4) {
                     dst[e0 + k * BF_NT] = v[k];
-                    s += v[k];
-                    q += v[k] * v[k];
+                    const f32x4 d = v[k] - K;
+                    s += d;
+                    q += d * d;
                 }
         }
     }
@@ -248,6 +253,15 @@ __global__ __launch_bounds__(BF_NT, 2) void bn_fused_fwd_kernel(BnFusedArgs a) {
     bf_grid_barrier(a.bar, BF_NB);
     // ---- phase 2: totals of all workgroups, finalize ----
     bf_totals(a.rec, GC2, red, totd, BF_NB);
+    // the totals about the pivots -> about 0, in fp64, over THIS launch's pixels: what the ranks exchange stays addable
+    for (int i = tid; i < a.G * C; i += BF_NT) {
+        const int g = i / C, c = i - g * C;
+        const size_t p0 = a.nstart[g] * HW, p1 = a.nstart[g + 1] * HW;
+        double* t0 = totd + (g * 2 + 0) * C + c;
+        double* t1 = totd + (g * 2 + 1) * C + c;
+        bn_unpivot(*t0, *t1, (double)(p1 - p0), bn_pivot1(a.y, p0, p1, C, c), t0, t1);
+    }
+    __syncthreads();
     if (a.world > 0) bf_exchange(a, GC2, totd);
     bn_fwd_tables<BF_NT>(totd, a, b == 0, s_sc, s_sh);
     __syncthreads();

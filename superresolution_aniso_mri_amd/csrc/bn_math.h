@@ -18,6 +18,64 @@ __device__ __forceinline__ int bn_group_of(int G, const int* nstart, int n) {
     return g;
 }
 
+// ---- forward: how the sums are taken -------------------------------------------------------------------------------------------------
+// The variance is s1 / M - mean^2, and fp32 squares and fp32 running sums carry an error of 2^-24 * E[x^2], which that subtraction magnifies by
+// (mean / sigma)^2: a channel at 12.8 +- 0.1 lost four digits of its invstd, a constant channel came out with a variance.  So every statistics
+// pass (bn_stats_kernel, bn_stats_kernel_pool, phase 1 of bn_fused_fwd_kernel) accumulates d = v - K, sum d and sum d * d in fp32, about a
+// per-channel pivot K[g][c] = the mean of eight pixels of the group in this call's y (bn_pivot4), so |mean - K| is a fraction of sigma and the
+// fp32 sums are as accurate as for centred data (bn.hip adds a workgroup's up to 128 lanes in fp64 before it rounds the partial:
+// with the pivot k sigma off the mean every rounding of sum d * d counts (1 + k^2) times in the variance).  Where the fp32 partials have become fp64 totals (bn_reduce_pivot_kernel,
+// bn_reduce_finalize_kernel, bn_fused_fwd_kernel behind bf_totals) bn_unpivot turns them into the sums about 0 in fp64: everything from
+// sums[g][2][C] on -- bn_moments, the all-reduce and the peer exchange of SyncBN, whose ranks each have a pivot of their own -- is unchanged.
+// (fp64 leaves (mean / sigma)^2 * 2^-53: 5e-10 at a ratio of 2000.)  tests/test_gpu_bn_conditioning.py holds every form to it.
+__device__ __forceinline__ void bn_unpivot(double sd, double qd, double M, double K, double* s0, double* s1) {
+    *s0 = sd + M * K;
+    *s1 = qd + 2.0 * K * sd + M * K * K;
+}
+
+// The pivot of the group with pixels [p0, p1), channels c..c+3 / channel c: the mean of BN_PIVOT_N of its pixels, one from each such part of the group and off the
+// image border for the usual widths (any value near the channel's mean serves; both forms below are the same fp32 operations, so the
+// statistics pass and the conversion use the same bits).  One pixel alone sits 1 sigma out on average and 3 sigma out for some channel of a
+// layer, which costs well-centred channels (1 + 3^2) roundings where the sums about 0 cost them 2; eight pixels bring that distance to a third.
+// An empty group has no pivot and needs none.
+#define BN_PIVOT_N 8          // pixels in the pivot (a power of two: the mean is a sum and an exact scaling)
+__device__ __forceinline__ size_t bn_pivot_pixel(size_t p0, size_t p1, int j) {
+    const size_t M = p1 - p0, i = ((size_t)(2 * j + 1) * M) / (2 * BN_PIVOT_N) + (size_t)(17 + 37 * j);
+    return p0 + (i < M ? i : M - 1);
+}
+__device__ __forceinline__ f32x4 bn_pivot4(const float* y, size_t p0, size_t p1, int C, int c) {
+    if (p0 >= p1) return (f32x4){0.f, 0.f, 0.f, 0.f};
+    f32x4 v[BN_PIVOT_N];
+#pragma unroll
+    for (int j = 0; j < BN_PIVOT_N; ++j) v[j] = *(const f32x4*)(y + bn_pivot_pixel(p0, p1, j) * C + c);
+    f32x4 t = v[0];
+#pragma unroll
+    for (int j = 1; j < BN_PIVOT_N; ++j) t += v[j];
+    return t * (1.f / BN_PIVOT_N);
+}
+__device__ __forceinline__ double bn_pivot1(const float* y, size_t p0, size_t p1, int C, int c) {
+    if (p0 >= p1) return 0.0;
+    float v[BN_PIVOT_N];
+#pragma unroll
+    for (int j = 0; j < BN_PIVOT_N; ++j) v[j] = y[bn_pivot_pixel(p0, p1, j) * C + c];
+    float t = v[0];
+#pragma unroll
+    for (int j = 1; j < BN_PIVOT_N; ++j) t += v[j];
+    return (double)(t * (1.f / BN_PIVOT_N));
+}
+
+// The pivot of a whole block through LDS: the C / 4 threads of the first pixel lane load it, everybody reads it (each thread loading for
+// itself asks every block's 256-512 threads for the same few cache lines: +1 us per launch).  Every thread of the block calls it; scratch holds C
+// floats and is free again on return.
+__device__ __forceinline__ f32x4 bn_pivot_block(const float* y, size_t p0, size_t p1, int C, float* scratch) {
+    const int C4 = C >> 2, c4 = threadIdx.x % C4;
+    if ((int)threadIdx.x < C4) *(f32x4*)(scratch + c4 * 4) = bn_pivot4(y, p0, p1, C, c4 * 4);
+    __syncthreads();
+    const f32x4 K = *(const f32x4*)(scratch + c4 * 4);
+    __syncthreads();
+    return K;
+}
+
 // ---- forward: sums -> mean / invstd / scale / shift / running statistics -----------------------------------------------------------
 // moments of M values from their sum s0 and sum of squares s1, in fp64: mean, 1 / sqrt(biased variance + eps); returns the biased variance
 __device__ __forceinline__ double bn_moments(double s0, double s1, double M, float eps, float* mean, float* invstd) {
