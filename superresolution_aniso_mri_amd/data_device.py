@@ -525,3 +525,264 @@ class BrainTripletAugmenter:
             rank, world = int(shard[0]), int(shard[1])
             lo, hi = (B * rank) // world, (B * (rank + 1)) // world
         return self.assemble(trips[lo:hi], alphas[lo:hi], transforms[lo:hi], reuse_output=reuse_output, raw=raw, size=size)
+
+
+# ---- labelled cardiac volumes (datasets/ACDC/data_with_labels.py of the reference) ---------------------------------------------------
+_VOLUME_EXTENSIONS = (".nii.gz", ".npy", ".nii", ".mha", ".mhd")
+
+
+def _volume_files(path):
+    """{stem: file name} of the volume files of a directory (the stem is the name without its extension, case kept)."""
+    import os
+    out = {}
+    for name in sorted(os.listdir(path)):
+        ext = next((e for e in _VOLUME_EXTENSIONS if name.lower().endswith(e)), None)
+        if ext is None:
+            continue
+        stem = name[:-len(ext)]
+        if stem in out:
+            raise ValueError("%s: %s and %s share the stem %r, so a label file cannot be paired by name" % (path, out[stem], name, stem))
+        out[stem] = name
+    return out
+
+
+def _read_volume_file(f):
+    """(array, spacing (z, y, x) or None for a .npy file)"""
+    from . import volume_io
+    if f.lower().endswith(".npy"):
+        return np.load(f), None
+    v = volume_io.read_volume(f)
+    return v.array, tuple(v.spacing[:3][::-1])
+
+
+def _as_label_bytes(lab, what):
+    """A label array as uint8; ValueError (naming ``what``) unless every value is an integer in 0 ... 255."""
+    lab = np.asarray(lab)
+    if lab.dtype != np.uint8:
+        if lab.dtype == bool or not np.issubdtype(lab.dtype, np.number) or np.iscomplexobj(lab):
+            raise ValueError("%s: labels must be numbers, got dtype %s" % (what, lab.dtype))
+        if lab.size and not np.all(np.isfinite(lab)):
+            raise ValueError("%s: labels must be finite" % what)
+        if lab.size and not np.array_equal(lab, np.round(lab)):
+            raise ValueError("%s: labels must be integral (class ids), found %r" % (what, float(lab[lab != np.round(lab)].flat[0])))
+        if lab.size and (lab.min() < 0 or lab.max() > 255):
+            raise ValueError("%s: labels must lie within 0 ... 255 (they are cached as bytes), found %r ... %r" % (what, lab.min(), lab.max()))
+    return np.ascontiguousarray(lab, dtype=np.uint8)
+
+
+def load_labelled_volume_dir(images_dir, labels_dir, resample=False, new_spacing=None):
+    """(volumes, labels) for ``LabelledTripletAugmenter``: the image files of ``images_dir`` (as ``load_volume_dir`` reads and rescales them;
+    4-D files give one volume per frame) and, paired BY NAME, the label maps of ``labels_dir`` -- the same stem, any supported extension
+    (``vol0.nii.gz`` pairs with ``vol0.npy``).  An image without a label file, or a label file without an image, is a ``FileNotFoundError``.
+    Labels must be integral, within 0 ... 255 and of their image's shape (``ValueError`` naming the file); they come back as uint8.
+
+    ``resample``: images go through ``load_volume_dir``'s in-plane resampling (blur, linear) and labels through
+    ``apply_2d_zoom_3d(order=0, do_blur=False, as_type=int)`` -- nearest sample, never a mixture of class ids -- as the reference's
+    ``ACDCImage`` does; both from the IMAGE file's spacing, so the two keep one shape."""
+    import os
+    from .datasets.common import apply_2d_zoom_3d, apply_2d_zoom_4d
+    imgs, labs = _volume_files(images_dir), _volume_files(labels_dir)
+    if not imgs:
+        raise FileNotFoundError("no .npy / .nii / .mha / .mhd volumes in %s" % images_dir)
+    for stem in imgs:
+        if stem not in labs:
+            raise FileNotFoundError("%s has no label file %s.* in %s" % (os.path.join(images_dir, imgs[stem]), stem, labels_dir))
+    for stem in labs:
+        if stem not in imgs:
+            raise FileNotFoundError("%s has no image file %s.* in %s" % (os.path.join(labels_dir, labs[stem]), stem, images_dir))
+    volumes, labels = [], []
+    for stem in sorted(imgs):
+        f, lf = os.path.join(images_dir, imgs[stem]), os.path.join(labels_dir, labs[stem])
+        arr, spacing = _read_volume_file(f)
+        lab, _ = _read_volume_file(lf)
+        if arr.ndim not in (3, 4):
+            raise ValueError("%s: expected a 3-D or 4-D volume, got shape %s" % (f, arr.shape))
+        if tuple(lab.shape) != tuple(arr.shape):
+            raise ValueError("%s: the label map's shape %s is not its image's %s (%s)" % (lf, tuple(lab.shape), tuple(arr.shape), f))
+        lab = _as_label_bytes(lab, lf)
+        if resample:
+            arr = _resample_to(arr, spacing, new_spacing, f)
+            fn = apply_2d_zoom_3d if lab.ndim == 3 else apply_2d_zoom_4d
+            lab = _as_label_bytes(fn(lab.astype(np.float32), spacing, NEW_SPACING if new_spacing is None else new_spacing, order=0,
+                                     do_blur=False, as_type=int), lf)
+            assert tuple(lab.shape) == tuple(arr.shape)
+        for v, l in zip([arr] if arr.ndim == 3 else list(arr), [lab] if lab.ndim == 3 else list(lab)):
+            v = np.asarray(v, dtype=np.float32)
+            volumes.append(v if (v.min() >= 0 and v.max() <= 1) else rescale_intensities(v))
+            labels.append(np.ascontiguousarray(l))
+    return volumes, labels
+
+
+class LabelledTripletAugmenter(TripletAugmenter):
+    """``TripletAugmenter`` for volumes that come with a label map: the batches of the reference's ``ACDCDatasetEDESPairs`` under the
+    transforms of train_cardiac_aesr.py:83-105 and the 6-channel branch of ``prepare_batch_pairs``, from two flat device caches (float32
+    images, uint8 labels; one offset addresses both) in one launch per batch (``aesr_labelled_triplet_assemble``,
+    include/aesr_hip_labelprep.h).  ``image`` is [2B, 2, W, W] and ``slice_between`` [B, 2, W, W]: channel 0 the intensities, channel 1 the
+    class ids as floats -- cropped and rotated together, the intensity curve on channel 0 only, padding 0 (background) in the labels.
+
+    ``volumes`` / ``labels``: lists of [Z, H, W] arrays of equal shapes, intensities in [0, 1], labels integral in 0 ... 255
+    (``load_labelled_volume_dir`` returns such a pair).  Differences from the cardiac class, all the reference's:
+      - ``draw_sample`` follows ``ACDCDatasetEDESPairs.__getitem__``: the slice step by ``slice_selection`` ('adjacent' 1, 'adjacent_plus' 2,
+        'mix' one draw), the neighbour, the slice in between -- ``(a + b) // 2`` when ``a + b`` is even, else the slice itself with
+        ``is_inbetween = 0`` --, the from / to order, then the transform's numbers;
+      - the transform's numbers come from ``rs_transform``, by default the SAME object as ``rs``: the training script hands one global
+        RandomState to the dataset and to the transforms.  The draws themselves are ``TripletAugmenter.draw_transform``'s;
+      - ``raw=True``: the script's test transform (``test_transform``), no draw, no intensity curve, no rotation.
+    Not the reference's: a batch is B draws of (volume, slice) by ``rs.randint`` (the reference's loader shuffles with torch's generator);
+    ``RandomAnyRotation`` (the dataset's own default transform, which the training script never uses) is not built."""
+
+    def __init__(self, volumes, labels, width, aug_patch_size, slice_selection="adjacent_plus", rs=None, rs_transform=None, device="cuda"):
+        if slice_selection not in ("adjacent", "adjacent_plus", "mix"):
+            raise ValueError("slice_selection=%r: one of 'adjacent', 'adjacent_plus', 'mix'" % (slice_selection,))
+        volumes, labels = list(volumes), list(labels)
+        if len(volumes) != len(labels) or not volumes:
+            raise ValueError("%d volumes but %d label maps" % (len(volumes), len(labels)))
+        flat = []
+        for i, (v, l) in enumerate(zip(volumes, labels)):
+            if np.ndim(v) != 3 or tuple(np.shape(l)) != tuple(np.shape(v)):
+                raise ValueError("volume %d: the image is %s and its label map %s; both must be one [Z,H,W]" % (i, np.shape(v), np.shape(l)))
+            flat.append(_as_label_bytes(l, "label map %d" % i).reshape(-1))
+            step = 1 if slice_selection == "adjacent" else 2
+            if np.shape(v)[0] < 2 * step:
+                raise ValueError("volume %d has %d slices: neighbours %d slices apart need at least %d (below that the reference's neighbour "
+                                 "rule leaves the volume)" % (i, np.shape(v)[0], step, 2 * step))
+        super().__init__(volumes, width, aug_patch_size, rs=rs, device=device)
+        self.slice_selection = slice_selection
+        self.rs_transform = rs_transform if rs_transform is not None else self.rs
+        self.label_cache = torch.from_numpy(np.concatenate(flat)).to(device)        # uint8, the layout of self.cache
+        assert self.label_cache.numel() == self.cache.numel()
+
+    # ---- host side ------------------------------------------------------------------------------------------------------------------
+    def draw_transform(self, vol_id):
+        """``TripletAugmenter.draw_transform`` -- [top, left] (only when a crop happens), gain, cutoff, k -- drawn from ``rs_transform``."""
+        rs, self.rs = self.rs, self.rs_transform          # the parent draws from self.rs: lend it the transforms' state for this call
+        try:
+            return super().draw_transform(vol_id)
+        finally:
+            self.rs = rs
+
+    def test_size(self, size=None):
+        """Width of a ``raw`` batch: ``CenterCrop`` keeps ``2 * int(canvas / 2)``; the canvas is ``aug_patch_size`` for ``width <= 128``,
+        else ``width`` (train_cardiac_aesr.py:99-104), or ``size``."""
+        canvas = int(size) if size is not None else (self.aug if self.width <= 128 else self.width)
+        return 2 * int(canvas / 2)
+
+    def test_transform(self, vol_id, size=None):
+        """The script's ``transform_te``, no draw: for ``width <= 128`` a centre crop of ``aug_patch_size``, otherwise zero padding up to
+        ``width`` and a centre crop of ``width``; ``size``: that canvas instead.  The reference's first branch does not pad, so a slice
+        smaller than the crop leaves it with slices of unequal size (or, between the two sizes, wrapped indices); here it is padded with
+        zeros as in the second branch -- for slices at least as large as the crop the two agree."""
+        _, H, W = self.shapes[vol_id]
+        aug = self.aug
+        self.aug = int(size) if size is not None else (self.aug if self.width <= 128 else self.width)
+        try:
+            oy, ox, _, _ = self._geometry(H, W)
+        finally:
+            self.aug = aug
+        return oy, ox, 0.0, 0.0, 0
+
+    def draw_sample(self, vol_id, slice_id, raw=False):
+        """``ACDCDatasetEDESPairs.__getitem__`` (datasets/ACDC/data_with_labels.py:141-155, 197-214) for one (volume, slice):
+        -> ((vol_id, z_from, z_to, z_between), is_inbetween, (oy, ox, gain, cutoff, k))."""
+        Z = self.shapes[vol_id][0]
+        slice_id = int(slice_id)
+        if not 0 <= slice_id < Z:
+            raise ValueError("slice index outside volume %d (Z=%d)" % (vol_id, Z))
+        if self.slice_selection == "adjacent":
+            step = 1
+        elif self.slice_selection == "adjacent_plus":
+            step = 2
+        else:
+            step = (1, 2)[int(self.rs.randint(0, 2))]          # == rs.choice([1, 2]), see get_random_adjacent_slice
+        other = int(get_random_adjacent_slice(slice_id, Z, self.rs, step))
+        if (slice_id + other) % 2 == 0:
+            between, is_inbetween = (slice_id + other) // 2, 1
+        else:
+            between, is_inbetween = slice_id, 0
+        if int(self.rs.randint(0, 2)) == 0:            # == rs.choice([0, 1])
+            z_from, z_to = slice_id, other
+        else:
+            z_from, z_to = other, slice_id
+        transform = self.test_transform(vol_id) if raw else self.draw_transform(vol_id)
+        return (vol_id, z_from, z_to, between), is_inbetween, transform
+
+    # ---- device side ----------------------------------------------------------------------------------------------------------------
+    def assemble(self, samples, transforms=None, reuse_output=False, raw=False, size=None):
+        """samples: list of (vol_id, z_from, z_to, z_between); transforms: list of (oy, ox, gain, cutoff, k) or None (drawn now, one sample
+        after the other; ``raw``: the test transform, nothing drawn).  Returns {'image': [2B,2,W,W], 'slice_between': [B,2,W,W],
+        'alpha_from', 'alpha_to': [B,1] of 0.5, 'is_inbetween': [2B,1] (0 where the slice between is one of the pair, as the reference marks
+        it), 'loss_mask': [2B,1] of ones}.  ``reuse_output``: image and slice_between are views of ONE persistent [3B,2,W,W] buffer of this
+        augmenter, written again by every batch of that size.  ``size`` (with ``raw`` only): the test transform's canvas."""
+        B, Wd = len(samples), self.width
+        if size is not None and not raw:
+            raise ValueError("size= goes with raw=True (the test transform)")
+        if raw:
+            Wd = self.test_size(size)
+        if transforms is None:
+            transforms = [self.test_transform(s[0], size) if raw else self.draw_transform(s[0]) for s in samples]
+        if len(transforms) != B:
+            raise ValueError("%d samples but %d transforms" % (B, len(transforms)))
+        for vid, zf, zt, zb in samples:
+            Z = self.shapes[vid][0]
+            if not (0 <= zf < Z and 0 <= zt < Z and 0 <= zb < Z):
+                raise ValueError("slice index outside volume %d (Z=%d)" % (vid, Z))
+        inb = torch.tensor([[0.0 if s[3] in (s[1], s[2]) else 1.0] for s in samples] * 2, dtype=torch.float32).reshape(2 * B, 1)
+        if reuse_output:
+            key = (B, Wd)
+            if key not in self._out:
+                both = torch.empty((3 * B, 2, Wd, Wd), device=self.device, dtype=torch.float32)
+                half = torch.full((B, 1), 0.5, device=self.device, dtype=torch.float32)
+                self._out[key] = (both, half, half.clone(), torch.empty((2 * B, 1), device=self.device, dtype=torch.float32),
+                                  torch.ones((2 * B, 1), device=self.device, dtype=torch.float32))
+            both, a_from, a_to, inb_dev, ones = self._out[key]
+            inb_dev.copy_(inb)
+            image, between = both[:2 * B], both[2 * B:]
+        else:
+            image = torch.empty((2 * B, 2, Wd, Wd), device=self.device, dtype=torch.float32)
+            between = torch.empty((B, 2, Wd, Wd), device=self.device, dtype=torch.float32)
+            a_from = torch.full((B, 1), 0.5, device=self.device, dtype=torch.float32)
+            a_to, inb_dev = a_from.clone(), inb.to(self.device)
+            ones = torch.ones((2 * B, 1), device=self.device, dtype=torch.float32)
+        launch = lib.aesr_labelled_triplet_assemble_raw if raw else lib.aesr_labelled_triplet_assemble
+        _hip.require_gpu_tensor(self.cache, "volume cache")
+        _hip.require_gpu_tensor(self.label_cache, "label cache", torch.uint8)
+        for b0 in range(0, B, 64):
+            n = min(64, B - b0)
+            descs = (_hip.TripletDesc * n)()
+            for i in range(n):
+                vid, zf, zt, zb = samples[b0 + i]
+                oy, ox, gain, cutoff, k = transforms[b0 + i]
+                _, H, W = self.shapes[vid]
+                descs[i] = _hip.TripletDesc(self.offsets[vid], H, W, zf, zt, zb, oy, ox, k, gain, cutoff)
+            if B <= 64:
+                img_dst, btw_dst = image, between
+            else:       # more than one launch: each launch owns a contiguous [from | to] pair block -> assemble then scatter
+                img_dst = torch.empty((2 * n, 2, Wd, Wd), device=self.device, dtype=torch.float32)
+                btw_dst = between[b0:b0 + n]
+            check(launch(ptr(self.cache), ptr(self.label_cache), descs, n, Wd, ptr(img_dst), ptr(btw_dst), stream()),
+                  "aesr_labelled_triplet_assemble_raw" if raw else "aesr_labelled_triplet_assemble")
+            if B > 64:
+                image[b0:b0 + n] = img_dst[:n]
+                image[B + b0:B + b0 + n] = img_dst[n:]
+        out = {"image": image, "slice_between": between, "alpha_from": a_from, "alpha_to": a_to, "is_inbetween": inb_dev, "loss_mask": ones}
+        if reuse_output:
+            out["_persistent"] = True
+        return out
+
+    def next_batch(self, B, reuse_output=False, shard=None, raw=False):
+        """A random batch: B random (volume, slice) pairs, each completed by ``draw_sample`` -- its slices, then its transform, sample after
+        sample, which is the order one shared RandomState serves the reference's dataset and transforms in.  ``reuse_output`` and ``shard`` =
+        (rank, world) as in ``TripletAugmenter.next_batch``: every rank draws the whole global batch and assembles its own samples
+        [B r / W, B (r + 1) / W)."""
+        samples, transforms = [], []
+        for _ in range(B):
+            vid = int(self.rs.randint(0, len(self.shapes)))
+            sid = int(self.rs.randint(0, self.shapes[vid][0]))
+            s, _, t = self.draw_sample(vid, sid, raw=raw)
+            samples.append(s)
+            transforms.append(t)
+        lo, hi = 0, B
+        if shard is not None:
+            rank, world = int(shard[0]), int(shard[1])
+            lo, hi = (B * rank) // world, (B * (rank + 1)) // world
+        return self.assemble(samples[lo:hi], transforms[lo:hi], reuse_output=reuse_output, raw=raw)

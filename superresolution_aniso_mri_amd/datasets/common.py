@@ -16,6 +16,10 @@ Every coordinate decision is made here, on the host, in float64 the way scipy ma
 - the Gaussian weights are scipy's (``radius = int(4 sigma + 0.5)``, ``exp(-0.5 / sigma^2 * x^2)`` normalised, in double), the boundary is
   ``reflect``; each 1-D pass is accumulated in double and stored as float32, as scipy does for float32 input.
 
+``order=0`` (how the reference resamples label maps: ``apply_2d_zoom_3d(labels, ..., order=0, do_blur=False, as_type=int)``) is host tables
+only: the same launch with the nearest-sample index ``min(floor(c + 0.5), n - 1)`` and weight 0, so a value is copied and never mixed; the
+dead lines are the same.  Equal to ``scipy.ndimage.zoom(order=0)`` on every case of tests/golden/inplane_labels.npz, exact .5 ties included.
+
 The device path takes float32: anything else is cast to float32 first (the reference would let scipy truncate every filter pass of an
 integer-typed array back to the integer type; that case is not reproduced).  There is no CPU fallback: a numpy
 array goes to the device and comes back."""
@@ -52,18 +56,24 @@ def gaussian_weights(sigma, truncate=4.0):
     return phi / phi.sum(), radius
 
 
-def zoom_tables(n, n_out, clamp_edges=False):
+def zoom_tables(n, n_out, clamp_edges=False, order=1):
     """(i0 [n_out] int32, t [n_out] float64): output index o is ``(1 - t[o]) * in[i0[o]] + t[o] * in[min(i0[o] + 1, n - 1)]``;
-    ``i0[o] == -1`` marks a dead line (exactly 0).  With ``clamp_edges`` a dead line reads ``in[n - 1]`` instead."""
+    ``i0[o] == -1`` marks a dead line (exactly 0).  With ``clamp_edges`` a dead line reads ``in[n - 1]`` instead.
+    ``order=0`` (nearest, for label maps): ``i0[o] = min(floor(c + 0.5), n - 1)`` and ``t = 0`` -- scipy.ndimage.zoom(order=0) rounds an
+    exact .5 up; the dead lines are the same."""
     n, n_out = int(n), int(n_out)
     if n < 1 or n_out < 1:
         raise ValueError("cannot resample %d samples to %d" % (n, n_out))
     step = np.float64(n - 1) / np.float64(n_out - 1) if n_out > 1 else np.float64(1.0)
     c = np.arange(n_out, dtype=np.float64) * step
     dead = c > np.float64(n - 1)
-    fl = np.floor(c)
-    i0 = fl.astype(np.int64)
-    t = c - fl
+    if order == 0:
+        i0 = np.minimum(np.floor(c + 0.5).astype(np.int64), n - 1)
+        t = np.zeros(n_out, np.float64)
+    else:
+        fl = np.floor(c)
+        i0 = fl.astype(np.int64)
+        t = c - fl
     i0[dead], t[dead] = (n - 1, 0.0) if clamp_edges else (-1, 0.0)
     return i0.astype(np.int32), t.astype(np.float64)
 
@@ -73,8 +83,9 @@ def dead_lines(n, n_out):
     return np.nonzero(zoom_tables(n, n_out)[0] < 0)[0]
 
 
-def inplane_resample(x, zoom, do_blur=True, clamp_edges=False):
-    """x: CUDA float32 [N, H, W], contiguous -> new CUDA tensor [N, Ho, Wo].  One launch; x is not modified."""
+def inplane_resample(x, zoom, do_blur=True, clamp_edges=False, order=1):
+    """x: CUDA float32 [N, H, W], contiguous -> new CUDA tensor [N, Ho, Wo].  One launch; x is not modified.  ``order=0``: the same launch
+    with the nearest-sample tables of ``zoom_tables`` (weight 0: a value is copied, never mixed)."""
     global LAUNCHES
     _hip.require_gpu_tensor(x, "x")
     if x.dim() != 3:
@@ -87,8 +98,8 @@ def inplane_resample(x, zoom, do_blur=True, clamp_edges=False):
     assert Ho == lib.aesr_inplane_out_size(H, zy) and Wo == lib.aesr_inplane_out_size(W, zx)
     wy, ry = gaussian_weights(0.25 / zy)
     wx, rx = gaussian_weights(0.25 / zx)
-    iy, ty = zoom_tables(H, Ho, clamp_edges)
-    ix, tx = zoom_tables(W, Wo, clamp_edges)
+    iy, ty = zoom_tables(H, Ho, clamp_edges, order)
+    ix, tx = zoom_tables(W, Wo, clamp_edges, order)
     out = torch.empty((N, Ho, Wo), device=x.device, dtype=torch.float32)
     ws = torch.empty(int(lib.aesr_inplane_workspace_bytes(Ho, Wo)) // 8, device=x.device, dtype=torch.float64)
     as_d = lambda a: np.ascontiguousarray(a, np.float64).ctypes.data_as(_hip.DP)        # noqa: E731
@@ -108,8 +119,9 @@ def _is_integer_type(as_type):
 
 
 def _apply(arr, spacing, new_spacing, order, do_blur, as_type, clamp_edges, ndim):
-    if order != 1:
-        raise NotImplementedError("order=%r: only the reference's default, order=1 (linear), is built" % (order,))
+    if order not in (0, 1):
+        raise NotImplementedError("order=%r: only order=1 (linear, the reference's default) and order=0 (nearest, its choice for label maps) "
+                                  "are built" % (order,))
     if arr.ndim != ndim:
         raise ValueError("expected a %d-D array, got shape %s" % (ndim, tuple(arr.shape)))
     zoom = zoom_factors(spacing, new_spacing)
@@ -124,7 +136,7 @@ def _apply(arr, spacing, new_spacing, order, do_blur, as_type, clamp_edges, ndim
         x = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)).cuda()
     lead = tuple(x.shape[:-2])
     x = x.to(torch.float32).contiguous().reshape((-1,) + tuple(x.shape[-2:]))       # no copy for a contiguous float32 tensor
-    out = inplane_resample(x, zoom, do_blur=do_blur, clamp_edges=clamp_edges)
+    out = inplane_resample(x, zoom, do_blur=do_blur, clamp_edges=clamp_edges, order=order)
     out = out.reshape(lead + tuple(out.shape[-2:]))
     if _is_integer_type(as_type):
         out = torch.round(out)                      # halves to even, like np.round
@@ -140,7 +152,7 @@ def apply_2d_zoom_3d(arr3d, spacing, new_spacing, order=1, do_blur=True, as_type
     :param arr3d: [#slices, IH, IW]; a numpy array (-> numpy array) or a CUDA tensor (-> CUDA tensor, no host round trip)
     :param spacing: the array's spacing; only the last two entries (y, x) count
     :param new_spacing: the spacing to resample to; only the last two entries count
-    :param order: 1 (anything else raises NotImplementedError)
+    :param order: 1 (linear) or 0 (nearest: label maps, with do_blur=False); anything else raises NotImplementedError
     :param do_blur: Gaussian blur with sigma = 0.25 / zoom before the interpolation
     :param as_type: an integer type marks labels (use with do_blur=False): the result is rounded and cast; otherwise float32
     :param clamp_edges: False mirrors scipy's all-zero last row / column where it occurs (module docstring); True repeats the edge

@@ -53,6 +53,8 @@ def build_parser():
     a("--synthetic_pool", type=int, default=8, help="distinct device-resident synthetic batches that --synthetic cycles through (made before the loop)")
     a("--volumes_dir", type=str, default=None, help="train on the volumes (.npy [Z,H,W] / [T,Z,H,W], .nii(.gz), .mha, .mhd) of this "
                                                   "directory: device-resident cache + on-device triplet assembly / augmentation")
+    a("--labels_dir", type=str, default=None, help="--dataset ACDCLBL with --volumes_dir: the label maps of those volumes, paired by file "
+                                                 "name (the same stem, any supported extension; integral values 0 ... 255, the image's shape)")
     a("--val_volumes_dir", type=str, default=None, help="4-D (or 3-D) validation images of this directory become the in-memory image_dict "
                                                       "that validate() previews as val_image_e###_p###.png (at most --val_patients of them)")
     a("--resample", action="store_true", help="with --volumes_dir / --val_volumes_dir: resample every volume in-plane from its header's "

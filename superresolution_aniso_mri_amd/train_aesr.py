@@ -6,7 +6,8 @@ Data: the reference's SimpleITK/NIfTI dataset readers and numpy augmentations ar
 hot path; ``--synthetic`` feeds device-resident synthetic triplets in the same batch layout (``--dataset ACDCLBL``: two-channel triplets, image +
 label map, for the multi-channel trainers; ``--ae_class`` then defaults to MultiChannelAE), ``--volumes_dir``
 feeds the volumes of a directory through the on-device augmenters of data_device.py (cardiac datasets: ``TripletAugmenter``; OASIS /
-dHCP / ADNI: thick slices simulated on the device, then ``BrainTripletAugmenter``).  Launch under
+dHCP / ADNI: thick slices simulated on the device, then ``BrainTripletAugmenter``; ``--dataset ACDCLBL`` with ``--labels_dir``: the label
+maps paired by file name, ``LabelledTripletAugmenter``).  Launch under
 ``python -m torch.distributed.run --nproc-per-node N`` for data parallel training (one process per GPU, RCCL)."""
 import os
 from shutil import rmtree
@@ -62,10 +63,16 @@ def main(argv=None, brain=False):
     labelled = args_dict["dataset"] == "ACDCLBL"
     if labelled and args_dict["ae_class"] == "VanillaACAI":
         args_dict["ae_class"] = "MultiChannelAE"        # the two-headed network is the only one the multi-channel trainers can drive
-    if labelled and args_dict.get("volumes_dir"):
+    if labelled and args_dict.get("volumes_dir") and not args_dict.get("labels_dir"):
         raise NotImplementedError("--dataset ACDCLBL with --volumes_dir: the label-aware augmenter (image and label map cropped and rotated "
-                                  "together, intensity curve on the image only) is not built; train with --synthetic or feed "
-                                  "trainer.train() two-channel batches from your own loader")
+                                  "together, intensity curve on the image only) needs --labels_dir DIR, the label maps of those volumes "
+                                  "paired by file name; without label files train with --synthetic or feed trainer.train() two-channel "
+                                  "batches from your own loader")
+    if args_dict.get("labels_dir") and not (labelled and args_dict.get("volumes_dir")):
+        raise ValueError("--labels_dir goes with --dataset ACDCLBL and --volumes_dir")
+    if labelled and args_dict.get("volumes_dir") and args_dict.get("val_volumes_dir"):
+        raise NotImplementedError("--dataset ACDCLBL with --val_volumes_dir: whole-volume validation previews are not built for the "
+                                  "multi-channel trainers")
     cfg = NetworkConfig(args_dict["model"], dataset=args_dict["dataset"], ae_class=args_dict["ae_class"])
     args_dict = merge_args_architecture(args_dict, cfg.architecture)
     if not args_dict.get("synthetic") and not args_dict.get("volumes_dir"):
@@ -104,6 +111,16 @@ def main(argv=None, brain=False):
                                           slice_selection=args_dict["slice_selection"], downsample_steps=args_dict["downsample_steps"],
                                           rs=np.random.RandomState(args_dict["seed"]), rs_transform=np.random.RandomState(args_dict["seed"] + 1),
                                           device=args_dict["device"])
+    elif labelled and args_dict.get("volumes_dir"):
+        # image and label volumes in two device-resident caches, ONE kernel per two-channel batch (data_device.LabelledTripletAugmenter);
+        # one RandomState serves the slice choice and the transforms, as in the reference's training script
+        from .data_device import LabelledTripletAugmenter, load_labelled_volume_dir
+        augmenter = LabelledTripletAugmenter(*load_labelled_volume_dir(args_dict["volumes_dir"], args_dict["labels_dir"],
+                                                                       resample=bool(args_dict.get("resample")),
+                                                                       new_spacing=args_dict.get("new_spacing")),
+                                             args_dict["width"], args_dict.get("aug_patch_size") or args_dict["width"],
+                                             slice_selection=args_dict["slice_selection"], rs=np.random.RandomState(args_dict["seed"]),
+                                             device=args_dict["device"])
     elif args_dict.get("volumes_dir"):
         # device-resident volume cache + ONE kernel per batch (data_device.py); every rank draws the same global batch from
         # the same RandomState and keeps its own triplets, so the step sees the batch a single process would see
@@ -128,6 +145,10 @@ def main(argv=None, brain=False):
             stride = max(1, args_dict["width"] // max(1, args_dict["latent_width"]))
             return augmenter.next_batch(n, reuse_output=training, shard=(dp.rank, dp.world) if dp.active else None, raw=not training,
                                         size=None if training else augmenter.eval_size(stride))
+        if labelled and augmenter is not None:
+            # the multi-channel trainers step eagerly in one process: fresh tensors per batch; the validation batch goes through the
+            # reference's test transform (raw=True: no intensity curve, no rotation) and is made once
+            return augmenter.next_batch(n, shard=(dp.rank, dp.world) if dp.active else None, raw=not training)
         if augmenter is not None:
             # training batches go into the augmenter's persistent output buffer, which the captured step reads directly (data parallel: the
             # rank's own triplets only -- every rank draws the whole global batch's random numbers); the validation batch is kept for the
