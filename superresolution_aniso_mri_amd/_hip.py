@@ -1,6 +1,6 @@
 """ctypes binding of libaesr_hip.so (C ABI: include/aesr_hip.h, include/aesr_hip_preproc.h, include/aesr_hip_dataprep.h, include/aesr_hip_train.h,
 include/aesr_hip_baselines.h, include/aesr_hip_reslice.h, include/aesr_hip_seg.h, include/aesr_hip_surface.h,
-include/aesr_hip_bnpool.h and include/aesr_hip_labelprep.h).
+include/aesr_hip_bnpool.h, include/aesr_hip_labelprep.h and include/aesr_hip_components.h).
 
 There is NO fallback: if the shared library is missing or an entry point is absent this module raises at
 import time, and every wrapper raises RuntimeError with the library's own message when a call fails.
@@ -228,6 +228,16 @@ SIGNATURES_LABELPREP = {
     "aesr_labelled_triplet_assemble": (c_int, [P, P, ctypes.POINTER(TripletDesc), c_int, c_int, P, P, P]),
     "aesr_labelled_triplet_assemble_raw": (c_int, [P, P, ctypes.POINTER(TripletDesc), c_int, c_int, P, P, P]),
 }
+# the connected-component ABI (include/aesr_hip_components.h, same library): must list every symbol that header declares (checked by tests)
+SIGNATURES_COMPONENTS = {
+    "aesr_components_workspace_bytes": (c_size_t, [c_int] * 5),
+    "aesr_components_label": (c_int, [P, P, P, P] + [c_int] * 4 + [IP, c_int, c_int, c_int, P]),
+    "aesr_components_tables": (c_int, [P, P, P, IP, P, P, c_size_t] + [c_int] * 4 + [IP, c_int, c_int, P]),
+    "aesr_components_overlap_count": (c_int, [P] * 6 + [c_int] * 4 + [IP, c_int, c_int, P]),
+    "aesr_components_overlap_runs": (c_int, [P] * 5 + [ctypes.c_longlong, P, c_size_t] + [c_int] * 4 + [IP, c_int, c_int, P]),
+    "aesr_components_apply_table": (c_int, [P, P, P, IP, P, P, c_size_t, P] + [c_int] * 4 + [IP, c_int, c_int, P]),
+}
+COMPONENTS_MAX_CLASSES, COMPONENTS_COLUMNS, COMPONENTS_MAX_PER_CLASS = 8, 8, 1 << 24          # AESR_COMPONENTS_* of include/aesr_hip_components.h
 SURFACE_MAX_CLASSES, SURFACE_COUNTS, SURFACE_MAX_W = 8, 7, 4096          # AESR_SURFACE_* of include/aesr_hip_surface.h
 SEG_MIN_CLASSES, SEG_MAX_CLASSES = 2, 8
 RESLICE_NEAREST, RESLICE_LINEAR = 0, 1          # AESR_RESLICE_* (RS_* below are the modes of aesr_resample2_*)
@@ -256,7 +266,7 @@ def _load():
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_PREPROC.items()) + list(SIGNATURES_DATAPREP.items())
                                    + list(SIGNATURES_TRAIN.items()) + list(SIGNATURES_BASELINES.items()) + list(SIGNATURES_RESLICE.items())
                                    + list(SIGNATURES_SEG.items()) + list(SIGNATURES_SURFACE.items()) + list(SIGNATURES_BNPOOL.items())
-                                   + list(SIGNATURES_LABELPREP.items())):
+                                   + list(SIGNATURES_LABELPREP.items()) + list(SIGNATURES_COMPONENTS.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             raise RuntimeError("libaesr_hip.so does not export %s (stale build?)" % name)

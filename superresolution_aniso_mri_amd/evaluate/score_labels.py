@@ -2,10 +2,13 @@
 
     python -m superresolution_aniso_mri_amd.evaluate.score_labels --pred DIR|FILE --ref DIR|FILE [--classes 1 2 3] [--ndim 2|3]
                                                                    [--connectivity k] [--spacing Z Y X] [--out scores.npz]
+                                                                   [--objects] [--largest_component]
 
 Files are NIfTI (.nii, .nii.gz), MetaImage (.mha, .mhd) or .npy; with directories they are matched by name and a file without a partner is
 an error.  The spacing comes from the header of the reference file; .npy has none and needs --spacing.  A 4-D file is a series of frames.
-Prints one table (mean over files and frames per class, and the mean over classes) and writes every array with --out."""
+Prints one table (mean over files and frames per class, and the mean over classes) and writes every array with --out.
+--objects adds the object-wise scores of evaluate/object_metrics.py (obj_tpr, obj_fpr, obj_assd and what they are made of) to the table and
+to --out; --largest_component keeps only the largest connected component of every class of the prediction before anything is scored."""
 import argparse
 import os
 import sys
@@ -14,9 +17,11 @@ import numpy as np
 
 from .. import volume_io
 from . import seg_metrics
+from .object_metrics import OBJECT_KEYS
 
 EXTENSIONS = (".nii.gz", ".nii", ".mha", ".mhd", ".npy")
 TABLE_KEYS = ("dice", "jc", "hd", "hd95", "assd", "ravd")
+OBJECT_TABLE_KEYS = ("obj_tpr", "obj_fpr", "obj_assd")
 
 
 def _stem(name):
@@ -74,8 +79,9 @@ def read_labels(path, spacing=None):
     return np.ascontiguousarray(arr, dtype=np.float32), tuple(float(s) for s in spacing)
 
 
-def score_files(pairs, classes=None, ndim=3, connectivity=1, spacing=None):
-    """pairs of match_files -> dict of arrays [frames of all files, C] (the keys of segmentation_scores) + names, frame_of"""
+def score_files(pairs, classes=None, ndim=3, connectivity=1, spacing=None, objects=False, largest_component=False):
+    """pairs of match_files -> dict of arrays [frames of all files, C] (the keys of segmentation_scores) + names, frame_of.
+    ``objects``: the keys of object_metrics.object_scores as well; ``largest_component``: the prediction is cleaned first."""
     rows, names = [], []
     if classes is None:          # one class list for every file: 1 ... the largest label of any reference
         top = max(float(read_labels(rpath, spacing)[0].max()) for _, _, rpath in pairs)
@@ -87,7 +93,15 @@ def score_files(pairs, classes=None, ndim=3, connectivity=1, spacing=None):
         pred, _ = read_labels(ppath, sp)
         if pred.shape != ref.shape:
             raise ValueError("%s: prediction %s and reference %s differ in shape" % (name, pred.shape, ref.shape))
-        rows.append(seg_metrics.segmentation_scores(pred, ref, sp, classes=classes, ndim=ndim, connectivity=connectivity))
+        if largest_component:
+            from .components import keep_largest_component
+            pred = keep_largest_component(pred, classes=classes, ndim=ndim, connectivity=connectivity)
+        row = seg_metrics.segmentation_scores(pred, ref, sp, classes=classes, ndim=ndim, connectivity=connectivity)
+        if objects:
+            from .object_metrics import object_scores
+            obj = object_scores(pred, ref, sp, classes=classes, ndim=ndim, connectivity=connectivity)
+            row.update({k: obj[k] for k in OBJECT_KEYS})
+        rows.append(row)
         names += [name] * ref.shape[0]
     out = {k: np.concatenate([row[k] for row in rows]) for k in rows[0] if k != "classes"}
     out["classes"] = rows[0]["classes"]
@@ -96,14 +110,15 @@ def score_files(pairs, classes=None, ndim=3, connectivity=1, spacing=None):
 
 
 def format_table(scores):
-    lines = ["%-8s" % "class" + "".join("%12s" % k for k in TABLE_KEYS)]
+    keys = TABLE_KEYS + tuple(k for k in OBJECT_TABLE_KEYS if k in scores)
+    lines = ["%-8s" % "class" + "".join("%12s" % k for k in keys)]
     import warnings
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", RuntimeWarning)          # a class that is empty everywhere: the mean of nothing is NaN
-        means = {k: np.nanmean(scores[k], axis=0) for k in TABLE_KEYS}
+        means = {k: np.nanmean(scores[k], axis=0) for k in keys}
         for i, c in enumerate(scores["classes"]):
-            lines.append("%-8d" % c + "".join("%12.4f" % means[k][i] for k in TABLE_KEYS))
-        lines.append("%-8s" % "mean" + "".join("%12.4f" % np.nanmean(means[k]) for k in TABLE_KEYS))
+            lines.append("%-8d" % c + "".join("%12.4f" % means[k][i] for k in keys))
+        lines.append("%-8s" % "mean" + "".join("%12.4f" % np.nanmean(means[k]) for k in keys))
     return "\n".join(lines)
 
 
@@ -116,10 +131,12 @@ def main(argv=None):
     ap.add_argument("--connectivity", type=int, default=1)
     ap.add_argument("--spacing", type=float, nargs=3, default=None, metavar=("Z", "Y", "X"))
     ap.add_argument("--out", default=None)
+    ap.add_argument("--objects", action="store_true", help="add the object-wise scores (obj_tpr, obj_fpr, obj_asd, obj_assd)")
+    ap.add_argument("--largest_component", action="store_true", help="keep the largest component of every class of the prediction")
     args = ap.parse_args(argv)
     try:
         pairs = match_files(args.pred, args.ref)
-        scores = score_files(pairs, args.classes, args.ndim, args.connectivity, args.spacing)
+        scores = score_files(pairs, args.classes, args.ndim, args.connectivity, args.spacing, args.objects, args.largest_component)
     except ValueError as e:
         ap.error(str(e))
     print("%d file(s), %d frame(s), ndim=%d, connectivity=%d" % (len(pairs), len(scores["names"]), args.ndim, args.connectivity))

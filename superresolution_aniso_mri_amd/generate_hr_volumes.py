@@ -199,6 +199,27 @@ def labels_name(name):
     return name + "_labels"
 
 
+def clean_label_volume(labels_np, largest_component=False, min_component_size=0):
+    """A decoded label map can hold small detached islands of a class.  [z,y,x] or [t,z,y,x] class ids -> the same with, per frame and
+    class (1 ... the largest label), components of fewer than ``min_component_size`` voxels set to 0 and / or only the largest component
+    kept (3-D, face connectivity; evaluate/components.py, on the device).  Shape and dtype are kept; nothing asked for: the input itself."""
+    if not largest_component and not min_component_size:
+        return labels_np
+    from .evaluate.components import keep_largest_component, remove_small_components
+    if not labels_np.max() >= 1:
+        return labels_np
+    classes = list(range(1, int(labels_np.max()) + 1))
+    out = []
+    for c0 in range(0, len(classes), 8):          # the kernels take eight classes at a time
+        chunk, cleaned = classes[c0:c0 + 8], labels_np if not out else out[-1]
+        if min_component_size:
+            cleaned = remove_small_components(cleaned, int(min_component_size), classes=chunk)
+        if largest_component:
+            cleaned = keep_largest_component(cleaned, classes=chunk)
+        out.append(cleaned)
+    return out[-1]
+
+
 def normalize_on_device(x, perc=(1, 99)):
     """``array_to_torch``'s intensity rule on a device tensor: values outside [0, 1] -> the 1st..99th percentile window mapped to [0, 1]
     and clipped (percentiles with numpy's linear interpolation between the two nearest sorted values)."""
@@ -280,9 +301,17 @@ def main(argv=None):
     p.add_argument("--labels_input_dir", type=str, default=None,
                    help="label volumes (class ids) with the same file names as the images: needs a multi-channel model; writes <name>_labels "
                         "beside every super-resolved image, an integer volume with the image's new z spacing")
+    p.add_argument("--largest_component", action="store_true",
+                   help="with --labels_input_dir: keep only the largest connected component of every class in <name>_labels")
+    p.add_argument("--min_component_size", type=int, default=0, metavar="K",
+                   help="with --labels_input_dir: remove components of fewer than K voxels from <name>_labels")
     p.add_argument("--output_dir", type=str, default=None)
     p.add_argument("--save", action="store_true")
     args = p.parse_args(argv)
+    if (args.largest_component or args.min_component_size) and args.labels_input_dir is None:
+        p.error("--largest_component and --min_component_size clean <name>_labels: they need --labels_input_dir")
+    if args.min_component_size < 0:
+        p.error("--min_component_size must not be negative")
     if args.method != "ae" and args.resample:
         p.error("--resample belongs to --method ae: a conventional --method interpolates along z only and keeps the in-plane grid")
     if args.method == "ae" and args.exper_dir is None:
@@ -324,7 +353,8 @@ def main(argv=None):
 
     def upsample(arr, spacing_yx, fname=None):
         if label_files:
-            return upsample_volume(trainer, arr, args.num_interpolations, label_array(fname))
+            hr_img, hr_lab = upsample_volume(trainer, arr, args.num_interpolations, label_array(fname))
+            return hr_img, clean_label_volume(hr_lab, args.largest_component, args.min_component_size)
         if args.method != "ae":
             return expand_volume(arr, args.num_interpolations, args.method, args.align, args.lanczos_radius)
         if not args.resample:

@@ -592,3 +592,100 @@ def surface_distances(workspace, counts, shape, spacing, ndim=3, counts_host=Non
     check(lib.aesr_surface_distances(ptr(workspace), ptr(counts), counts_host.ctypes.data_as(_hip.LLP), ptr(distances), total if total else 1,
                                      ptr(stats), N, Z, H, W, C, int(ndim), _hip.double_array(spacing), stream()), "aesr_surface_distances")
     return distances[:total], stats, lengths
+
+
+# ---- connected components (include/aesr_hip_components.h, csrc/components.hip) ----------------------------------------------------------
+def _components_check_volume(vol, name="vol"):
+    _hip.require_gpu_tensor(vol, name)
+    if vol.dim() != 4:
+        raise ValueError("%s must be [N, Z, H, W] (got %s)" % (name, tuple(vol.shape)))
+    return tuple(int(s) for s in vol.shape)
+
+
+def components_workspace_bytes(N, Z, H, W, C):
+    """Bytes of workspace the component entry points share for N volumes [Z, H, W] and C classes (0: a size the library refuses)."""
+    return int(lib.aesr_components_workspace_bytes(int(N), int(Z), int(H), int(W), int(C)))
+
+
+def _components_workspace(workspace, shape, C, device):
+    nbytes = components_workspace_bytes(*shape, C)
+    if workspace is None:
+        return torch.empty(max(nbytes, 16), device=device, dtype=torch.uint8)
+    if workspace.numel() < nbytes or not workspace.is_cuda or workspace.dtype != torch.uint8:
+        raise ValueError("workspace must be a CUDA uint8 tensor of at least %d bytes" % nbytes)
+    return workspace
+
+
+def components_units(shape, ndim):
+    """Number of units of [N, Z, H, W] volumes: slices with ndim = 2, frames with ndim = 3."""
+    return int(shape[0]) * int(shape[1]) if int(ndim) == 2 else int(shape[0])
+
+
+def components_label(vol, classes, ndim=3, connectivity=1, workspace=None):
+    """vol: CUDA fp32 [N, Z, H, W] label volume; classes: the class ids.  Returns (labels int32 [N, Z, H, W]: 0 or the voxel's component
+    number within its (unit, class), numbered as scipy.ndimage.label does; n_components int32 [U, C] on the device; the workspace).
+    No host sync."""
+    shape = _components_check_volume(vol)
+    classes = [int(c) for c in classes]
+    C = len(classes)
+    workspace = _components_workspace(workspace, shape, C, vol.device)
+    labels = torch.empty(shape, device=vol.device, dtype=torch.int32)
+    ncomp = torch.empty((max(components_units(shape, ndim), 1), max(C, 1)), device=vol.device, dtype=torch.int32)
+    check(lib.aesr_components_label(ptr(vol), ptr(labels), ptr(ncomp), ptr(workspace), *shape, _hip.int_array(classes), C, int(ndim),
+                                    int(connectivity), stream()), "aesr_components_label")
+    return labels, ncomp, workspace
+
+
+def _components_host_counts(n_components, n_components_host):
+    if n_components_host is None:
+        n_components_host = n_components.cpu().numpy()
+    return np.ascontiguousarray(n_components_host, dtype=np.int32)
+
+
+def components_tables(vol, labels, n_components, classes, ndim=3, workspace=None, n_components_host=None):
+    """After ``components_label`` with the same classes / ndim.  Returns (table int64 [R, 8] on the device, one row per component in the
+    order (unit, class, number): voxel count, z0, z1, y0, y1, x0, x1, linear index of the first voxel within its frame; the host copy of
+    n_components).  Copies ``n_components`` to the host unless ``n_components_host`` is given -- the one synchronisation."""
+    shape = _components_check_volume(vol)
+    classes = [int(c) for c in classes]
+    host = _components_host_counts(n_components, n_components_host)
+    rows = int(host.astype(np.int64).sum())
+    workspace = _components_workspace(workspace, shape, len(classes), vol.device)
+    table = torch.empty((max(rows, 1), _hip.COMPONENTS_COLUMNS), device=vol.device, dtype=torch.int64)
+    check(lib.aesr_components_tables(ptr(vol), ptr(labels), ptr(n_components), host.ctypes.data_as(_hip.IP), ptr(workspace), ptr(table),
+                                     max(rows, 1), *shape, _hip.int_array(classes), len(classes), int(ndim), stream()), "aesr_components_tables")
+    return table[:rows], host
+
+
+def components_overlaps(vol_a, labels_a, vol_b, labels_b, classes, ndim=3, workspace=None):
+    """The overlap runs of two labelled volumes of the same shape, classes and ndim: int32 [K, 4] on the device, rows (unit, class index,
+    label in A, label in B) in raster order; their distinct rows are the pairs of components that share a voxel.  One host sync (K)."""
+    shape = _components_check_volume(vol_a, "vol_a")
+    if _components_check_volume(vol_b, "vol_b") != shape or tuple(labels_a.shape) != shape or tuple(labels_b.shape) != shape:
+        raise ValueError("the two volumes and their label maps must have one shape")
+    classes = [int(c) for c in classes]
+    workspace = _components_workspace(workspace, shape, len(classes), vol_a.device)
+    count = torch.empty(1, device=vol_a.device, dtype=torch.int64)
+    cls = _hip.int_array(classes)
+    check(lib.aesr_components_overlap_count(ptr(vol_a), ptr(labels_a), ptr(vol_b), ptr(labels_b), ptr(workspace), ptr(count), *shape, cls,
+                                            len(classes), int(ndim), stream()), "aesr_components_overlap_count")
+    K = int(count.item())
+    runs = torch.empty((max(K, 1), 4), device=vol_a.device, dtype=torch.int32)
+    check(lib.aesr_components_overlap_runs(ptr(vol_a), ptr(labels_a), ptr(vol_b), ptr(labels_b), ptr(workspace), K, ptr(runs), max(K, 1), *shape,
+                                           cls, len(classes), int(ndim), stream()), "aesr_components_overlap_runs")
+    return runs[:K]
+
+
+def components_apply_table(vol, labels, n_components, table, classes, ndim=3, workspace=None, n_components_host=None):
+    """out[p] = 0 where labels[p] == 0, else table[offset[unit][class] + labels[p] - 1] (fp32 [N, Z, H, W]); ``table``: CUDA fp32 with one
+    entry per component in the order (unit, class, number)."""
+    shape = _components_check_volume(vol)
+    classes = [int(c) for c in classes]
+    host = _components_host_counts(n_components, n_components_host)
+    _hip.require_gpu_tensor(table, "table")
+    workspace = _components_workspace(workspace, shape, len(classes), vol.device)
+    out = torch.empty(shape, device=vol.device, dtype=torch.float32)
+    check(lib.aesr_components_apply_table(ptr(vol), ptr(labels), ptr(n_components), host.ctypes.data_as(_hip.IP), ptr(workspace), ptr(table),
+                                          int(table.numel()), ptr(out), *shape, _hip.int_array(classes), len(classes), int(ndim), stream()),
+          "aesr_components_apply_table")
+    return out
