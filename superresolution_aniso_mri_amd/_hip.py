@@ -1,6 +1,4 @@
-"""ctypes binding of libaesr_hip.so (C ABI: include/aesr_hip.h, include/aesr_hip_preproc.h, include/aesr_hip_dataprep.h, include/aesr_hip_train.h,
-include/aesr_hip_baselines.h, include/aesr_hip_reslice.h, include/aesr_hip_seg.h, include/aesr_hip_surface.h,
-include/aesr_hip_bnpool.h, include/aesr_hip_labelprep.h and include/aesr_hip_components.h).
+"""ctypes binding of libaesr_hip.so (C ABI: the headers under include/, one table each; ``HEADERS`` maps header to table).
 
 There is NO fallback: if the shared library is missing or an entry point is absent this module raises at
 import time, and every wrapper raises RuntimeError with the library's own message when a call fails.
@@ -52,7 +50,7 @@ class PackJob(ctypes.Structure):
     _fields_ = [("w", c_void_p), ("packed", c_void_p), ("Cout", c_int), ("Cin", c_int), ("KS", c_int), ("transpose", c_int)]
 
 
-# name -> (restype, argtypes); must list every symbol include/aesr_hip.h declares (checked by tests)
+# One table per public header, name -> (restype, argtypes); ``HEADERS`` below binds them.
 SIGNATURES = {
     "aesr_version": (c_int, []),
     "aesr_last_error_string": (c_char_p, []),
@@ -170,34 +168,32 @@ SIGNATURES = {
     "aesr_comm_allreduce_many": (c_int, [P, ctypes.POINTER(c_void_p), ctypes.POINTER(c_size_t), c_int, c_int, c_int, P]),
     "aesr_comm_broadcast": (c_int, [P, P, c_size_t, c_int, c_int, P]),
 }
-# the volume pre/post-processing ABI (include/aesr_hip_preproc.h, same library): must list every symbol that header declares (checked by tests)
+# volume pre/post-processing
 SIGNATURES_PREPROC = {
     "aesr_inplane_out_size": (c_int, [c_int, c_double]),
     "aesr_inplane_workspace_bytes": (c_size_t, [c_int, c_int]),
     "aesr_inplane_resample": (c_int, [P, P, P] + [c_int] * 5 + [DP, c_int, DP, c_int, IP, DP, IP, DP, c_int, P]),
 }
-# the brain data preparation ABI (include/aesr_hip_dataprep.h, same library): must list every symbol that header declares (checked by tests)
+# brain data preparation
 SIGNATURES_DATAPREP = {
     "aesr_thick_slices_out_slices": (c_int, [c_int, c_int]),
     "aesr_thick_slices_store_bytes": (c_int, [c_int, P, P]),
     "aesr_thick_slices": (c_int, [P, P, c_int, c_int, c_int, c_int, DP, c_int, P]),
     "aesr_triplet_assemble_raw": (c_int, [P, ctypes.POINTER(TripletDesc), c_int, c_int, P, P, P]),
 }
-# the fused training-step ABI (include/aesr_hip_train.h, same library): must list every symbol that header declares (checked by tests)
+# the fused training step
 SIGNATURES_TRAIN = {
     "aesr_conv2d_cout1_bwd_workspace_floats": (c_size_t, [c_int]),
     "aesr_conv2d_cout1_bwd": (c_int, [P] * 8 + [c_int] * 5 + [c_float, c_int, c_float, P]),
 }
-# BatchNorm + AvgPool2d(2) pooled once in the statistics pass (include/aesr_hip_bnpool.h, same library): must list every symbol that header
-# declares (checked by tests)
+# BatchNorm + AvgPool2d(2) pooled once in the statistics pass
 SIGNATURES_BNPOOL = {
     "aesr_bn_pool_supported": (c_int, [c_int] * 5),
     "aesr_bn_pool_stats_finalize": (c_int, [P, P, P, DP] + [P] * 9 + [c_int] * 5 + [IP, c_float, c_float, c_int, P]),
     "aesr_bn_pool_apply": (c_int, [P, P, P, P] + [c_int] * 5 + [IP, P]),
     "aesr_bn_pool_bwd": (c_int, [P] * 7 + [DP] + [P] * 4 + [c_int] * 5 + [c_float, c_int, IP, P]),
 }
-# the conventional through-plane interpolation ABI (include/aesr_hip_baselines.h, same library): must list every symbol that header declares
-# (checked by tests)
+# conventional through-plane interpolation
 SIGNATURES_BASELINES = {
     "aesr_z_expand_out_slices": (c_int, [c_int, c_int, c_int]),
     "aesr_z_expand_store_bytes": (c_int, [c_int, P, P]),
@@ -205,30 +201,30 @@ SIGNATURES_BASELINES = {
     "aesr_bspline_prefilter_z": (c_int, [P, P] + [c_int] * 4 + [P]),
     "aesr_z_expand": (c_int, [P, P, P] + [c_int] * 7 + [IP, DP, c_int, c_int, P]),
 }
-# the oblique reslicing ABI (include/aesr_hip_reslice.h, same library): must list every symbol that header declares (checked by tests)
+# oblique reslicing
 SIGNATURES_RESLICE = {
     "aesr_reslice_affine": (c_int, [P, P] + [c_int] * 7 + [DP, c_int, P]),
     "aesr_reslice_grid": (c_int, [P, P, P] + [c_int] * 7 + [c_int, P]),
 }
-# the label-head ABI (include/aesr_hip_seg.h, same library): must list every symbol that header declares (checked by tests)
+# the label head
 SIGNATURES_SEG = {
     "aesr_softmax_dice_workspace_floats": (c_size_t, [c_int] * 4),
     "aesr_softmax_dice_fwd": (c_int, [P, P, c_size_t] + [P] * 5 + [c_int] * 4 + [P]),
     "aesr_softmax_dice_bwd": (c_int, [P, P, c_size_t, P, P, P] + [c_int] * 4 + [P]),
 }
-# the segmentation-score ABI (include/aesr_hip_surface.h, same library): must list every symbol that header declares (checked by tests)
+# segmentation scores
 LLP = ctypes.POINTER(ctypes.c_longlong)     # host array of int64
 SIGNATURES_SURFACE = {
     "aesr_surface_workspace_bytes": (c_size_t, [c_int] * 5),
     "aesr_surface_borders": (c_int, [P, P, P, P] + [c_int] * 4 + [IP, c_int, c_int, c_int, P]),
     "aesr_surface_distances": (c_int, [P, P, LLP, P, c_size_t, P] + [c_int] * 6 + [DP, P]),
 }
-# the labelled training batches ABI (include/aesr_hip_labelprep.h, same library): must list every symbol that header declares (checked by tests)
+# labelled training batches
 SIGNATURES_LABELPREP = {
     "aesr_labelled_triplet_assemble": (c_int, [P, P, ctypes.POINTER(TripletDesc), c_int, c_int, P, P, P]),
     "aesr_labelled_triplet_assemble_raw": (c_int, [P, P, ctypes.POINTER(TripletDesc), c_int, c_int, P, P, P]),
 }
-# the connected-component ABI (include/aesr_hip_components.h, same library): must list every symbol that header declares (checked by tests)
+# connected components
 SIGNATURES_COMPONENTS = {
     "aesr_components_workspace_bytes": (c_size_t, [c_int] * 5),
     "aesr_components_label": (c_int, [P, P, P, P] + [c_int] * 4 + [IP, c_int, c_int, c_int, P]),
@@ -236,6 +232,22 @@ SIGNATURES_COMPONENTS = {
     "aesr_components_overlap_count": (c_int, [P] * 6 + [c_int] * 4 + [IP, c_int, c_int, P]),
     "aesr_components_overlap_runs": (c_int, [P] * 5 + [ctypes.c_longlong, P, c_size_t] + [c_int] * 4 + [IP, c_int, c_int, P]),
     "aesr_components_apply_table": (c_int, [P, P, P, IP, P, P, c_size_t, P] + [c_int] * 4 + [IP, c_int, c_int, P]),
+}
+# The C ABI, header by header in the order the headers were added: each table must list every symbol its header under include/ declares,
+# with the types of the prototype, and no symbol may stand in two (tests/test_abi.py checks all of it against the headers and the library).
+# _load() binds exactly these tables; include/ is not read at run time.
+HEADERS = {
+    "aesr_hip.h": SIGNATURES,
+    "aesr_hip_preproc.h": SIGNATURES_PREPROC,
+    "aesr_hip_dataprep.h": SIGNATURES_DATAPREP,
+    "aesr_hip_train.h": SIGNATURES_TRAIN,
+    "aesr_hip_baselines.h": SIGNATURES_BASELINES,
+    "aesr_hip_reslice.h": SIGNATURES_RESLICE,
+    "aesr_hip_seg.h": SIGNATURES_SEG,
+    "aesr_hip_surface.h": SIGNATURES_SURFACE,
+    "aesr_hip_bnpool.h": SIGNATURES_BNPOOL,
+    "aesr_hip_labelprep.h": SIGNATURES_LABELPREP,
+    "aesr_hip_components.h": SIGNATURES_COMPONENTS,
 }
 COMPONENTS_MAX_CLASSES, COMPONENTS_COLUMNS, COMPONENTS_MAX_PER_CLASS = 8, 8, 1 << 24          # AESR_COMPONENTS_* of include/aesr_hip_components.h
 SURFACE_MAX_CLASSES, SURFACE_COUNTS, SURFACE_MAX_W = 8, 7, 4096          # AESR_SURFACE_* of include/aesr_hip_surface.h
@@ -263,14 +275,12 @@ def _load():
             "libaesr_hip.so not found at %s -- build it with `python __graft_entry__.py` (or `make -C "
             "superresolution_aniso_mri_amd/csrc`). The HIP extension is mandatory: there is no CPU/eager fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_PREPROC.items()) + list(SIGNATURES_DATAPREP.items())
-                                   + list(SIGNATURES_TRAIN.items()) + list(SIGNATURES_BASELINES.items()) + list(SIGNATURES_RESLICE.items())
-                                   + list(SIGNATURES_SEG.items()) + list(SIGNATURES_SURFACE.items()) + list(SIGNATURES_BNPOOL.items())
-                                   + list(SIGNATURES_LABELPREP.items()) + list(SIGNATURES_COMPONENTS.items())):
-        fn = getattr(lib, name, None)
-        if fn is None:
-            raise RuntimeError("libaesr_hip.so does not export %s (stale build?)" % name)
-        fn.restype, fn.argtypes = res, args
+    for table in HEADERS.values():
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name, None)
+            if fn is None:
+                raise RuntimeError("libaesr_hip.so does not export %s (stale build?)" % name)
+            fn.restype, fn.argtypes = res, args
     return lib
 
 

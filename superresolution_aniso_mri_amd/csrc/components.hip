@@ -20,6 +20,7 @@
 //     scan, pack by raster rank.
 // Everything is integer and roots are minimum indices: no result depends on the order in which atomics arrive.
 #include "aesr_kernels.h"
+#include "aesr_hostcheck.h"
 #include "../../include/aesr_hip_components.h"
 
 #define CC_THREADS 256
@@ -33,18 +34,12 @@
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-struct CcClasses {
-    float v[CC_MAXC];
-};
-
 // byte offsets of the workspace sections, all multiples of 16
 struct CcLayout {
     size_t parent, partial, block_off, offs, ov_partial, ov_off, total;
     long long T;
     int nb2, nbT;          // workgroups of 256 voxels: per slice (the larger of the two unit kinds, times N * Z), over the whole array
 };
-
-static inline size_t cc_up16(size_t v) { return (v + 15) / 16 * 16; }
 
 static CcLayout cc_layout(int N, int Z, int H, int W, int C) {
     CcLayout L;
@@ -53,22 +48,14 @@ static CcLayout cc_layout(int N, int Z, int H, int W, int C) {
     L.nbT = (int)((L.T + CC_THREADS - 1) / CC_THREADS);
     const size_t per_class = (size_t)N * Z * (size_t)L.nb2;          // >= N * ceil(Z H W / 256), the count with ndim = 3
     size_t o = 0;
-    L.parent = o;       o += cc_up16((size_t)L.T * 4);
-    L.partial = o;      o += cc_up16(per_class * C * 4);
-    L.block_off = o;    o += cc_up16(per_class * C * 4);
-    L.offs = o;         o += cc_up16(((size_t)N * Z * C + 1) * 4);
-    L.ov_partial = o;   o += cc_up16((size_t)L.nbT * 4);
-    L.ov_off = o;       o += cc_up16((size_t)L.nbT * 4);
+    L.parent = o;       o += aesr_up16((size_t)L.T * 4);
+    L.partial = o;      o += aesr_up16(per_class * C * 4);
+    L.block_off = o;    o += aesr_up16(per_class * C * 4);
+    L.offs = o;         o += aesr_up16(((size_t)N * Z * C + 1) * 4);
+    L.ov_partial = o;   o += aesr_up16((size_t)L.nbT * 4);
+    L.ov_off = o;       o += aesr_up16((size_t)L.nbT * 4);
     L.total = o;
     return L;
-}
-
-__device__ __forceinline__ int cc_class_of(float v, const CcClasses& cls, int C) {
-    int k = -1;
-#pragma unroll
-    for (int c = 0; c < CC_MAXC; ++c)
-        if (c < C && v == cls.v[c]) k = c;          // NaN equals nothing; ids are distinct, so at most one hit
-    return k;
 }
 
 // ---- union-find ------------------------------------------------------------------------------------------------------------------------
@@ -117,7 +104,7 @@ __device__ __forceinline__ void cc_union(int* parent, int a, int b) {
 
 // workgroup (slice s = n * Z + z, tile row ty, tile column tx); thread t the voxels (ty * 16 + t / 16, tx * 64 + 4 (t % 16) ... + 3)
 template <bool VEC>
-__global__ __launch_bounds__(CC_THREADS) void cc_tile_kernel(const float* __restrict__ vol, int* __restrict__ parent, CcClasses cls, int C, int H,
+__global__ __launch_bounds__(CC_THREADS) void cc_tile_kernel(const float* __restrict__ vol, int* __restrict__ parent, AesrClasses cls, int C, int H,
                                                              int W, int txn, int tyn, int diag) {
     __shared__ int lab[CC_TILE];
     __shared__ int kc[CC_TILE];
@@ -145,7 +132,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_tile_kernel(const float* __rest
     const int li0 = ly * CC_TW + lx0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        k[j] = (row_in && x0 + j < W) ? cc_class_of(v[j], cls, C) : -1;
+        k[j] = (row_in && x0 + j < W) ? aesr_class_of(v[j], cls, C) : -1;
         kc[li0 + j] = k[j];
         lab[li0 + j] = li0 + j;
     }
@@ -191,13 +178,13 @@ __global__ __launch_bounds__(CC_THREADS) void cc_tile_kernel(const float* __rest
 }
 
 // one thread per voxel p: the backward neighbours q < p of equal class in another tile of the slice, and (zr) in the slice above
-__global__ __launch_bounds__(CC_THREADS) void cc_merge_kernel(const float* __restrict__ vol, int* parent, CcClasses cls, int C, int T, int Z, int H,
+__global__ __launch_bounds__(CC_THREADS) void cc_merge_kernel(const float* __restrict__ vol, int* parent, AesrClasses cls, int C, int T, int Z, int H,
                                                               int W, int zr, int conn) {
     const long long gp = (long long)blockIdx.x * CC_THREADS + threadIdx.x;
     if (gp >= T) return;
     const int p = (int)gp;
     const float v = vol[p];
-    if (cc_class_of(v, cls, C) < 0) return;
+    if (aesr_class_of(v, cls, C) < 0) return;
     const int x = p % W, y = (p / W) % H, z = (p / (W * H)) % Z;
     const bool xe = x % CC_TW == 0, ye = y % CC_TH == 0;          // p is the first voxel of its tile in x / in y
     const bool diag = conn >= 2;
@@ -231,7 +218,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_merge_kernel(const float* __res
 
 // workgroup b of unit u takes the voxels [b * 256, (b + 1) * 256) of that unit, one per thread
 __global__ __launch_bounds__(CC_THREADS) void cc_flatten_kernel(const float* __restrict__ vol, const int* __restrict__ parent, int* __restrict__ labels,
-                                                                unsigned int* __restrict__ partial, CcClasses cls, int C, int Vu, int nb) {
+                                                                unsigned int* __restrict__ partial, AesrClasses cls, int C, int Vu, int nb) {
     __shared__ unsigned int red[CC_WAVES][CC_MAXC];
     const int u = blockIdx.x / nb, b = blockIdx.x - u * nb;
     const int idx = b * CC_THREADS + (int)threadIdx.x;
@@ -244,7 +231,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_flatten_kernel(const float* __r
         if (r >= 0) {
             for (int q = parent[r]; q != r; q = parent[r]) r = q;          // strictly decreasing: ends at the root
             root = r == p;
-            if (root) k = cc_class_of(vol[p], cls, C);
+            if (root) k = aesr_class_of(vol[p], cls, C);
         }
         labels[p] = r;
     }
@@ -294,14 +281,14 @@ __global__ __launch_bounds__(CC_THREADS) void cc_scan_kernel(const unsigned int*
 
 // same voxel assignment as cc_flatten_kernel; a root (labels[p] == p) writes its number over its parent entry
 __global__ __launch_bounds__(CC_THREADS) void cc_number_kernel(const float* __restrict__ vol, const int* __restrict__ labels, int* __restrict__ parent,
-                                                               const unsigned int* __restrict__ block_off, CcClasses cls, int C, int Vu, int nb) {
+                                                               const unsigned int* __restrict__ block_off, AesrClasses cls, int C, int Vu, int nb) {
     __shared__ unsigned int wtot[CC_MAXC][CC_WAVES];
     const int u = blockIdx.x / nb, b = blockIdx.x - u * nb;
     const int idx = b * CC_THREADS + (int)threadIdx.x;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int p = u * Vu + min(idx, Vu - 1);
     int k = -1;
-    if (idx < Vu && labels[p] == p) k = cc_class_of(vol[p], cls, C);
+    if (idx < Vu && labels[p] == p) k = aesr_class_of(vol[p], cls, C);
     unsigned int below = 0;
 #pragma unroll
     for (int c = 0; c < CC_MAXC; ++c)
@@ -382,7 +369,7 @@ __device__ __forceinline__ void cc_table_flush(unsigned long long* table, const 
 // what is left goes out lane by lane.  Sums, minima and maxima of integers: the order changes nothing.
 __global__ __launch_bounds__(CC_THREADS) void cc_table_kernel(const float* __restrict__ vol, const int* __restrict__ labels,
                                                               const int* __restrict__ n_components, const int* __restrict__ offs,
-                                                              unsigned long long* table, unsigned long long rows, CcClasses cls, int C, int T,
+                                                              unsigned long long* table, unsigned long long rows, AesrClasses cls, int C, int T,
                                                               int Z, int H, int W, int Vu) {
     const long long g0 = ((long long)blockIdx.x * CC_THREADS + threadIdx.x) * 4;
     const int lane = threadIdx.x & 63;
@@ -398,7 +385,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_table_kernel(const float* __res
         if (gp < T) {
             p = (int)gp;
             const int lab = labels[p];
-            const int k = lab > 0 ? cc_class_of(vol[p], cls, C) : -1;
+            const int k = lab > 0 ? aesr_class_of(vol[p], cls, C) : -1;
             if (k >= 0) {
                 const int uc = (p / Vu) * C + k;
                 const unsigned long long r = (unsigned long long)offs[uc] + (unsigned int)(lab - 1);
@@ -449,14 +436,14 @@ __global__ __launch_bounds__(CC_THREADS) void cc_table_kernel(const float* __res
 __global__ __launch_bounds__(CC_THREADS) void cc_apply_kernel(const float* __restrict__ vol, const int* __restrict__ labels,
                                                               const int* __restrict__ n_components, const int* __restrict__ offs,
                                                               const float* __restrict__ table, unsigned long long table_len, float* __restrict__ out,
-                                                              CcClasses cls, int C, int T, int Vu) {
+                                                              AesrClasses cls, int C, int T, int Vu) {
     const long long gp = (long long)blockIdx.x * CC_THREADS + threadIdx.x;
     if (gp >= T) return;
     const int p = (int)gp;
     const int lab = labels[p];
     float o = 0.f;
     if (lab > 0) {
-        const int k = cc_class_of(vol[p], cls, C);
+        const int k = aesr_class_of(vol[p], cls, C);
         if (k >= 0) {
             const int uc = (p / Vu) * C + k;
             const unsigned long long row = (unsigned long long)offs[uc] + (unsigned int)(lab - 1);
@@ -468,20 +455,20 @@ __global__ __launch_bounds__(CC_THREADS) void cc_apply_kernel(const float* __res
 
 // true when voxel p starts an x-run of equal (unit, class, label A, label B); k, la, lb are its class index and labels
 __device__ __forceinline__ bool cc_run_start(const float* __restrict__ va, const int* __restrict__ la, const float* __restrict__ vb,
-                                             const int* __restrict__ lb, int p, int W, const CcClasses& cls, int C, int& k, int& a, int& b) {
-    k = cc_class_of(va[p], cls, C);
-    if (k < 0 || cc_class_of(vb[p], cls, C) != k) return false;
+                                             const int* __restrict__ lb, int p, int W, const AesrClasses& cls, int C, int& k, int& a, int& b) {
+    k = aesr_class_of(va[p], cls, C);
+    if (k < 0 || aesr_class_of(vb[p], cls, C) != k) return false;
     a = la[p];
     b = lb[p];
     if (a <= 0 || b <= 0) return false;
     if (p % W == 0) return true;
     const int q = p - 1;          // the same row, so the same unit
-    return !(cc_class_of(va[q], cls, C) == k && cc_class_of(vb[q], cls, C) == k && la[q] == a && lb[q] == b);
+    return !(aesr_class_of(va[q], cls, C) == k && aesr_class_of(vb[q], cls, C) == k && la[q] == a && lb[q] == b);
 }
 
 __global__ __launch_bounds__(CC_THREADS) void cc_overlap_count_kernel(const float* __restrict__ va, const int* __restrict__ la,
                                                                       const float* __restrict__ vb, const int* __restrict__ lb,
-                                                                      unsigned int* __restrict__ partial, CcClasses cls, int C, int T, int W) {
+                                                                      unsigned int* __restrict__ partial, AesrClasses cls, int C, int T, int W) {
     __shared__ unsigned int red[CC_WAVES];
     const long long gp = (long long)blockIdx.x * CC_THREADS + threadIdx.x;
     int k, a, b;
@@ -527,7 +514,7 @@ __global__ __launch_bounds__(CC_SCAN_THREADS) void cc_overlap_scan_kernel(const 
 __global__ __launch_bounds__(CC_THREADS) void cc_overlap_runs_kernel(const float* __restrict__ va, const int* __restrict__ la,
                                                                      const float* __restrict__ vb, const int* __restrict__ lb,
                                                                      const unsigned int* __restrict__ off, int* __restrict__ runs,
-                                                                     unsigned long long limit, CcClasses cls, int C, int T, int W, int Vu) {
+                                                                     unsigned long long limit, AesrClasses cls, int C, int T, int W, int Vu) {
     __shared__ unsigned int wtot[CC_WAVES];
     const long long gp = (long long)blockIdx.x * CC_THREADS + threadIdx.x;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -551,25 +538,6 @@ __global__ __launch_bounds__(CC_THREADS) void cc_overlap_runs_kernel(const float
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------------------
-static bool cc_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
-struct CcBuf {
-    const void* p;
-    size_t bytes;
-    bool out;
-};
-
-// true when an output (or the workspace) overlaps any other buffer of the call
-static bool cc_any_overlap(const CcBuf* bufs, int n) {
-    for (int i = 0; i < n; ++i)
-        for (int j = i + 1; j < n; ++j)
-            if ((bufs[i].out || bufs[j].out) && cc_overlap(bufs[i].p, bufs[i].bytes, bufs[j].p, bufs[j].bytes)) return true;
-    return false;
-}
-
 // sizes every entry point and the query share; 0 = fine, else the code with the message set (fn == NULL: silent, for the query)
 static int cc_check_sizes(const char* fn, int N, int Z, int H, int W, int C) {
     if (N <= 0 || Z <= 0 || H <= 0 || W <= 0) {
@@ -592,16 +560,10 @@ static int cc_check_sizes(const char* fn, int N, int Z, int H, int W, int C) {
 }
 
 // ndim and the class ids; fills cls
-static int cc_check_classes(const char* fn, const int* classes, int C, int ndim, CcClasses* cls) {
+static int cc_check_classes(const char* fn, const int* classes, int C, int ndim, AesrClasses* cls) {
     AESR_CHECK_ARG(classes, "%s: a null pointer", fn);
     AESR_CHECK_ARG(ndim == 2 || ndim == 3, "%s: ndim=%d, 2 or 3 are supported", fn, ndim);
-    for (int c = 0; c < CC_MAXC; ++c) cls->v[c] = 0.f;
-    for (int c = 0; c < C; ++c) {
-        AESR_CHECK_ARG(classes[c] >= -(1 << 24) && classes[c] <= (1 << 24), "%s: class id %d is not exact in fp32", fn, classes[c]);
-        for (int d = 0; d < c; ++d) AESR_CHECK_ARG(classes[d] != classes[c], "%s: class id %d is listed twice", fn, classes[c]);
-        cls->v[c] = (float)classes[c];
-    }
-    return AESR_OK;
+    return aesr_fill_classes(fn, classes, C, cls);
 }
 
 // the host copy of n_components: 0 = fine with *rows = their sum
@@ -640,16 +602,16 @@ int aesr_components_label(const float* vol, int* labels, int* n_components, void
     AESR_CHECK_ARG((uintptr_t)vol % 4 == 0 && (uintptr_t)labels % 4 == 0 && (uintptr_t)n_components % 4 == 0,
                    "%s: vol, labels or n_components is not 4-byte aligned", fn);
     AESR_CHECK_ARG((uintptr_t)workspace % 16 == 0, "%s: workspace is not 16-byte aligned", fn);
-    CcClasses cls;
+    AesrClasses cls;
     rc = cc_check_classes(fn, classes, C, ndim, &cls);
     if (rc != AESR_OK) return rc;
     AESR_CHECK_ARG(connectivity >= 1 && connectivity <= ndim, "%s: connectivity=%d must be in 1 ... ndim = %d", fn, connectivity, ndim);
     const CcLayout L = cc_layout(N, Z, H, W, C);
     const int U = ndim == 2 ? N * Z : N;
     const int Vu = ndim == 2 ? H * W : Z * H * W;
-    const CcBuf bufs[4] = {{vol, (size_t)L.T * 4, false}, {labels, (size_t)L.T * 4, true}, {n_components, (size_t)U * C * 4, true},
+    const AesrBuf bufs[4] = {{vol, (size_t)L.T * 4, false}, {labels, (size_t)L.T * 4, true}, {n_components, (size_t)U * C * 4, true},
                            {workspace, L.total, true}};
-    if (cc_any_overlap(bufs, 4)) {
+    if (aesr_any_overlap(bufs, 4)) {
         aesr_set_error("%s: an output or the workspace overlaps an input or another output", fn);
         return AESR_ERR_UNSUPPORTED;
     }
@@ -696,7 +658,7 @@ int aesr_components_tables(const float* vol, const int* labels, const int* n_com
                    "%s: vol, labels or n_components is not 4-byte aligned", fn);
     AESR_CHECK_ARG((uintptr_t)workspace % 16 == 0, "%s: workspace is not 16-byte aligned", fn);
     AESR_CHECK_ARG((uintptr_t)table % 8 == 0, "%s: table is not 8-byte aligned", fn);
-    CcClasses cls;
+    AesrClasses cls;
     rc = cc_check_classes(fn, classes, C, ndim, &cls);
     if (rc != AESR_OK) return rc;
     const CcLayout L = cc_layout(N, Z, H, W, C);
@@ -707,9 +669,9 @@ int aesr_components_tables(const float* vol, const int* labels, const int* n_com
     if (rc != AESR_OK) return rc;
     AESR_CHECK_ARG(rows <= capacity, "%s: the table has %llu rows, the buffer only %zu", fn, rows, capacity);
     AESR_CHECK_ARG(table || rows == 0, "%s: table is a null pointer", fn);
-    const CcBuf bufs[5] = {{vol, (size_t)L.T * 4, false}, {labels, (size_t)L.T * 4, false}, {n_components, (size_t)U * C * 4, false},
+    const AesrBuf bufs[5] = {{vol, (size_t)L.T * 4, false}, {labels, (size_t)L.T * 4, false}, {n_components, (size_t)U * C * 4, false},
                            {workspace, L.total, true}, {table, capacity * CC_COLS * 8, true}};
-    if (cc_any_overlap(bufs, 5)) {
+    if (aesr_any_overlap(bufs, 5)) {
         aesr_set_error("%s: an output or the workspace overlaps an input or another output", fn);
         return AESR_ERR_UNSUPPORTED;
     }
@@ -739,7 +701,7 @@ int aesr_components_apply_table(const float* vol, const int* labels, const int* 
                        (uintptr_t)out % 4 == 0,
                    "%s: vol, labels, n_components, table or out is not 4-byte aligned", fn);
     AESR_CHECK_ARG((uintptr_t)workspace % 16 == 0, "%s: workspace is not 16-byte aligned", fn);
-    CcClasses cls;
+    AesrClasses cls;
     rc = cc_check_classes(fn, classes, C, ndim, &cls);
     if (rc != AESR_OK) return rc;
     const CcLayout L = cc_layout(N, Z, H, W, C);
@@ -750,9 +712,9 @@ int aesr_components_apply_table(const float* vol, const int* labels, const int* 
     if (rc != AESR_OK) return rc;
     AESR_CHECK_ARG(rows <= table_len, "%s: the components need %llu table entries, the table has only %zu", fn, rows, table_len);
     AESR_CHECK_ARG(table || rows == 0, "%s: table is a null pointer", fn);
-    const CcBuf bufs[6] = {{vol, (size_t)L.T * 4, false}, {labels, (size_t)L.T * 4, false}, {n_components, (size_t)U * C * 4, false},
+    const AesrBuf bufs[6] = {{vol, (size_t)L.T * 4, false}, {labels, (size_t)L.T * 4, false}, {n_components, (size_t)U * C * 4, false},
                            {table, table_len * 4, false}, {workspace, L.total, true}, {out, (size_t)L.T * 4, true}};
-    if (cc_any_overlap(bufs, 6)) {
+    if (aesr_any_overlap(bufs, 6)) {
         aesr_set_error("%s: an output or the workspace overlaps an input or another output", fn);
         return AESR_ERR_UNSUPPORTED;
     }
@@ -769,7 +731,7 @@ int aesr_components_apply_table(const float* vol, const int* labels, const int* 
 
 // the checks the two overlap entry points share
 static int cc_check_overlap_args(const char* fn, const float* vol_a, const int* labels_a, const float* vol_b, const int* labels_b,
-                                 void* workspace, int N, int Z, int H, int W, const int* classes, int C, int ndim, CcClasses* cls) {
+                                 void* workspace, int N, int Z, int H, int W, const int* classes, int C, int ndim, AesrClasses* cls) {
     int rc = cc_check_sizes(fn, N, Z, H, W, C);
     if (rc != AESR_OK) return rc;
     AESR_CHECK_ARG(vol_a && labels_a && vol_b && labels_b && workspace, "%s: a null pointer", fn);
@@ -782,16 +744,16 @@ static int cc_check_overlap_args(const char* fn, const float* vol_a, const int* 
 int aesr_components_overlap_count(const float* vol_a, const int* labels_a, const float* vol_b, const int* labels_b, void* workspace,
                                   long long* count, int N, int Z, int H, int W, const int* classes, int C, int ndim, void* stream) {
     const char* fn = "aesr_components_overlap_count";
-    CcClasses cls;
+    AesrClasses cls;
     const int rc = cc_check_overlap_args(fn, vol_a, labels_a, vol_b, labels_b, workspace, N, Z, H, W, classes, C, ndim, &cls);
     if (rc != AESR_OK) return rc;
     AESR_CHECK_ARG(count, "%s: a null pointer", fn);
     AESR_CHECK_ARG((uintptr_t)count % 8 == 0, "%s: count is not 8-byte aligned", fn);
     const CcLayout L = cc_layout(N, Z, H, W, C);
     const size_t vb = (size_t)L.T * 4;
-    const CcBuf bufs[6] = {{vol_a, vb, false}, {labels_a, vb, false}, {vol_b, vb, false}, {labels_b, vb, false}, {workspace, L.total, true},
+    const AesrBuf bufs[6] = {{vol_a, vb, false}, {labels_a, vb, false}, {vol_b, vb, false}, {labels_b, vb, false}, {workspace, L.total, true},
                            {count, 8, true}};
-    if (cc_any_overlap(bufs, 6)) {
+    if (aesr_any_overlap(bufs, 6)) {
         aesr_set_error("%s: an output or the workspace overlaps an input or another output", fn);
         return AESR_ERR_UNSUPPORTED;
     }
@@ -811,7 +773,7 @@ int aesr_components_overlap_runs(const float* vol_a, const int* labels_a, const 
                                  long long count_host, int* runs, size_t capacity, int N, int Z, int H, int W, const int* classes, int C,
                                  int ndim, void* stream) {
     const char* fn = "aesr_components_overlap_runs";
-    CcClasses cls;
+    AesrClasses cls;
     const int rc = cc_check_overlap_args(fn, vol_a, labels_a, vol_b, labels_b, workspace, N, Z, H, W, classes, C, ndim, &cls);
     if (rc != AESR_OK) return rc;
     AESR_CHECK_ARG((uintptr_t)runs % 4 == 0, "%s: runs is not 4-byte aligned", fn);
@@ -821,9 +783,9 @@ int aesr_components_overlap_runs(const float* vol_a, const int* labels_a, const 
     AESR_CHECK_ARG((unsigned long long)count_host <= capacity, "%s: there are %lld runs, the buffer holds only %zu", fn, count_host, capacity);
     AESR_CHECK_ARG(runs || count_host == 0, "%s: runs is a null pointer", fn);
     const size_t vb = (size_t)L.T * 4;
-    const CcBuf bufs[6] = {{vol_a, vb, false}, {labels_a, vb, false}, {vol_b, vb, false}, {labels_b, vb, false}, {workspace, L.total, false},
+    const AesrBuf bufs[6] = {{vol_a, vb, false}, {labels_a, vb, false}, {vol_b, vb, false}, {labels_b, vb, false}, {workspace, L.total, false},
                            {runs, capacity * 16, true}};
-    if (cc_any_overlap(bufs, 6)) {
+    if (aesr_any_overlap(bufs, 6)) {
         aesr_set_error("%s: the output overlaps an input or the workspace", fn);
         return AESR_ERR_UNSUPPORTED;
     }

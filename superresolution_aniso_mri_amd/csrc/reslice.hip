@@ -18,6 +18,7 @@
 
 #include "../../include/aesr_hip_reslice.h"
 #include "aesr_kernels.h"
+#include "aesr_hostcheck.h"
 
 #pragma clang fp contract(off)
 
@@ -121,11 +122,6 @@ __global__ __launch_bounds__(RSL_THREADS) void reslice_kernel(const float* __res
     }
 }
 
-static bool rsl_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 // the checks the two entry points share; `fn` is the entry point's name in the message
 static int rsl_check(const char* fn, const float* src, const float* out, int N, int Zs, int Hs, int Ws, int Zo, int Ho, int Wo, int interp) {
     AESR_CHECK_ARG(src, "%s: src is a null pointer", fn);
@@ -138,7 +134,7 @@ static int rsl_check(const char* fn, const float* src, const float* out, int N, 
     AESR_CHECK_ARG(interp == AESR_RESLICE_NEAREST || interp == AESR_RESLICE_LINEAR, "%s: interp=%d is neither 0 (nearest) nor 1 (linear)", fn, interp);
     AESR_CHECK_ARG((double)N * Zs * Hs * Ws < 2147483648.0, "%s: N * Zs * Hs * Ws = %d x %d x %d x %d has 2^31 elements or more", fn, N, Zs, Hs, Ws);
     AESR_CHECK_ARG((double)N * Zo * Ho * Wo < 2147483648.0, "%s: N * Zo * Ho * Wo = %d x %d x %d x %d has 2^31 elements or more", fn, N, Zo, Ho, Wo);
-    if (rsl_overlap(out, (size_t)4 * N * Zo * Ho * Wo, src, (size_t)4 * N * Zs * Hs * Ws)) {
+    if (aesr_overlap(out, (size_t)4 * N * Zo * Ho * Wo, src, (size_t)4 * N * Zs * Hs * Ws)) {
         aesr_set_error("%s: out overlaps src", fn);
         return AESR_ERR_UNSUPPORTED;
     }
@@ -182,7 +178,7 @@ int aesr_reslice_grid(const float* src, const float* grid, float* out, int N, in
     AESR_CHECK_ARG((uintptr_t)grid % 4 == 0, "aesr_reslice_grid: grid is not 4-byte aligned");
     const int rc = rsl_check("aesr_reslice_grid", src, out, N, Zs, Hs, Ws, Zo, Ho, Wo, interp);
     if (rc != AESR_OK) return rc;
-    if (rsl_overlap(out, (size_t)4 * N * Zo * Ho * Wo, grid, (size_t)12 * Zo * Ho * Wo)) {
+    if (aesr_overlap(out, (size_t)4 * N * Zo * Ho * Wo, grid, (size_t)12 * Zo * Ho * Wo)) {
         aesr_set_error("aesr_reslice_grid: out overlaps grid");
         return AESR_ERR_UNSUPPORTED;
     }

@@ -11,6 +11,7 @@
 // 4-byte accesses with the same arithmetic, so values never depend on a pointer's alignment.  No atomics: which pixel a thread takes and
 // the order of every sum are fixed by (H, W, K) alone, so two runs give the same bits.
 #include "aesr_kernels.h"
+#include "aesr_hostcheck.h"
 #include "../../include/aesr_hip_seg.h"
 
 #define SEG_THREADS 256
@@ -193,11 +194,6 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_bwd_kernel(const float* __res
 
 static inline int seg_blocks_per_sample(int H, int W) { return ceil_div(H * W, SEG_PPB); }
 
-static bool seg_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 // the checks the launch entry points share; `fn` is the entry point's name in the message
 static int seg_check(const char* fn, int N, int H, int W, int K) {
     AESR_CHECK_ARG(N > 0 && H > 0 && W > 0, "%s: N, H, W = %d, %d, %d must all be positive", fn, N, H, W);
@@ -248,9 +244,9 @@ int aesr_softmax_dice_fwd(const float* logits, const float* labels, size_t label
         AESR_CHECK_ARG((double)(N - 1) * (double)label_stride + HW < 2147483648.0, "aesr_softmax_dice_fwd: the labels span 2^31 elements or more");
     }
     const size_t lab_bytes = labels ? 4 * ((size_t)(N - 1) * label_stride + HW) : 0;
-    if (seg_overlap(probs, bytes, logits, bytes) || seg_overlap(probs, bytes, labels, lab_bytes) ||
-        seg_overlap(argmax, (size_t)4 * N * HW, logits, bytes) || seg_overlap(argmax, (size_t)4 * N * HW, labels, lab_bytes) ||
-        seg_overlap(argmax, (size_t)4 * N * HW, probs, bytes)) {
+    if (aesr_overlap(probs, bytes, logits, bytes) || aesr_overlap(probs, bytes, labels, lab_bytes) ||
+        aesr_overlap(argmax, (size_t)4 * N * HW, logits, bytes) || aesr_overlap(argmax, (size_t)4 * N * HW, labels, lab_bytes) ||
+        aesr_overlap(argmax, (size_t)4 * N * HW, probs, bytes)) {
         aesr_set_error("aesr_softmax_dice_fwd: an output overlaps an input or another output");
         return AESR_ERR_UNSUPPORTED;
     }
@@ -278,8 +274,8 @@ int aesr_softmax_dice_bwd(const float* probs, const float* labels, size_t label_
     AESR_CHECK_ARG(label_stride >= (size_t)HW || N == 1, "aesr_softmax_dice_bwd: label_stride=%zu is smaller than H * W = %d", label_stride, HW);
     AESR_CHECK_ARG((double)(N - 1) * (double)label_stride + HW < 2147483648.0, "aesr_softmax_dice_bwd: the labels span 2^31 elements or more");
     const size_t bytes = (size_t)4 * N * HW * K;
-    if (seg_overlap(dlogits, bytes, probs, bytes) || seg_overlap(dlogits, bytes, labels, 4 * ((size_t)(N - 1) * label_stride + HW)) ||
-        seg_overlap(dlogits, bytes, sums, (size_t)8 * N * 3 * K) || seg_overlap(dlogits, bytes, gloss, 4)) {
+    if (aesr_overlap(dlogits, bytes, probs, bytes) || aesr_overlap(dlogits, bytes, labels, 4 * ((size_t)(N - 1) * label_stride + HW)) ||
+        aesr_overlap(dlogits, bytes, sums, (size_t)8 * N * 3 * K) || aesr_overlap(dlogits, bytes, gloss, 4)) {
         aesr_set_error("aesr_softmax_dice_bwd: dlogits overlaps an input");
         return AESR_ERR_UNSUPPORTED;
     }

@@ -20,6 +20,7 @@
 // No floating-point atomics, no buffer that needs initialisation; which thread takes which voxel and the order of every sum depend on the
 // sizes alone, so two runs give the same bits.  -ffp-contract=off (Makefile) keeps a*a + b from becoming an fma.
 #include "aesr_kernels.h"
+#include "aesr_hostcheck.h"
 #include "../../include/aesr_hip_surface.h"
 
 #include <cmath>
@@ -36,18 +37,12 @@
 #define SURF_YCHUNK 256                             // column rows staged at a time: 256 * 16 * 8 B = 32 KB
 #define SURF_SCAN_THREADS 1024
 
-struct SurfClasses {
-    float v[SURF_MAXC];
-};
-
 // byte offsets of the workspace sections, all multiples of 16
 struct SurfLayout {
     size_t my, list_tab, gx, partial, block_off, flags, total;
     long long V, Vp;
     int nb;
 };
-
-static inline size_t surf_up16(size_t v) { return (v + 15) / 16 * 16; }
 
 static SurfLayout surf_layout(int N, int Z, int H, int W, int C) {
     SurfLayout L;
@@ -56,22 +51,14 @@ static SurfLayout surf_layout(int N, int Z, int H, int W, int C) {
     L.nb = (int)((L.V + SURF_VPB - 1) / SURF_VPB);
     const size_t lists = (size_t)N * C * 2;
     size_t o = 0;
-    L.my = o;          o += surf_up16(lists * (size_t)L.V * 8);
-    L.list_tab = o;    o += surf_up16(lists * 2 * 8);
-    L.gx = o;          o += surf_up16(lists * (size_t)L.V * 4);
-    L.partial = o;     o += surf_up16((size_t)N * L.nb * C * SURF_NQ * 4);
-    L.block_off = o;   o += surf_up16(lists * (size_t)L.nb * 4);
-    L.flags = o;       o += surf_up16((size_t)N * 2 * (size_t)L.Vp);
+    L.my = o;          o += aesr_up16(lists * (size_t)L.V * 8);
+    L.list_tab = o;    o += aesr_up16(lists * 2 * 8);
+    L.gx = o;          o += aesr_up16(lists * (size_t)L.V * 4);
+    L.partial = o;     o += aesr_up16((size_t)N * L.nb * C * SURF_NQ * 4);
+    L.block_off = o;   o += aesr_up16(lists * (size_t)L.nb * 4);
+    L.flags = o;       o += aesr_up16((size_t)N * 2 * (size_t)L.Vp);
     L.total = o;
     return L;
-}
-
-__device__ __forceinline__ int surf_class_of(float v, const SurfClasses& cls, int C) {
-    int k = -1;
-#pragma unroll
-    for (int c = 0; c < SURF_MAXC; ++c)
-        if (c < C && v == cls.v[c]) k = c;          // NaN equals nothing; ids are distinct, so at most one hit
-    return k;
 }
 
 // true when voxel (z, y, x) of mask (vol == v) has a neighbour that is not in the mask; outside the array counts as not in it
@@ -93,7 +80,7 @@ __device__ __forceinline__ bool surf_is_border(const float* __restrict__ vol, fl
 template <bool VEC>
 __global__ __launch_bounds__(SURF_THREADS) void surf_classify_kernel(const float* __restrict__ result, const float* __restrict__ reference,
                                                                      unsigned int* __restrict__ flags, unsigned int* __restrict__ partial,
-                                                                     SurfClasses cls, int C, int V, int Vp, int Z, int H, int W, int nb,
+                                                                     AesrClasses cls, int C, int V, int Vp, int Z, int H, int W, int nb,
                                                                      int zr, int conn) {
     __shared__ unsigned int red[SURF_THREADS / 64][SURF_MAXC * SURF_NQ];
     const int n = blockIdx.x / nb, b = blockIdx.x - n * nb;
@@ -126,8 +113,8 @@ __global__ __launch_bounds__(SURF_THREADS) void surf_classify_kernel(const float
         bA[j] = bB[j] = false;
         if (idx < V) {
             const int z = idx / HW, rem = idx - z * HW, y = rem / W, x = rem - y * W;
-            kA[j] = surf_class_of(a[j], cls, C);
-            kB[j] = surf_class_of(g[j], cls, C);
+            kA[j] = aesr_class_of(a[j], cls, C);
+            kB[j] = aesr_class_of(g[j], cls, C);
             if (kA[j] >= 0) bA[j] = surf_is_border(rv, a[j], z, y, x, Z, H, W, zr, conn);
             if (kB[j] >= 0) bB[j] = surf_is_border(gv, g[j], z, y, x, Z, H, W, zr, conn);
             if (bA[j]) wordA |= (unsigned int)(kA[j] + 1) << (8 * j);
@@ -430,11 +417,6 @@ __global__ __launch_bounds__(SURF_THREADS) void surf_reduce_kernel(const double*
     }
 }
 
-static bool surf_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a_bytes && b_bytes && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 // sizes both launch entry points and the query share; 0 = fine, else the code with the message set (fn == NULL: silent, for the query)
 static int surf_check_sizes(const char* fn, int N, int Z, int H, int W, int C) {
     if (N <= 0 || Z <= 0 || H <= 0 || W <= 0) {
@@ -478,18 +460,13 @@ int aesr_surface_borders(const float* result, const float* reference, void* work
     AESR_CHECK_ARG((uintptr_t)counts % 8 == 0, "%s: counts is not 8-byte aligned", fn);
     AESR_CHECK_ARG(ndim == 2 || ndim == 3, "%s: ndim=%d, 2 or 3 are supported", fn, ndim);
     AESR_CHECK_ARG(connectivity >= 1 && connectivity <= ndim, "%s: connectivity=%d must be in 1 ... ndim = %d", fn, connectivity, ndim);
-    SurfClasses cls;
-    for (int c = 0; c < SURF_MAXC; ++c) cls.v[c] = 0.f;
-    for (int c = 0; c < C; ++c) {
-        AESR_CHECK_ARG(classes[c] >= -(1 << 24) && classes[c] <= (1 << 24), "%s: class id %d is not exact in fp32", fn, classes[c]);
-        for (int d = 0; d < c; ++d) AESR_CHECK_ARG(classes[d] != classes[c], "%s: class id %d is listed twice", fn, classes[c]);
-        cls.v[c] = (float)classes[c];
-    }
+    AesrClasses cls;
+    const int rc_cls = aesr_fill_classes(fn, classes, C, &cls);
+    if (rc_cls != AESR_OK) return rc_cls;
     const SurfLayout L = surf_layout(N, Z, H, W, C);
     const size_t vol_bytes = (size_t)N * (size_t)L.V * 4, cnt_bytes = (size_t)N * C * AESR_SURFACE_COUNTS * 8;
-    if (surf_overlap(workspace, L.total, result, vol_bytes) || surf_overlap(workspace, L.total, reference, vol_bytes) ||
-        surf_overlap(counts, cnt_bytes, result, vol_bytes) || surf_overlap(counts, cnt_bytes, reference, vol_bytes) ||
-        surf_overlap(counts, cnt_bytes, workspace, L.total)) {
+    const AesrBuf bufs[4] = {{result, vol_bytes, false}, {reference, vol_bytes, false}, {workspace, L.total, true}, {counts, cnt_bytes, true}};
+    if (aesr_any_overlap(bufs, 4)) {
         aesr_set_error("%s: an output or the workspace overlaps an input or another output", fn);
         return AESR_ERR_UNSUPPORTED;
     }
@@ -539,9 +516,9 @@ int aesr_surface_distances(void* workspace, const long long* counts, const long 
     AESR_CHECK_ARG(need <= capacity, "%s: the lists hold %llu distances, the buffer only %zu", fn, need, capacity);
     AESR_CHECK_ARG(distances || need == 0, "%s: distances is a null pointer", fn);
     const size_t cnt_bytes = (size_t)N * C * AESR_SURFACE_COUNTS * 8, st_bytes = (size_t)N * C * 4 * 8, d_bytes = capacity * 8;
-    if (surf_overlap(distances, d_bytes, workspace, L.total) || surf_overlap(distances, d_bytes, counts, cnt_bytes) ||
-        surf_overlap(stats, st_bytes, workspace, L.total) || surf_overlap(stats, st_bytes, counts, cnt_bytes) ||
-        surf_overlap(stats, st_bytes, distances, d_bytes) || surf_overlap(counts, cnt_bytes, workspace, L.total)) {
+    // counts is only read: it is checked against the three buffers that are written, which is every pair of the four
+    const AesrBuf bufs[4] = {{counts, cnt_bytes, false}, {workspace, L.total, true}, {distances, d_bytes, true}, {stats, st_bytes, true}};
+    if (aesr_any_overlap(bufs, 4)) {
         aesr_set_error("%s: an output overlaps an input, the workspace or another output", fn);
         return AESR_ERR_UNSUPPORTED;
     }

@@ -1,62 +1,9 @@
-"""No GPU: the BatchNorm + AvgPool2d(2) pool-once header of libaesr_hip.so (include/aesr_hip_bnpool.h, ``_hip.SIGNATURES_BNPOOL``).
+"""No GPU: the entry points of include/aesr_hip_bnpool.h (BatchNorm + AvgPool2d(2) pooled once) on the host; tests/test_abi.py checks the
+header against ``_hip.SIGNATURES_BNPOOL``.
 
-- the header == the table == the library's exports, with the argument types as bound; disjoint from every other header and table;
-- ``GUARDED_ENTRIES`` and ``EXEMPT`` of tests/test_gpu_bn_pool.py partition the table, and only the ``_supported`` query is exempt;
 - ``aesr_bn_pool_supported`` on both sides of each of its limits;
 - argument refusals come before anything touches the device: non-zero, the function's name in the message."""
 import ctypes
-import glob
-import os
-import re
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = {"aesr_bn_pool_supported", "aesr_bn_pool_stats_finalize", "aesr_bn_pool_apply", "aesr_bn_pool_bwd"}
-
-
-def _declared(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return set(re.findall(r"\b(aesr_[a-z0-9_]+)\s*\(", hdr))
-
-
-def test_header_table_and_exports_agree():
-    from superresolution_aniso_mri_amd import _hip
-    declared = _declared("aesr_hip_bnpool.h")
-    assert declared == set(_hip.SIGNATURES_BNPOOL) == NAMES
-    others = set()
-    tables = [k for k in vars(_hip) if k.startswith("SIGNATURES") and k != "SIGNATURES_BNPOOL"]
-    assert len(tables) >= 8
-    for k in tables:
-        others |= set(getattr(_hip, k))
-    headers = [os.path.basename(h) for h in glob.glob(os.path.join(ROOT, "include", "*.h")) if not h.endswith("aesr_hip_bnpool.h")]
-    assert len(headers) >= 8
-    for h in headers:
-        others |= _declared(h)
-    assert not declared & others
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    for name in declared:
-        assert getattr(lib, name, None) is not None, "%s is declared in include/aesr_hip_bnpool.h but not exported" % name
-        res, args = _hip.SIGNATURES_BNPOOL[name]
-        assert getattr(_hip.lib, name).argtypes == args and getattr(_hip.lib, name).restype == res
-    # the C declarations, argument by argument
-    P, I, F, IP, DP = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, _hip.IP, _hip.DP
-    assert _hip.SIGNATURES_BNPOOL["aesr_bn_pool_supported"] == (I, [I] * 5)
-    assert _hip.SIGNATURES_BNPOOL["aesr_bn_pool_stats_finalize"] == (I, [P, P, P, DP] + [P] * 9 + [I] * 5 + [IP, F, F, I, P])
-    assert _hip.SIGNATURES_BNPOOL["aesr_bn_pool_apply"] == (I, [P] * 4 + [I] * 5 + [IP, P])
-    assert _hip.SIGNATURES_BNPOOL["aesr_bn_pool_bwd"] == (I, [P] * 7 + [DP] + [P] * 4 + [I] * 5 + [F, I, IP, P])
-
-
-def test_guard_band_cases_and_exemptions_partition_the_bnpool_abi():
-    """The rule of tests/test_memguard_host.py::test_case_table_and_exemptions_partition_the_abi for this table."""
-    import test_gpu_bn_pool as tg
-    from superresolution_aniso_mri_amd import _hip
-    covered, exempt, names = set(tg.GUARDED_ENTRIES), set(tg.EXEMPT), set(_hip.SIGNATURES_BNPOOL)
-    assert not (covered & exempt) and covered | exempt == names, (sorted(names - covered - exempt), sorted((covered | exempt) - names))
-    for name, reason in tg.EXEMPT.items():
-        assert reason and name.endswith("_supported"), "%s is a launch entry point: it needs a case, not an exemption" % name
-    assert exempt == {"aesr_bn_pool_supported"}
-    assert callable(tg.test_guard_bands_poisons_and_offset_pointers) and callable(tg.test_refusals_write_nothing)
-    assert set(tg.GUARD_CASES) <= set(tg.CASES)
 
 
 def test_supported_on_both_sides_of_each_limit():

@@ -6,19 +6,15 @@ from datasets/common_brains.py, OASIS/dataset.py, dHCP/dataset.py and shared_tra
   ``z_step = 1`` and for ``[::k]``.  It shares no code with the package; the kernel is held to it and to the fixture on the GPU.
 - ``BrainSampler`` reproduces every slice id and coefficient the reference's datasets drew, ``BrainTripletAugmenter.draw_transform`` every
   number its transforms drew (two RandomStates, two seeds); ``adjacent`` raises the documented ``ValueError``.
-- include/aesr_hip_dataprep.h == ``_hip.SIGNATURES_DATAPREP`` == the library's exports, disjoint from the other two headers and tables,
-  and partitioned by GUARDED_ENTRIES / EXEMPT of tests/test_gpu_brain.py.
 - Every refusal of ``aesr_thick_slices`` returns its code before anything touches the device: callable without a GPU.
 - ``get_file_suffix_blurred`` and ``determine_interpol_coefficients`` against recorded values."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 STEPS = (2, 3, 5, 6)            # z_step values every case is run with: 39, 36, 40, 2, 1, 0, 8 = Z - 1 of the cases; 5 and 6 exceed Z = 3, 2, 1
 # (set, leg) -> the augmenter that mirrors the reference's dataset + transform of that leg: dataset, width, aug_patch_size, downsample_steps
 LEGS = {("oasis", "crop"): ("OASIS", 200, 220, 3), ("oasis", "nocrop"): ("OASIS", 220, 220, 3), ("oasis", "test"): ("OASIS", 220, 220, 3),
@@ -193,37 +189,6 @@ def test_augmenter_refuses_what_the_transforms_cannot_do():
 
 
 # ---- the third header --------------------------------------------------------------------------------------------------------------
-def _declared(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return set(re.findall(r"\b(aesr_[a-z0-9_]+)\s*\(", hdr))
-
-
-def test_dataprep_header_table_and_exports_agree():
-    from superresolution_aniso_mri_amd import _hip
-    declared = _declared("aesr_hip_dataprep.h")
-    assert declared == set(_hip.SIGNATURES_DATAPREP) == {"aesr_thick_slices", "aesr_thick_slices_out_slices", "aesr_thick_slices_store_bytes",
-                                                               "aesr_triplet_assemble_raw"}
-    others = set(_hip.SIGNATURES) | set(_hip.SIGNATURES_PREPROC) | _declared("aesr_hip.h") | _declared("aesr_hip_preproc.h")
-    assert not declared & others
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    for name in declared:
-        assert getattr(lib, name, None) is not None, "%s is declared in include/aesr_hip_dataprep.h but not exported" % name
-        assert getattr(_hip.lib, name).argtypes == _hip.SIGNATURES_DATAPREP[name][1]
-
-
-def test_guard_band_cases_and_exemptions_partition_the_dataprep_abi():
-    """The rule of tests/test_memguard_host.py::test_case_table_and_exemptions_partition_the_abi for the third table."""
-    import test_gpu_brain as tg
-    from superresolution_aniso_mri_amd import _hip
-    covered, exempt, names = set(tg.GUARDED_ENTRIES), set(tg.EXEMPT), set(_hip.SIGNATURES_DATAPREP)
-    assert not (covered & exempt) and covered | exempt == names, (sorted(names - covered - exempt), sorted((covered | exempt) - names))
-    for name, reason in tg.EXEMPT.items():
-        assert reason and name.endswith(("_slices", "_size", "_bytes")), "%s is a launch entry point: it needs a case, not an exemption" % name
-    assert covered == {"aesr_thick_slices", "aesr_triplet_assemble_raw"}
-    assert callable(tg.test_thick_slices_guard_bands_poisons_and_offset_pointers) and callable(tg.test_assemble_raw_guard_bands_and_poisons)
-
-
 def test_out_slices_is_ceil():
     from superresolution_aniso_mri_amd import _hip
     f = _hip.lib.aesr_thick_slices_out_slices

@@ -5,12 +5,10 @@ kwatsch/medpy_metrics.py (tests/make_golden_components.py -> tests/golden/compon
   reference every device test of csrc/components.hip compares against -- reproduces the fixture's labels, counts, boxes and sizes exactly;
 - the restated overlap-run rule yields exactly the pair set of a brute-force np.unique over voxel pairs;
 - ``evaluate.object_metrics.correspondences`` reproduces every stored mapping and every stored obj_tpr / obj_fpr;
-- include/aesr_hip_components.h == ``_hip.SIGNATURES_COMPONENTS`` == the library's exports, disjoint from the other ten tables;
-- every refusal of the entry points comes back on the host; the workspace query's values; the guarded / exempt partition;
+- every refusal of the entry points comes back on the host; the workspace query's values;
 - the no-CPU-fallback error; ``kwatsch.medpy_metrics.obj_tpr`` still raises."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -18,10 +16,6 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "components.npz")
-COMPONENTS_NAMES = {"aesr_components_workspace_bytes", "aesr_components_label", "aesr_components_tables", "aesr_components_overlap_count",
-                    "aesr_components_overlap_runs", "aesr_components_apply_table"}
-OTHER_HEADERS = ("aesr_hip.h", "aesr_hip_preproc.h", "aesr_hip_dataprep.h", "aesr_hip_train.h", "aesr_hip_baselines.h", "aesr_hip_reslice.h",
-                 "aesr_hip_seg.h", "aesr_hip_surface.h", "aesr_hip_bnpool.h", "aesr_hip_labelprep.h")
 LABEL_CASES = ["ties", "multiwg", "serpentine", "helix", "comb_last", "comb_first", "checker", "diagonal", "eight", "slices6", "img2d", "z1",
                "full", "faces", "tie"]
 SCORE_CASES = ["aniso_a", "aniso_b", "aniso_k2", "aniso_k3", "iso", "flat_a", "flat_k2", "classes3", "frames", "apart", "empty"]
@@ -276,53 +270,6 @@ def test_correspondences_reproduce_the_reference_mappings(name):
 
 
 # ---- the eleventh header ----------------------------------------------------------------------------------------------------------------
-def _declared(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return set(re.findall(r"\b(aesr_[a-z0-9_]+)\s*\(", hdr))
-
-
-def test_components_header_table_and_exports_agree():
-    from superresolution_aniso_mri_amd import _hip
-    declared = _declared("aesr_hip_components.h")
-    assert declared == set(_hip.SIGNATURES_COMPONENTS) == COMPONENTS_NAMES
-    others = (set(_hip.SIGNATURES) | set(_hip.SIGNATURES_PREPROC) | set(_hip.SIGNATURES_DATAPREP) | set(_hip.SIGNATURES_TRAIN)
-              | set(_hip.SIGNATURES_BASELINES) | set(_hip.SIGNATURES_RESLICE) | set(_hip.SIGNATURES_SEG) | set(_hip.SIGNATURES_SURFACE)
-              | set(_hip.SIGNATURES_BNPOOL) | set(_hip.SIGNATURES_LABELPREP))
-    assert all(os.path.isfile(os.path.join(ROOT, "include", h)) for h in OTHER_HEADERS)
-    for header in OTHER_HEADERS:
-        others |= _declared(header)
-    assert not declared & others
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    for name in declared:
-        assert getattr(lib, name, None) is not None, "%s is declared in include/aesr_hip_components.h but not exported" % name
-        res, args = _hip.SIGNATURES_COMPONENTS[name]
-        assert getattr(_hip.lib, name).argtypes == args and getattr(_hip.lib, name).restype == res
-    P, I, S, IP, LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, _hip.IP, ctypes.c_longlong
-    sig = _hip.SIGNATURES_COMPONENTS
-    assert sig["aesr_components_workspace_bytes"] == (S, [I] * 5)
-    assert sig["aesr_components_label"] == (I, [P, P, P, P, I, I, I, I, IP, I, I, I, P])
-    assert sig["aesr_components_tables"] == (I, [P, P, P, IP, P, P, S, I, I, I, I, IP, I, I, P])
-    assert sig["aesr_components_overlap_count"] == (I, [P, P, P, P, P, P, I, I, I, I, IP, I, I, P])
-    assert sig["aesr_components_overlap_runs"] == (I, [P, P, P, P, P, LL, P, S, I, I, I, I, IP, I, I, P])
-    assert sig["aesr_components_apply_table"] == (I, [P, P, P, IP, P, P, S, P, I, I, I, I, IP, I, I, P])
-    # the source and the header are wired into both rules of the build
-    mk = open(os.path.join(ROOT, "superresolution_aniso_mri_amd", "csrc", "Makefile")).read()
-    assert re.search(r"^SRCS = .*\bcomponents\.hip\b", mk, flags=re.M) and mk.count("../../include/aesr_hip_components.h") == 2
-    hdr = open(os.path.join(ROOT, "include", "aesr_hip_components.h")).read()
-    assert (_hip.COMPONENTS_MAX_CLASSES, _hip.COMPONENTS_COLUMNS, _hip.COMPONENTS_MAX_PER_CLASS) == tuple(
-        int(re.search(r"#define AESR_COMPONENTS_%s (\d+)" % k, hdr).group(1)) for k in ("MAX_CLASSES", "COLUMNS", "MAX_PER_CLASS"))
-    assert len(re.findall(r"#define AESR_COMPONENTS_", hdr)) == 3
-
-
-def test_guard_band_cases_and_exemptions_partition_the_components_abi():
-    """The rule of tests/test_memguard_host.py::test_case_table_and_exemptions_partition_the_abi for the eleventh table."""
-    import test_gpu_components as tg
-    covered, exempt = set(tg.GUARDED_ENTRIES), set(tg.EXEMPT)
-    assert not (covered & exempt) and covered | exempt == COMPONENTS_NAMES
-    assert exempt == {"aesr_components_workspace_bytes"} and all(tg.EXEMPT.values())
-
-
 def workspace_bytes_restated(N, Z, H, W, C):
     up = lambda v: (v + 15) // 16 * 16          # noqa: E731
     T = N * Z * H * W

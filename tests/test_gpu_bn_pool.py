@@ -17,7 +17,7 @@ float64 on the CPU.
 - The three launch entry points between the guard bands of tests/memguard.py at their contractual sizes; refusals write nothing.
 - Engine level: one encoder block with ``engine.BN_POOL_ONCE`` off and on, eagerly and as a captured graph.
 
-GUARDED_ENTRIES and EXEMPT partition ``_hip.SIGNATURES_BNPOOL`` (tests/test_bn_pool_abi.py checks that without a GPU)."""
+GUARDED_ENTRIES and EXEMPT partition ``_hip.SIGNATURES_BNPOOL`` (tests/test_abi.py checks that without a GPU)."""
 import ctypes
 import functools
 

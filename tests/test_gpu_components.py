@@ -6,7 +6,7 @@ pair sets a brute force; the clean-up equals its restatement; the object-wise sc
 distances to 1e-12 relative: only the order of the mean's sum differs); two runs give the same bits; guard bands, poisoned workspace and
 outputs and shifted pointers for every guarded entry point; the command lines end to end.
 
-GUARDED_ENTRIES and EXEMPT partition ``_hip.SIGNATURES_COMPONENTS`` (tests/test_components_golden.py checks that without a GPU)."""
+GUARDED_ENTRIES and EXEMPT partition ``_hip.SIGNATURES_COMPONENTS`` (tests/test_abi.py checks that without a GPU)."""
 import os
 
 import numpy as np

@@ -10,7 +10,7 @@ thin_reduce_kernel<false, true> + thin_cout1_finish_kernel) against the three ca
 - Engine level: a decoder-shaped pass and the small trainer fixture with ``engine.FUSE_COUT1_BWD`` off and on, eagerly and in a captured
   step graph: gradients and final state ``torch.equal``.
 
-GUARDED_ENTRIES and EXEMPT partition ``_hip.SIGNATURES_TRAIN`` (tests/test_train_abi.py checks that without a GPU)."""
+GUARDED_ENTRIES and EXEMPT partition ``_hip.SIGNATURES_TRAIN`` (tests/test_abi.py checks that without a GPU)."""
 import ctypes
 import functools
 import os

@@ -6,7 +6,7 @@
 - ``clamp_edges=True`` differs from the fixture only on the dead lines; device tensor in -> device tensor out with the input's bits
   unchanged; a 4-D input is one launch and equals the per-frame calls bitwise.
 - The legs of tests/memguard.py on the C entry point at the contractual buffer sizes (GUARDED_ENTRIES / EXEMPT partition
-  ``_hip.SIGNATURES_PREPROC``; tests/test_inplane_golden.py checks that without a GPU); the unsupported radius is refused with nothing written.
+  ``_hip.SIGNATURES_PREPROC``; tests/test_abi.py checks that without a GPU); the unsupported radius is refused with nothing written.
 - ``generate_hr_volumes --resample`` end to end, the loaders of data_device.py and ``train_aesr --volumes_dir --resample``."""
 import ctypes
 import os

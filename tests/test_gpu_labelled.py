@@ -15,7 +15,7 @@ load_labelled_volume_dir; datasets.common order=0; train_aesr --labels_dir).
 - ``load_labelled_volume_dir`` on .npy and NIfTI pairs with ``resample``.
 - End to end: train both multi-channel trainers from a directory of volumes and one of label maps, generate, score.
 
-GUARDED_ENTRIES and EXEMPT partition ``_hip.SIGNATURES_LABELPREP`` (tests/test_labelled_golden.py checks that without a GPU)."""
+GUARDED_ENTRIES and EXEMPT partition ``_hip.SIGNATURES_LABELPREP`` (tests/test_abi.py checks that without a GPU)."""
 import ctypes
 import os
 

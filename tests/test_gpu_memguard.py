@@ -19,7 +19,7 @@ each on a fresh set of buffers:
 What a green run does NOT say: out-of-range READS are invisible to guard bands (a guard is not changed by a read), and so is a store
 that lands 4 096 elements or more away from its buffer.
 
-The case table and EXEMPT partition _hip.SIGNATURES (tests/test_memguard_host.py checks that without a GPU).
+The case table and EXEMPT partition _hip.SIGNATURES (tests/test_abi.py checks that without a GPU).
 """
 import ctypes
 import types

@@ -1,9 +1,7 @@
 """not-gpu: host-side logic of the drop-in boundary -- C-ABI export table, plugin table, CLI flags, trainer factory,
 checkpoint / settings formats, loss logging, annealing table, batch sharding.  No kernel is launched here."""
-import ctypes
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,15 +12,8 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 def test_cabi_exports_every_declared_symbol():
-    hdr = open(os.path.join(ROOT, "include", "aesr_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(aesr_[a-z0-9_]+)\s*\(", hdr))
-    assert len(declared) >= 30
+    """What the library answers on the host; that header, table and exports agree is checked by tests/test_abi.py."""
     from superresolution_aniso_mri_amd import _hip
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    for name in declared:
-        assert getattr(lib, name, None) is not None, "%s is declared in include/aesr_hip.h but not exported" % name
-    assert declared == set(_hip.SIGNATURES.keys()), declared ^ set(_hip.SIGNATURES.keys())
     assert _hip.lib.aesr_version() == 1
     # argument validation happens on the host before any launch -> callable without a GPU
     assert _hip.lib.aesr_lerp_fwd(None, None, None, None, 1, 4, None) != 0

@@ -6,18 +6,14 @@ tests/make_golden_inplane.py from datasets/common.py:157-206 of the reference).
   fixture case within 1e-7 (6e-8 was measured for such a restatement against scipy, plus the rounding of the last store).  It shares no
   code with the package: the package's host tables are checked against it.
 - The host tables (``datasets.common.zoom_tables``) predict the dead lines of the quirk cases and none elsewhere.
-- include/aesr_hip_preproc.h == ``_hip.SIGNATURES_PREPROC`` == the library's exports, and every launch entry point of that table is the
-  subject of a guard-band case of tests/test_gpu_inplane.py (the partition rule of tests/test_memguard_host.py for the second table).
 - Host-side argument checks of the C entry points, and the CLI's refusal of ``--resample`` on a ``.npy`` volume without ``--spacing``."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 TOL = 1e-7
 QUIRK = {"d_quirk": (True, True), "d_quirk224": (True, True)}      # tag -> (last row dead, last column dead)
 
@@ -148,36 +144,6 @@ def test_gaussian_weights_are_scipys():
         w, r = dc.gaussian_weights(sigma)
         assert r == int(4.0 * sigma + 0.5) and w.shape == (2 * r + 1,)
         assert np.array_equal(w, scipy_filters._gaussian_kernel1d(sigma, 0, r))
-
-
-def _declared(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return set(re.findall(r"\b(aesr_[a-z0-9_]+)\s*\(", hdr))
-
-
-def test_preproc_header_table_and_exports_agree():
-    from superresolution_aniso_mri_amd import _hip
-    declared = _declared("aesr_hip_preproc.h")
-    assert declared == set(_hip.SIGNATURES_PREPROC), declared ^ set(_hip.SIGNATURES_PREPROC)
-    assert not declared & set(_hip.SIGNATURES) and not declared & _declared("aesr_hip.h")
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    for name in declared:
-        assert getattr(lib, name, None) is not None, "%s is declared in include/aesr_hip_preproc.h but not exported" % name
-        assert getattr(_hip.lib, name).argtypes == _hip.SIGNATURES_PREPROC[name][1]
-
-
-def test_guard_band_cases_and_exemptions_partition_the_preproc_abi():
-    """The rule of tests/test_memguard_host.py::test_case_table_and_exemptions_partition_the_abi for the second table: every name is
-    guarded by a case of tests/test_gpu_inplane.py or exempt as a pure host query."""
-    import test_gpu_inplane as tg
-    from superresolution_aniso_mri_amd import _hip
-    covered, exempt, names = set(tg.GUARDED_ENTRIES), set(tg.EXEMPT), set(_hip.SIGNATURES_PREPROC)
-    assert not (covered & exempt) and covered | exempt == names, (sorted(names - covered - exempt), sorted((covered | exempt) - names))
-    for name, reason in tg.EXEMPT.items():
-        assert reason and name.endswith(("_size", "_bytes")), "%s is a launch entry point: it needs a case, not an exemption" % name
-    assert "aesr_inplane_resample" in covered
-    assert callable(getattr(tg, "test_guard_bands_poisons_and_offset_pointers"))
 
 
 def test_out_size_is_pythons_round():

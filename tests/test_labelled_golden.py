@@ -10,20 +10,15 @@ reference; tests/golden/inplane_labels.npz, written by tests/make_golden_inplane
   shared RandomState and with two.  The descriptors they give, run through a numpy statement of the kernel's contract
   (``gather_by_descriptor``: include/aesr_hip_labelprep.h), reproduce the batches too -- the test transform's two branches included.
 - The ``order=0`` tables of ``datasets.common.zoom_tables``, applied in numpy, equal inplane_labels.npz exactly.
-- include/aesr_hip_labelprep.h == ``_hip.SIGNATURES_LABELPREP`` == the library's exports, disjoint from every other header and table, and
-  partitioned by GUARDED_ENTRIES / EXEMPT of tests/test_gpu_labelled.py.  Every argument refusal returns its code before anything touches the
-  device: callable without a GPU.
+- Every argument refusal of the two entry points returns its code before anything touches the device: callable without a GPU.
 - Every host refusal of the loader and the augmenter; the command line."""
 import ctypes
-import glob
 import os
-import re
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 NAMES = {"aesr_labelled_triplet_assemble", "aesr_labelled_triplet_assemble_raw"}
 TOL = 2e-6          # tests/test_gpu_augment.py: fp32 expf against the reference's float64 curve
 _FX = {}
@@ -253,49 +248,7 @@ def test_order0_tables_equal_the_reference_exactly():
         dc.apply_2d_zoom_4d(np.zeros((1, 1, 4, 4), np.float32), (1.0, 1.0), (1.4, 1.4), order=2)
 
 
-# ---- header and ABI ----------------------------------------------------------------------------------------------------------------
-def _declared(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return set(re.findall(r"\b(aesr_[a-z0-9_]+)\s*\(", hdr))
-
-
-def test_header_table_and_exports_agree():
-    from superresolution_aniso_mri_amd import _hip
-    declared = _declared("aesr_hip_labelprep.h")
-    assert declared == set(_hip.SIGNATURES_LABELPREP) == NAMES
-    others = set()
-    tables = [k for k in vars(_hip) if k.startswith("SIGNATURES") and k != "SIGNATURES_LABELPREP"]
-    assert len(tables) >= 9
-    for k in tables:
-        others |= set(getattr(_hip, k))
-    headers = [os.path.basename(h) for h in glob.glob(os.path.join(ROOT, "include", "*.h")) if not h.endswith("aesr_hip_labelprep.h")]
-    assert len(headers) >= 9
-    for h in headers:
-        others |= _declared(h)
-    assert not declared & others
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    P, I = ctypes.c_void_p, ctypes.c_int
-    for name in declared:
-        assert getattr(lib, name, None) is not None, "%s is declared in include/aesr_hip_labelprep.h but not exported" % name
-        res, args = _hip.SIGNATURES_LABELPREP[name]
-        assert getattr(_hip.lib, name).argtypes == args and getattr(_hip.lib, name).restype == res
-        assert (res, args) == (I, [P, P, ctypes.POINTER(_hip.TripletDesc), I, I, P, P, P])
-    # the descriptor is the existing one, unchanged
-    assert [f[0] for f in _hip.TripletDesc._fields_] == ["vol_off", "H", "W", "z_from", "z_to", "z_between", "oy", "ox", "k", "gain", "cutoff"]
-    assert ctypes.sizeof(_hip.TripletDesc) == 48
-
-
-def test_guard_band_cases_and_exemptions_partition_the_labelprep_abi():
-    """The rule of tests/test_memguard_host.py::test_case_table_and_exemptions_partition_the_abi for this table."""
-    import test_gpu_labelled as tg
-    from superresolution_aniso_mri_amd import _hip
-    covered, exempt, names = set(tg.GUARDED_ENTRIES), set(tg.EXEMPT), set(_hip.SIGNATURES_LABELPREP)
-    assert not (covered & exempt) and covered | exempt == names, (sorted(names - covered - exempt), sorted((covered | exempt) - names))
-    assert not exempt, "both entry points launch: each needs a guarded case"
-    assert callable(tg.test_guard_bands_poisons_and_offset_pointers) and callable(tg.test_refusals_write_nothing)
-
-
+# ---- the entry points ------------------------------------------------------------------------------------------------------------
 def test_entry_points_check_their_arguments_on_the_host():
     """Every refusal comes before anything touches the device: callable without a GPU; the pointers below are never dereferenced."""
     from superresolution_aniso_mri_amd import _hip

@@ -102,19 +102,3 @@ def test_guard_sizes_and_byte_buffers():
     mg.assert_guards_intact([empty])
 
 
-def test_case_table_and_exemptions_partition_the_abi():
-    """Every name of _hip.SIGNATURES is the subject of a guarded case or exempt for a stated reason; only pure host queries and the entry
-    points that need a peer or a communicator may be exempt."""
-    import test_gpu_memguard as tg
-    from superresolution_aniso_mri_amd import _hip
-    covered, exempt, names = tg.covered_entries(), set(tg.EXEMPT), set(_hip.SIGNATURES)
-    assert not (covered & exempt), sorted(covered & exempt)
-    assert covered | exempt == names, (sorted(names - covered - exempt), sorted((covered | exempt) - names))
-    host_suffixes = ("_supported", "_floats", "_bytes", "_words", "_doubles", "_kernel", "_timeouts")
-    host_names = ("aesr_version", "aesr_last_error_string", "aesr_adam_state_init")
-    for name, reason in tg.EXEMPT.items():
-        assert reason
-        peer = name.startswith(("aesr_comm_", "aesr_p2p_")) or (name.startswith("aesr_bn_fused1_") and name.endswith("_p2p"))
-        assert peer or name.endswith(host_suffixes) or name in host_names, "%s is a launch entry point: it needs a case, not an exemption" % name
-    assert len(covered) >= 70
-    assert len({c.id for c in tg.CASES}) == len(tg.CASES)

@@ -4,7 +4,6 @@
 - the modules import through the paths ``NetworkConfig("ae_combined", "ACDCLBL", "MultiChannelAE")`` hands out and through the resolver
   of ``get_trainer_dynamic``;
 - state-dict keys and order, ``named_parameters()`` order, shapes and the same-seed initial parameters equal the fixture bit for bit;
-- include/aesr_hip_seg.h == ``_hip.SIGNATURES_SEG`` == the library's exports, disjoint from the other six tables;
 - ``softmax_dice_f64`` below -- softmax with the row maximum subtracted, the soft-Dice loss and its CLOSED-FORM gradient in float64, the
   reference every device test of csrc/seg_head.hip compares against -- reproduces what the reference's ``nn.Softmax`` + ``DiceLoss`` and
   autograd give in float64 on the fixture's logits (``ref64/*``) to 1e-12;
@@ -12,7 +11,6 @@
 """
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -188,49 +186,6 @@ def test_dice_loss_module_on_soft_probabilities(size):
 
 
 # ---- the seventh header ------------------------------------------------------------------------------------------------------------
-def _declared(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return set(re.findall(r"\b(aesr_[a-z0-9_]+)\s*\(", hdr))
-
-
-SEG_NAMES = {"aesr_softmax_dice_workspace_floats", "aesr_softmax_dice_fwd", "aesr_softmax_dice_bwd"}
-OTHER_HEADERS = ("aesr_hip.h", "aesr_hip_preproc.h", "aesr_hip_dataprep.h", "aesr_hip_train.h", "aesr_hip_baselines.h", "aesr_hip_reslice.h")
-
-
-def test_seg_header_table_and_exports_agree():
-    from superresolution_aniso_mri_amd import _hip
-    declared = _declared("aesr_hip_seg.h")
-    assert declared == set(_hip.SIGNATURES_SEG) == SEG_NAMES
-    others = (set(_hip.SIGNATURES) | set(_hip.SIGNATURES_PREPROC) | set(_hip.SIGNATURES_DATAPREP) | set(_hip.SIGNATURES_TRAIN)
-              | set(_hip.SIGNATURES_BASELINES) | set(_hip.SIGNATURES_RESLICE))
-    for header in OTHER_HEADERS:
-        others |= _declared(header)
-    assert not declared & others
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    P, I, S = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-    for name in declared:
-        assert getattr(lib, name, None) is not None, "%s is declared in include/aesr_hip_seg.h but not exported" % name
-        res, args = _hip.SIGNATURES_SEG[name]
-        assert getattr(_hip.lib, name).argtypes == args and getattr(_hip.lib, name).restype == res
-    assert _hip.SIGNATURES_SEG["aesr_softmax_dice_workspace_floats"] == (S, [I] * 4)
-    assert _hip.SIGNATURES_SEG["aesr_softmax_dice_fwd"] == (I, [P, P, S, P, P, P, P, P, I, I, I, I, P])
-    assert _hip.SIGNATURES_SEG["aesr_softmax_dice_bwd"] == (I, [P, P, S, P, P, P, I, I, I, I, P])
-    # the source and the header are wired into the build
-    mk = open(os.path.join(ROOT, "superresolution_aniso_mri_amd", "csrc", "Makefile")).read()
-    assert re.search(r"^SRCS = .*\bseg_head\.hip\b", mk, flags=re.M) and mk.count("../../include/aesr_hip_seg.h") == 2
-
-
-def test_guard_band_cases_and_exemptions_partition_the_seg_abi():
-    """The rule of tests/test_memguard_host.py::test_case_table_and_exemptions_partition_the_abi for the seventh table."""
-    import test_gpu_multichannel as tg
-    covered, exempt = set(tg.GUARDED_ENTRIES), set(tg.EXEMPT)
-    assert not (covered & exempt) and covered | exempt == SEG_NAMES
-    for name, reason in tg.EXEMPT.items():
-        assert reason and name.endswith("_floats"), "%s is a launch entry point: it needs a case" % name
-    assert covered == {"aesr_softmax_dice_fwd", "aesr_softmax_dice_bwd"}
-
-
 def test_entry_points_check_their_arguments_on_the_host():
     """Every refusal comes before anything touches the device: callable without a GPU; the pointers below are never dereferenced."""
     from superresolution_aniso_mri_amd import _hip

@@ -13,17 +13,14 @@ CPU ``grid_sample``) and against a float64 numpy restatement kept in this file (
   unnormalisation can round such a coordinate either way); at most 1 % of the voxels may be excluded.
 - ``make_identity_grid`` / ``make_lax_identity_grid`` / ``make_transform`` of the package equal the fixture's grids within 1e-6;
   ``affine_between`` equals the restatement's matrix.
-- include/aesr_hip_reslice.h == ``_hip.SIGNATURES_RESLICE`` == the library's exports, disjoint from the other five tables, and partitioned
-  by GUARDED_ENTRIES / EXEMPT of tests/test_gpu_reslice.py; every refusal that is decided on the host."""
+- Every refusal that is decided on the host."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 Q = 1024.0          # the fixture's volumes are uint16 counts of 1/1024 (exact in fp32)
 # tag -> (SAX [z, y, x], LAX [z, y, x], frames)
 CASES = {"oblique": ((13, 40, 36), (3, 33, 47), 1), "oblique4d": ((13, 40, 36), (3, 33, 47), 3), "odd": ((5, 9, 11), (2, 7, 13), 1),
@@ -286,49 +283,6 @@ def test_python_interface_refusals(tmp_path, capsys):
     capsys.readouterr()
     a = rs.parse_args(["--sax", "s.nii", "--lax", "l.nii", "--out", "o.nii"])
     assert (a.sax, a.lax, a.out, a.interp) == ("s.nii", "l.nii", "o.nii", "linear")
-
-
-# ---- the sixth header ------------------------------------------------------------------------------------------------------------
-def _declared(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return set(re.findall(r"\b(aesr_[a-z0-9_]+)\s*\(", hdr))
-
-
-def test_reslice_header_table_and_exports_agree():
-    from superresolution_aniso_mri_amd import _hip
-    declared = _declared("aesr_hip_reslice.h")
-    assert declared == set(_hip.SIGNATURES_RESLICE) == {"aesr_reslice_affine", "aesr_reslice_grid"}
-    others = (set(_hip.SIGNATURES) | set(_hip.SIGNATURES_PREPROC) | set(_hip.SIGNATURES_DATAPREP) | set(_hip.SIGNATURES_TRAIN)
-              | set(_hip.SIGNATURES_BASELINES))
-    for header in ("aesr_hip.h", "aesr_hip_preproc.h", "aesr_hip_dataprep.h", "aesr_hip_train.h", "aesr_hip_baselines.h"):
-        others |= _declared(header)
-    assert not declared & others
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    P, I = ctypes.c_void_p, ctypes.c_int
-    for name in declared:
-        assert getattr(lib, name, None) is not None, "%s is declared in include/aesr_hip_reslice.h but not exported" % name
-        res, args = _hip.SIGNATURES_RESLICE[name]
-        assert getattr(_hip.lib, name).argtypes == args and getattr(_hip.lib, name).restype == res
-    assert _hip.SIGNATURES_RESLICE["aesr_reslice_affine"] == (I, [P, P] + [I] * 7 + [_hip.DP, I, P])
-    assert _hip.SIGNATURES_RESLICE["aesr_reslice_grid"] == (I, [P, P, P] + [I] * 7 + [I, P])
-    hdr = open(os.path.join(ROOT, "include", "aesr_hip_reslice.h")).read()
-    assert (_hip.RESLICE_NEAREST, _hip.RESLICE_LINEAR) == tuple(
-        int(re.search(r"#define %s (\d+)" % n, hdr).group(1)) for n in ("AESR_RESLICE_NEAREST", "AESR_RESLICE_LINEAR")) == (0, 1)
-    # the modes of aesr_resample2_* keep their names and values
-    assert (_hip.RS_POOL, _hip.RS_NEAREST, _hip.RS_BILINEAR) == (1, 2, 3)
-
-
-def test_guard_band_cases_and_exemptions_partition_the_reslice_abi():
-    """The rule of tests/test_memguard_host.py::test_case_table_and_exemptions_partition_the_abi for the sixth table."""
-    import test_gpu_reslice as tg
-    from superresolution_aniso_mri_amd import _hip
-    covered, exempt, names = set(tg.GUARDED_ENTRIES), set(tg.EXEMPT), set(_hip.SIGNATURES_RESLICE)
-    assert not (covered & exempt) and covered | exempt == names, (sorted(names - covered - exempt), sorted((covered | exempt) - names))
-    for name, reason in tg.EXEMPT.items():
-        assert reason and name.endswith(("_bytes", "_size")), "%s is a launch entry point: it needs a case" % name
-    assert covered == {"aesr_reslice_affine", "aesr_reslice_grid"}
-    assert callable(tg.test_affine_guard_bands_poisons_and_offset_pointers) and callable(tg.test_grid_guard_bands_poisons_and_offset_pointers)
 
 
 # ---- refusals decided on the host ------------------------------------------------------------------------------------------------

@@ -4,12 +4,10 @@ kwatsch/medpy_metrics.py (tests/make_golden_seg_metrics.py -> tests/golden/seg_m
 - ``surface_distances_np`` below -- borders by the neighbourhood rule, then brute force over all pairs of border voxels in float64 with the
   association sqrt(min (dz sz)^2 + ((dy sy)^2 + (dx sx)^2)), the reference every device test of csrc/seg_metrics.hip compares against --
   reproduces the fixture's ``__surface_distances`` lists (same length, same order) and scores within 1e-12 relative;
-- include/aesr_hip_surface.h == ``_hip.SIGNATURES_SURFACE`` == the library's exports, disjoint from the other seven tables;
 - every refusal of the two launch entry points comes back on the host; the workspace query's values;
 - the mirror module's import paths, what it does not provide, the no-CPU-fallback error, the command line's refusals."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -18,9 +16,6 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "seg_metrics.npz")
 REL = 1e-12
-SURFACE_NAMES = {"aesr_surface_workspace_bytes", "aesr_surface_borders", "aesr_surface_distances"}
-OTHER_HEADERS = ("aesr_hip.h", "aesr_hip_preproc.h", "aesr_hip_dataprep.h", "aesr_hip_train.h", "aesr_hip_baselines.h", "aesr_hip_reslice.h",
-                 "aesr_hip_seg.h")
 _CACHE = {}
 
 
@@ -185,48 +180,6 @@ def test_fixture_covers_the_cases_the_kernels_need():
 
 
 # ---- the eighth header -------------------------------------------------------------------------------------------------------------
-def _declared(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return set(re.findall(r"\b(aesr_[a-z0-9_]+)\s*\(", hdr))
-
-
-def test_surface_header_table_and_exports_agree():
-    from superresolution_aniso_mri_amd import _hip
-    declared = _declared("aesr_hip_surface.h")
-    assert declared == set(_hip.SIGNATURES_SURFACE) == SURFACE_NAMES
-    others = (set(_hip.SIGNATURES) | set(_hip.SIGNATURES_PREPROC) | set(_hip.SIGNATURES_DATAPREP) | set(_hip.SIGNATURES_TRAIN)
-              | set(_hip.SIGNATURES_BASELINES) | set(_hip.SIGNATURES_RESLICE) | set(_hip.SIGNATURES_SEG))
-    for header in OTHER_HEADERS:
-        others |= _declared(header)
-    assert not declared & others
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    P, I, S = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-    for name in declared:
-        assert getattr(lib, name, None) is not None, "%s is declared in include/aesr_hip_surface.h but not exported" % name
-        res, args = _hip.SIGNATURES_SURFACE[name]
-        assert getattr(_hip.lib, name).argtypes == args and getattr(_hip.lib, name).restype == res
-    assert _hip.SIGNATURES_SURFACE["aesr_surface_workspace_bytes"] == (S, [I] * 5)
-    assert _hip.SIGNATURES_SURFACE["aesr_surface_borders"] == (I, [P, P, P, P, I, I, I, I, _hip.IP, I, I, I, P])
-    assert _hip.SIGNATURES_SURFACE["aesr_surface_distances"] == (I, [P, P, _hip.LLP, P, S, P, I, I, I, I, I, I, _hip.DP, P])
-    assert "aesr_hip_seg.h" not in "aesr_hip_surface.h"
-    # the source and the header are wired into both rules of the build
-    mk = open(os.path.join(ROOT, "superresolution_aniso_mri_amd", "csrc", "Makefile")).read()
-    assert re.search(r"^SRCS = .*\bseg_metrics\.hip\b", mk, flags=re.M) and mk.count("../../include/aesr_hip_surface.h") == 2
-    hdr = open(os.path.join(ROOT, "include", "aesr_hip_surface.h")).read()
-    assert (_hip.SURFACE_MAX_CLASSES, _hip.SURFACE_COUNTS, _hip.SURFACE_MAX_W) == tuple(
-        int(re.search(r"#define AESR_SURFACE_%s (\d+)" % k, hdr).group(1)) for k in ("MAX_CLASSES", "COUNTS", "MAX_W"))
-
-
-def test_guard_band_cases_and_exemptions_partition_the_surface_abi():
-    """The rule of tests/test_memguard_host.py::test_case_table_and_exemptions_partition_the_abi for the eighth table."""
-    import test_gpu_seg_metrics as tg
-    covered, exempt = set(tg.GUARDED_ENTRIES), set(tg.EXEMPT)
-    assert not (covered & exempt) and covered | exempt == SURFACE_NAMES
-    assert exempt == {"aesr_surface_workspace_bytes"} and all(tg.EXEMPT.values())
-    assert covered == {"aesr_surface_borders", "aesr_surface_distances"}
-
-
 def workspace_bytes_restated(N, Z, H, W, C):
     up = lambda v: (v + 15) // 16 * 16          # noqa: E731
     V = Z * H * W

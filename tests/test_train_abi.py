@@ -1,54 +1,10 @@
-"""No GPU: the fourth header of libaesr_hip.so (include/aesr_hip_train.h, ``_hip.SIGNATURES_TRAIN``).
+"""No GPU: the entry points of include/aesr_hip_train.h on the host (tests/test_abi.py checks the header against ``_hip.SIGNATURES_TRAIN``).
 
-- the header == the table == the library's exports, with the argument types as bound; disjoint from the three other headers and tables;
-- ``GUARDED_ENTRIES`` and ``EXEMPT`` of tests/test_gpu_cout1_bwd.py partition the table, and only the ``_floats`` query is exempt;
 - the workspace query is (512 + 1) * 10 * Cin;
 - argument refusals come before anything touches the device: non-zero, the function's name in the message."""
 import ctypes
-import os
-import re
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OTHER_HEADERS = ("aesr_hip.h", "aesr_hip_preproc.h", "aesr_hip_dataprep.h")
 THIN_CHANNELS = (4, 8, 16, 32, 64, 128, 256)
-
-
-def _declared(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return set(re.findall(r"\b(aesr_[a-z0-9_]+)\s*\(", hdr))
-
-
-def test_train_header_table_and_exports_agree():
-    from superresolution_aniso_mri_amd import _hip
-    declared = _declared("aesr_hip_train.h")
-    assert declared == set(_hip.SIGNATURES_TRAIN) == {"aesr_conv2d_cout1_bwd", "aesr_conv2d_cout1_bwd_workspace_floats"}
-    others = set(_hip.SIGNATURES) | set(_hip.SIGNATURES_PREPROC) | set(_hip.SIGNATURES_DATAPREP)
-    for h in OTHER_HEADERS:
-        others |= _declared(h)
-    assert not declared & others
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    for name in declared:
-        assert getattr(lib, name, None) is not None, "%s is declared in include/aesr_hip_train.h but not exported" % name
-        res, args = _hip.SIGNATURES_TRAIN[name]
-        assert getattr(_hip.lib, name).argtypes == args and getattr(_hip.lib, name).restype == res
-    # the C declaration, argument by argument: 8 pointers, 5 ints, float, int, float, stream
-    P = ctypes.c_void_p
-    assert _hip.SIGNATURES_TRAIN["aesr_conv2d_cout1_bwd"] == (ctypes.c_int, [P] * 8 + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_int, ctypes.c_float, P])
-    assert _hip.SIGNATURES_TRAIN["aesr_conv2d_cout1_bwd_workspace_floats"] == (ctypes.c_size_t, [ctypes.c_int])
-
-
-def test_guard_band_cases_and_exemptions_partition_the_train_abi():
-    """The rule of tests/test_memguard_host.py::test_case_table_and_exemptions_partition_the_abi for the fourth table."""
-    import test_gpu_cout1_bwd as tg
-    from superresolution_aniso_mri_amd import _hip
-    covered, exempt, names = set(tg.GUARDED_ENTRIES), set(tg.EXEMPT), set(_hip.SIGNATURES_TRAIN)
-    assert not (covered & exempt) and covered | exempt == names, (sorted(names - covered - exempt), sorted((covered | exempt) - names))
-    for name, reason in tg.EXEMPT.items():
-        assert reason and name.endswith("_floats"), "%s is a launch entry point: it needs a case, not an exemption" % name
-    assert covered == {"aesr_conv2d_cout1_bwd"}
-    assert callable(tg.test_guard_bands_poisons_and_offset_pointers) and callable(tg.test_refusals_write_nothing)
-    assert set(tg.GUARD_SHAPES) <= set(tg.SHAPES)
 
 
 def test_workspace_query():

@@ -9,18 +9,14 @@ own results (tests/golden/z_expand.npz, written by tests/make_golden_z_expand.py
   kernel's arithmetic in numpy -- reproduce the restatement within one fp32 rounding.
 - Lanczos weights: sum in [0.998, 1] at the default radius 5 (LANCZOS_SUM has the ranges of radius 3 and 4), exactly {1, 0...} at the phase that sits on a sample; ``align='grid'`` with linear returns the
   originals bitwise at every f-th slot; the evaluation protocol returns as many slices as it was given.
-- include/aesr_hip_baselines.h == ``_hip.SIGNATURES_BASELINES`` == the library's exports, disjoint from the other four tables, and
-  partitioned by GUARDED_ENTRIES / EXEMPT of tests/test_gpu_z_expand.py.
 - Every refusal of the two launch entry points and of the Python interface that is decided on the host; the CLI flags."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 Q = 1024.0          # the fixture's inputs are multiples of 1/1024 (exact in fp32), stored as uint16 counts
 # tag -> (shape, factor); the last three axes are [Z, H, W]
 CASES = {"z1f2": ((1, 3, 5), 2), "z2f3": ((2, 3, 5), 3), "z3f2": ((3, 3, 5), 2), "z5f4": ((5, 4, 8), 4), "z11f6": ((11, 4, 8), 6),
@@ -303,47 +299,6 @@ def test_protocol_slice_count_is_the_inputs():
 
 
 # ---- the fifth header ------------------------------------------------------------------------------------------------------------
-def _declared(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return set(re.findall(r"\b(aesr_[a-z0-9_]+)\s*\(", hdr))
-
-
-def test_baselines_header_table_and_exports_agree():
-    from superresolution_aniso_mri_amd import _hip
-    declared = _declared("aesr_hip_baselines.h")
-    assert declared == set(_hip.SIGNATURES_BASELINES) == {"aesr_z_expand_out_slices", "aesr_z_expand_store_bytes", "aesr_bspline_coef_bytes",
-                                                                "aesr_bspline_prefilter_z", "aesr_z_expand"}
-    others = set(_hip.SIGNATURES) | set(_hip.SIGNATURES_PREPROC) | set(_hip.SIGNATURES_DATAPREP) | set(_hip.SIGNATURES_TRAIN)
-    for header in ("aesr_hip.h", "aesr_hip_preproc.h", "aesr_hip_dataprep.h", "aesr_hip_train.h"):
-        others |= _declared(header)
-    assert not declared & others
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    P, I = ctypes.c_void_p, ctypes.c_int
-    for name in declared:
-        assert getattr(lib, name, None) is not None, "%s is declared in include/aesr_hip_baselines.h but not exported" % name
-        res, args = _hip.SIGNATURES_BASELINES[name]
-        assert getattr(_hip.lib, name).argtypes == args and getattr(_hip.lib, name).restype == res
-    assert _hip.SIGNATURES_BASELINES["aesr_z_expand"] == (I, [P, P, P] + [I] * 7 + [_hip.IP, _hip.DP, I, I, P])
-    assert _hip.SIGNATURES_BASELINES["aesr_bspline_prefilter_z"] == (I, [P, P, I, I, I, I, P])
-    assert _hip.SIGNATURES_BASELINES["aesr_bspline_coef_bytes"] == (ctypes.c_size_t, [I] * 4)
-    hdr = open(os.path.join(ROOT, "include", "aesr_hip_baselines.h")).read()
-    assert (_hip.ZX_ALIGN_ITK, _hip.ZX_ALIGN_GRID, _hip.ZX_CLAMP, _hip.ZX_MIRROR) == tuple(
-        int(re.search(r"#define %s (\d+)" % n, hdr).group(1)) for n in ("AESR_ZX_ALIGN_ITK", "AESR_ZX_ALIGN_GRID", "AESR_ZX_CLAMP", "AESR_ZX_MIRROR"))
-
-
-def test_guard_band_cases_and_exemptions_partition_the_baselines_abi():
-    """The rule of tests/test_memguard_host.py::test_case_table_and_exemptions_partition_the_abi for the fifth table."""
-    import test_gpu_z_expand as tg
-    from superresolution_aniso_mri_amd import _hip
-    covered, exempt, names = set(tg.GUARDED_ENTRIES), set(tg.EXEMPT), set(_hip.SIGNATURES_BASELINES)
-    assert not (covered & exempt) and covered | exempt == names, (sorted(names - covered - exempt), sorted((covered | exempt) - names))
-    for name, reason in tg.EXEMPT.items():
-        assert reason and name.endswith(("_bytes", "_out_slices", "_store_bytes")), "%s is a launch entry point: it needs a case" % name
-    assert covered == {"aesr_z_expand", "aesr_bspline_prefilter_z"}
-    assert callable(tg.test_z_expand_guard_bands_poisons_and_offset_pointers) and callable(tg.test_prefilter_guard_bands_poisons_and_offset_pointers)
-
-
 def test_host_queries():
     from superresolution_aniso_mri_amd import _hip
     f = _hip.lib.aesr_z_expand_out_slices
