@@ -579,8 +579,20 @@ def load_labelled_volume_dir(images_dir, labels_dir, resample=False, new_spacing
     ``resample``: images go through ``load_volume_dir``'s in-plane resampling (blur, linear) and labels through
     ``apply_2d_zoom_3d(order=0, do_blur=False, as_type=int)`` -- nearest sample, never a mixture of class ids -- as the reference's
     ``ACDCImage`` does; both from the IMAGE file's spacing, so the two keep one shape."""
+    volumes, labels = [], []
+    for f, lf in _paired_volume_files(images_dir, labels_dir):
+        arr, lab, _ = _read_labelled_pair(f, lf, resample, new_spacing)
+        for v, l in zip([arr] if arr.ndim == 3 else list(arr), [lab] if lab.ndim == 3 else list(lab)):
+            v = np.asarray(v, dtype=np.float32)
+            volumes.append(v if (v.min() >= 0 and v.max() <= 1) else rescale_intensities(v))
+            labels.append(np.ascontiguousarray(l))
+    return volumes, labels
+
+
+def _paired_volume_files(images_dir, labels_dir):
+    """[(image file, label file)] of two directories paired by stem, in the order of the sorted stems; an empty image directory, an image
+    without a label file or a label file without an image is a ``FileNotFoundError``."""
     import os
-    from .datasets.common import apply_2d_zoom_3d, apply_2d_zoom_4d
     imgs, labs = _volume_files(images_dir), _volume_files(labels_dir)
     if not imgs:
         raise FileNotFoundError("no .npy / .nii / .mha / .mhd volumes in %s" % images_dir)
@@ -590,27 +602,61 @@ def load_labelled_volume_dir(images_dir, labels_dir, resample=False, new_spacing
     for stem in labs:
         if stem not in imgs:
             raise FileNotFoundError("%s has no image file %s.* in %s" % (os.path.join(labels_dir, labs[stem]), stem, images_dir))
-    volumes, labels = [], []
-    for stem in sorted(imgs):
-        f, lf = os.path.join(images_dir, imgs[stem]), os.path.join(labels_dir, labs[stem])
-        arr, spacing = _read_volume_file(f)
-        lab, _ = _read_volume_file(lf)
-        if arr.ndim not in (3, 4):
-            raise ValueError("%s: expected a 3-D or 4-D volume, got shape %s" % (f, arr.shape))
-        if tuple(lab.shape) != tuple(arr.shape):
-            raise ValueError("%s: the label map's shape %s is not its image's %s (%s)" % (lf, tuple(lab.shape), tuple(arr.shape), f))
-        lab = _as_label_bytes(lab, lf)
+    return [(os.path.join(images_dir, imgs[stem]), os.path.join(labels_dir, labs[stem])) for stem in sorted(imgs)]
+
+
+def _read_labelled_pair(f, lf, resample, new_spacing):
+    """(image array, labels uint8, the image file's spacing (z, y, x) or None) of one image / label file pair, 3-D or 4-D, shapes equal,
+    labels integral within 0 ... 255 (``ValueError`` naming the file); ``resample``: both resampled in-plane from the IMAGE file's spacing,
+    the image with blur and linear interpolation, the labels by nearest sample.  Intensities are not rescaled here."""
+    from .datasets.common import apply_2d_zoom_3d, apply_2d_zoom_4d
+    arr, spacing = _read_volume_file(f)
+    lab, _ = _read_volume_file(lf)
+    if arr.ndim not in (3, 4):
+        raise ValueError("%s: expected a 3-D or 4-D volume, got shape %s" % (f, arr.shape))
+    if tuple(lab.shape) != tuple(arr.shape):
+        raise ValueError("%s: the label map's shape %s is not its image's %s (%s)" % (lf, tuple(lab.shape), tuple(arr.shape), f))
+    lab = _as_label_bytes(lab, lf)
+    if resample:
+        arr = _resample_to(arr, spacing, new_spacing, f)
+        fn = apply_2d_zoom_3d if lab.ndim == 3 else apply_2d_zoom_4d
+        lab = _as_label_bytes(fn(lab.astype(np.float32), spacing, NEW_SPACING if new_spacing is None else new_spacing, order=0,
+                                 do_blur=False, as_type=int), lf)
+        assert tuple(lab.shape) == tuple(arr.shape)
+    return arr, lab, spacing
+
+
+def load_labelled_image_dict(images_dir, labels_dir, max_patients=2, resample=False, new_spacing=None):
+    """The in-memory validation patients of the multi-channel trainers' ``validate(image_dict=...)``: ``load_image_dict`` for images that
+    come with label maps.  {p_id: {'image': [t,z,y,x] float32 in [0,1], 'labels': [t,z,y,x] uint8, 'patient_id': 'patientNNN',
+    'spacing': (z,y,x)[, 'original_spacing']}} from the first ``max_patients`` image files (sorted by stem) of ``images_dir`` and the label
+    files of ``labels_dir``, paired by stem exactly as ``load_labelled_volume_dir`` pairs them, with its checks and its errors (both
+    directories are checked for unpaired files as a whole; shapes and label values of the files that are read).  A 3-D file counts as one
+    frame.  p_id: the digits in the image file's name, else its rank.  ``resample``: image and labels resampled in-plane to ``new_spacing``
+    (labels by nearest sample) before the intensities are rescaled; 'spacing' then reports [z, new_y, new_x] and 'original_spacing' the
+    file's own.  A .npy file carries no spacing: (1, 1, 1), and ``resample`` refuses it."""
+    import os
+    import re
+    out = {}
+    for rank, (f, lf) in enumerate(_paired_volume_files(images_dir, labels_dir)):
+        if len(out) >= int(max_patients):
+            break
+        arr, lab, spacing = _read_labelled_pair(f, lf, resample, new_spacing)
+        original_spacing = spacing = (1.0, 1.0, 1.0) if spacing is None else spacing
         if resample:
-            arr = _resample_to(arr, spacing, new_spacing, f)
-            fn = apply_2d_zoom_3d if lab.ndim == 3 else apply_2d_zoom_4d
-            lab = _as_label_bytes(fn(lab.astype(np.float32), spacing, NEW_SPACING if new_spacing is None else new_spacing, order=0,
-                                     do_blur=False, as_type=int), lf)
-            assert tuple(lab.shape) == tuple(arr.shape)
-        for v, l in zip([arr] if arr.ndim == 3 else list(arr), [lab] if lab.ndim == 3 else list(lab)):
-            v = np.asarray(v, dtype=np.float32)
-            volumes.append(v if (v.min() >= 0 and v.max() <= 1) else rescale_intensities(v))
-            labels.append(np.ascontiguousarray(l))
-    return volumes, labels
+            ns = NEW_SPACING if new_spacing is None else tuple(new_spacing)[-2:]
+            spacing = (spacing[0], float(ns[0]), float(ns[1]))
+        arr = np.asarray(arr, dtype=np.float32)
+        arr, lab = (arr[None], lab[None]) if arr.ndim == 3 else (arr, lab)
+        if not (arr.min() >= 0 and arr.max() <= 1):
+            arr = np.stack([rescale_intensities(a) for a in arr]).astype(np.float32)
+        digits = re.findall(r"\d+", os.path.basename(f))
+        p_id = int(digits[0]) if digits and int(digits[0]) not in out else 1000 + rank
+        out[p_id] = {"image": arr, "labels": np.ascontiguousarray(lab), "patient_id": "patient{:03d}".format(p_id),
+                     "spacing": np.asarray(spacing, dtype=np.float64)}
+        if resample:
+            out[p_id]["original_spacing"] = np.asarray(original_spacing, dtype=np.float64)
+    return out
 
 
 class LabelledTripletAugmenter(TripletAugmenter):

@@ -57,6 +57,9 @@ def build_parser():
                                                  "name (the same stem, any supported extension; integral values 0 ... 255, the image's shape)")
     a("--val_volumes_dir", type=str, default=None, help="4-D (or 3-D) validation images of this directory become the in-memory image_dict "
                                                       "that validate() previews as val_image_e###_p###.png (at most --val_patients of them)")
+    a("--val_labels_dir", type=str, default=None, help="--dataset ACDCLBL with --val_volumes_dir: the label maps of those validation images, "
+                                                     "paired by file name; validate() then also previews the synthesised label maps "
+                                                     "(val_labels_e###_p###.png) and scores them (val_label_scores_e###.npz)")
     a("--resample", action="store_true", help="with --volumes_dir / --val_volumes_dir: resample every volume in-plane from its header's "
                                               "spacing to --new_spacing on the device before the intensities are rescaled (the "
                                               "reference's CardiacImage(resample=True))")

@@ -15,10 +15,17 @@ Per step, x = batch['image'] [2B, 2, H, W] (channel 0 intensity, channel 1 class
                              run as ONE launch sequence per stack with two BatchNorm statistic groups in that order: the encoder's layers
                              are updated once, the decoder's and the label head's twice; the model is left in train mode.
 The Dice terms go from the LOGITS to the loss in one kernel pass and back in one (``ops.softmax_dice``, csrc/seg_head.hip), reading
-the labels in place from channel 1 of the batch.  Eager steps only (no graph capture); single process (data parallel raises, as
+the labels in place from channel 1 of the batch.
+
+``train()`` is a thin wrapper around ``_step_core`` (device-resident inputs, no host read of a device value), so that
+``enable_step_graph`` replays the step from one HIP graph launch for launch (``AEBaseTrainer._train_graphed``): steps that keep their
+predictions and eval steps stay eager, and the eval-mode encoder pass inside the step gets its BatchNorm scale / shift from a launch of
+the graph.  ``validate(image_dict=...)`` previews whole held-out volumes -- images AND label maps -- and scores the synthesised label
+maps on the device beside the nearest-slice baseline (``_generate_val_volumes``).  Single process (data parallel raises, as
 ``ACAITrainer`` does); the reference's CPU round-trip chunking is not reproduced (eval-mode BatchNorm makes chunked == unchunked)."""
 import os
 
+import numpy as np
 import torch
 
 from ... import ops
@@ -66,23 +73,36 @@ class MultiChannelBaseTrainer(AEBaseTrainer):
         if self.dp is not None and self.dp.active:
             raise NotImplementedError("%s is single-process (data parallel is not built for the multi-channel trainers)" % type(self).__name__)
 
-    def _graph_ok(self, keep_predictions, eval_mode):
-        return False
-
     def _head_losses(self, x, out, want_argmax):
         """(loss_ae, 0.1 * Dice, probs NHWC, argmax int32 or None) of one decoded sub-batch against its two-channel target."""
         loss_ae = self.get_loss(x[:, 0:1], out["image"], is_test=False)["loss_ae"]
         dice, probs, amax = self.mask_loss.from_logits(out["logits"], x[:, 1], want_argmax=want_argmax)
         return loss_ae, LABEL_WEIGHT * dice, probs, amax
 
-    def _begin_step(self, batch_item, eval_mode):
+    _training_after_step = False      # the host-side mode train() leaves the model in (what _step_core sets last)
+
+    def _before_step(self):
+        """Host-side work of train() that must not happen inside a captured step (device scalars the step reads)."""
+
+    def train(self, batch_item, keep_predictions=True, eval_mode=False):
+        """Thin wrapper: moves the batch, sets the mode, counts the step, then replays the captured step (``enable_step_graph``;
+        ``AEBaseTrainer._graph_ok`` decides) or runs ``_step_core`` eagerly and keeps the predictions.  Only the two image tensors go to
+        the step: both trainers mix at 0.5, so a batch's ``alpha_from`` / ``alpha_to`` would only be copied into the graph's inputs."""
         self._single_process()
-        x, between = self._to_device(batch_item["image"]), self._to_device(batch_item["slice_between"])
+        dev_batch = {k: self._to_device(batch_item[k]) for k in ("image", "slice_between")}
+        if batch_item.get("_persistent"):
+            dev_batch["_persistent"] = True          # LabelledTripletAugmenter(reuse_output=True): the buffer IS the graph's static input
         self._set_mode(not eval_mode)
         self._iters += 1
         self._note_batch(batch_item, "train")
-        self.model.prepare_weights()
-        return x, between
+        self._before_step()
+        if self._graph_ok(keep_predictions, eval_mode):
+            self._train_graphed(dev_batch)
+            self._set_mode(self._training_after_step)      # a replay runs no Python: leave the mode the eager step leaves
+            return
+        r = self._step_core(dev_batch, eval_mode, want_argmax=keep_predictions)
+        if keep_predictions:
+            self._keep_step(r)
 
     def _keep(self, lat, mix, out_image, amax):
         s = mix["slice_inbetween_mix"].detach().cpu()
@@ -90,11 +110,15 @@ class MultiChannelBaseTrainer(AEBaseTrainer):
                                   "label_inbetween_mix": mix["label_inbetween_mix"].detach().cpu(), "slice_inbetween_05": s,
                                   "reconstruction": out_image.detach().cpu(), "pred_labels": amax.unsqueeze(1).long().cpu()}
 
-    def train(self, batch_item, keep_predictions=True, eval_mode=False):
-        x, between = self._begin_step(batch_item, eval_mode)
+    def _step_core(self, batch, eval_mode, want_argmax=False):
+        """The plain step on device-resident inputs, written to be captured: no host read of a device value, every loss through ``_log``.
+        ``between`` is encoded in EVAL mode behind the train-mode encoder pass; under capture the engine recomputes the eval-mode
+        BatchNorm scale / shift in a launch of the step instead of taking them from its host cache."""
+        x, between = batch["image"], batch["slice_between"]
+        self.model.prepare_weights()
         z = self.model.encode(x)
         out = self.model.decode_logits(z)
-        loss_ae, loss_labels, _, amax = self._head_losses(x, out, keep_predictions)
+        loss_ae, loss_labels, _, amax = self._head_losses(x, out, want_argmax)
         lat = self.get_latent_loss(reference=between, alpha_from=0.5, alpha_to=0.5, z=z.detach(), no_grad=True)      # leaves eval mode
         self._backward_and_step(loss_ae + loss_labels, eval_mode)
         self._log("loss_ae", loss_ae)
@@ -103,9 +127,11 @@ class MultiChannelBaseTrainer(AEBaseTrainer):
         # reference :112-113: the logged mix is decoded with is_test=True AFTER the optimizer step -- new parameters, running statistics, no
         # BatchNorm update -- and nothing switches the model back: it is in eval mode when train() returns
         self._set_mode(False)
-        if keep_predictions:
-            mix = self._get_mixup_image(z=z.detach(), alpha_from=0.5, alpha_to=0.5, is_test=True)
-            self._keep(lat, mix, out["image"], amax)
+        return {"z": z, "lat": lat, "out": out, "amax": amax}
+
+    def _keep_step(self, r):
+        mix = self._get_mixup_image(z=r["z"].detach(), alpha_from=0.5, alpha_to=0.5, is_test=True)
+        self._keep(r["lat"], mix, r["out"]["image"], r["amax"])
 
     # ---- eval wrappers -------------------------------------------------------------------------------------------------------------
     def decode(self, z, eval=True, clear_cache=False, chunk_size=16, **kwargs):
@@ -177,11 +203,44 @@ class MultiChannelBaseTrainer(AEBaseTrainer):
         self._log("loss_label", loss_labels, True)
         self._log("loss_latent_1", lat["loss_latent"], True)
         self.save_best_val_model()
+        result = {"img_grid_recons": grid, "loss_ae": self.losses_test["loss_ae"][-1], "pred_label_grid": label_grid}
         if image_dict is not None:
-            raise NotImplementedError("whole-volume validation previews (image_dict) are not built for the multi-channel trainers")
+            result.update(self._generate_val_volumes(image_dict, frame_id=frame_id))
         from ..base_trainer import _check_watchdogs
-        _check_watchdogs(self, "validate")
-        return {"img_grid_recons": grid, "loss_ae": self.losses_test["loss_ae"][-1], "pred_label_grid": label_grid}
+        _check_watchdogs(self, "validate")      # behind the whole-volume previews too: nothing of this call is handed out unchecked
+        return result
+
+    def _generate_val_volumes(self, image_dict, frame_id):
+        """Whole-volume validation previews with label scores.  ``image_dict[p_id]``: {'image' [t,z,y,x] in [0,1], 'labels' [t,z,y,x] class
+        ids, 'patient_id', 'spacing' (z,y,x)} (``data_device.load_labelled_image_dict``).  Per patient, frame ``frame_id`` (clipped to the
+        last frame) of the image and of its label map is padded / centre-cropped to ``eval_patch_size`` (default ``width``) with one
+        geometry (label padding 0 = background), every 2nd slice kept and the held-out slices AND label maps synthesised at alpha 0.5
+        (``evaluate.common.create_super_volume(labels=)``); the synthesised label volume is scored on the device against the full label
+        volume beside the nearest-slice baseline (``evaluate.seg_metrics.score_label_supervolume``).  Returns {'synthesized_vols',
+        'synthesized_label_vols': {p_id: comparison grid (labels / nclasses)}, 'alphas', 'label_scores': {p_id: {'model', 'nearest'}}};
+        the volumes behind the grids stay in ``self.val_volume_predictions[p_id]`` ('image', 'labels': the cropped frame; 'upsampled_image',
+        'upsampled_labels': the super-volume).  The scores are not losses: they never enter ``losses_test``."""
+        from ...evaluate.common import create_super_volume
+        from ...evaluate.evaluate_image import create_compare_image
+        from ...evaluate.find_best_model import adjust_and_center_crop
+        from ...evaluate.seg_metrics import score_label_supervolume
+        eval_patch_size = self.args.get("eval_patch_size", self.args["width"])
+        vols, label_vols, alphas, scores, kept = {}, {}, {}, {}, {}
+        for p_id, data in image_dict.items():
+            if tuple(data["labels"].shape) != tuple(data["image"].shape):
+                raise ValueError("patient %s: the labels %s do not match the image %s" % (p_id, tuple(data["labels"].shape), tuple(data["image"].shape)))
+            f_id = min(int(frame_id), int(data["image"].shape[0]) - 1)
+            vol = torch.from_numpy(np.ascontiguousarray(adjust_and_center_crop(data["image"][f_id], eval_patch_size)))
+            lab = torch.from_numpy(np.ascontiguousarray(adjust_and_center_crop(data["labels"][f_id], eval_patch_size)))      # float32: small integers, exact
+            out = create_super_volume(self, vol, alpha_range=[0.5], downsample_steps=2, generate_inbetween_slices=True, labels=lab)
+            up_img, up_lab = out["upsampled_image"].detach().cpu(), out["upsampled_labels"].detach().cpu()
+            vols[p_id] = create_compare_image(vol.numpy(), up_img.numpy())
+            label_vols[p_id] = create_compare_image(lab.numpy() / self.nclasses, up_lab.float().numpy() / self.nclasses)
+            alphas[p_id] = out["pred_alphas"].squeeze()
+            scores[p_id] = score_label_supervolume(self, vol, lab, 2, data["spacing"])
+            kept[p_id] = {"image": vol, "labels": lab, "upsampled_image": up_img, "upsampled_labels": up_lab}
+        self.val_volume_predictions = kept
+        return {"synthesized_vols": vols, "synthesized_label_vols": label_vols, "alphas": alphas, "label_scores": scores}
 
     # ---- epoch hooks (reference :253-276) --------------------------------------------------------------------------------------------
     def generate_train_images(self, **kwargs):
@@ -197,8 +256,24 @@ class MultiChannelBaseTrainer(AEBaseTrainer):
     def end_epoch_processing(self, **kwargs):
         val = kwargs.get("val_result_dict") or {}
         super().end_epoch_processing(**kwargs)          # advances self.epoch (the reference adds a second increment here: a slip, not kept)
-        if self._is_writer() and val.get("pred_label_grid") is not None:
-            save_image_grid(val["pred_label_grid"], os.path.join(self.args["dir_images"], "val_pred_labels_e{:03d}.png".format(kwargs.get("epoch"))))
+        if not self._is_writer():
+            return
+        epoch, images = kwargs.get("epoch"), self.args["dir_images"]
+        if val.get("pred_label_grid") is not None:
+            save_image_grid(val["pred_label_grid"], os.path.join(images, "val_pred_labels_e{:03d}.png".format(epoch)))
+        # whole-volume previews: val_image_e###_p###.png is the base class's; the label grid beside it, and every score table of every patient in
+        # one file per epoch, keys "p###/model/dice", "p###/nearest/hd95", ... ([N][C] as evaluate.seg_metrics returns them)
+        for p_id, grid in (val.get("synthesized_label_vols") or {}).items():
+            save_image_grid(grid, os.path.join(images, "val_labels_e{:03d}_p{:03d}.png".format(epoch, int(p_id))))
+        if val.get("label_scores"):
+            np.savez(os.path.join(images, "val_label_scores_e{:03d}.npz".format(epoch)),
+                     **{"p{:03d}/{}/{}".format(int(p_id), who, k): np.asarray(v) for p_id, both in val["label_scores"].items()
+                        for who, table in both.items() for k, v in table.items()})
+
+
+def mean_label_dice(label_scores):
+    """(model, nearest): the mean Dice over classes and patients of ``validate(image_dict=...)['label_scores']``."""
+    return tuple(float(np.mean([np.mean(both[who]["dice"]) for both in label_scores.values()])) for who in ("model", "nearest"))
 
 
 class MultiChannelTrainer(MultiChannelBaseTrainer):
@@ -214,21 +289,32 @@ class MultiChannelCAISRTrainer(CombinedStepMixin, MultiChannelBaseTrainer):
         super(MultiChannelCAISRTrainer, self).__init__(args, ae, max_grad_norm, model_file, eval_mode, **kwargs)
         self._init_mask_loss(args["nclasses"])
 
-    def train(self, batch_item, keep_predictions=True, eval_mode=False):
-        x, between = self._begin_step(batch_item, eval_mode)
+    _training_after_step = True
+    train = MultiChannelBaseTrainer.train          # not CombinedStepMixin's, which comes first in the MRO: two-channel batches, labels kept
+
+    def _before_step(self):
+        self._lambda_tensor()          # the synthesis weight reaches its device scalar here: _weigh_and_log then launches nothing for it
+
+    def _step_core(self, batch, eval_mode, want_argmax=False):
+        """The combined step on device-resident inputs, written to be captured (see ``MultiChannelBaseTrainer._step_core``)."""
+        x, between = batch["image"], batch["slice_between"]
+        self.model.prepare_weights()
         z = self.model.encode(x)
         lat = self.get_latent_loss(reference=between, alpha_from=0.5, alpha_to=0.5, z=z.detach(), no_grad=True)      # leaves eval mode
         self._set_mode(not eval_mode)
         z_mix = ops.lerp_mix(z, 0.5, 0.5)
         out, mix = self.model.decode_multi([z, z_mix])          # dec(z) then dec(z_mix): two BatchNorm statistic groups, in that order
-        loss_ae, loss_labels, _, amax = self._head_losses(x, out, keep_predictions)
-        loss_extra, amax_mix = self._extra_from_logits(between, mix, keep_predictions, is_test=False)
+        loss_ae, loss_labels, _, amax = self._head_losses(x, out, want_argmax)
+        loss_extra, amax_mix = self._extra_from_logits(between, mix, want_argmax, is_test=False)
         self._backward_and_step(loss_ae + loss_extra + loss_labels, eval_mode)
         self._log("loss_ae", loss_ae)
         self._log("loss_label", loss_labels)
         self._log("loss_latent_1", lat["loss_latent"])
-        if keep_predictions:
-            self._keep(lat, {"slice_inbetween_mix": mix["image"], "label_inbetween_mix": amax_mix.unsqueeze(1).long()}, out["image"], amax)
+        return {"lat": lat, "mix": mix, "out": out, "amax": amax, "amax_mix": amax_mix}
+
+    def _keep_step(self, r):
+        self._keep(r["lat"], {"slice_inbetween_mix": r["mix"]["image"], "label_inbetween_mix": r["amax_mix"].unsqueeze(1).long()},
+                   r["out"]["image"], r["amax"])
 
     def _weigh_and_log(self, loss_image, loss_labels, is_test):
         w = self._lambda_tensor()

@@ -7,7 +7,8 @@ hot path; ``--synthetic`` feeds device-resident synthetic tr
 label map, for the multi-channel trainers; ``--ae_class`` then defaults to MultiChannelAE), ``--volumes_dir``
 feeds the volumes of a directory through the on-device augmenters of data_device.py (cardiac datasets: ``TripletAugmenter``; OASIS /
 dHCP / ADNI: thick slices simulated on the device, then ``BrainTripletAugmenter``; ``--dataset ACDCLBL`` with ``--labels_dir``: the label
-maps paired by file name, ``LabelledTripletAugmenter``).  Launch under
+maps paired by file name, ``LabelledTripletAugmenter``; ``--val_volumes_dir`` with ``--val_labels_dir``: whole held-out patients previewed and
+their synthesised label maps scored at every validation).  Launch under
 ``python -m torch.distributed.run --nproc-per-node N`` for data parallel training (one process per GPU, RCCL)."""
 import os
 from shutil import rmtree
@@ -70,9 +71,11 @@ def main(argv=None, brain=False):
                                   "batches from your own loader")
     if args_dict.get("labels_dir") and not (labelled and args_dict.get("volumes_dir")):
         raise ValueError("--labels_dir goes with --dataset ACDCLBL and --volumes_dir")
-    if labelled and args_dict.get("volumes_dir") and args_dict.get("val_volumes_dir"):
-        raise NotImplementedError("--dataset ACDCLBL with --val_volumes_dir: whole-volume validation previews are not built for the "
-                                  "multi-channel trainers")
+    if labelled and args_dict.get("val_volumes_dir") and not args_dict.get("val_labels_dir"):
+        raise NotImplementedError("--dataset ACDCLBL with --val_volumes_dir: the multi-channel trainers preview and score label maps with the "
+                                  "images, which needs --val_labels_dir DIR, the label maps of those validation images paired by file name")
+    if args_dict.get("val_labels_dir") and not (labelled and args_dict.get("val_volumes_dir")):
+        raise ValueError("--val_labels_dir goes with --dataset ACDCLBL and --val_volumes_dir")
     cfg = NetworkConfig(args_dict["model"], dataset=args_dict["dataset"], ae_class=args_dict["ae_class"])
     args_dict = merge_args_architecture(args_dict, cfg.architecture)
     if not args_dict.get("synthetic") and not args_dict.get("volumes_dir"):
@@ -146,9 +149,11 @@ def main(argv=None, brain=False):
             return augmenter.next_batch(n, reuse_output=training, shard=(dp.rank, dp.world) if dp.active else None, raw=not training,
                                         size=None if training else augmenter.eval_size(stride))
         if labelled and augmenter is not None:
-            # the multi-channel trainers step eagerly in one process: fresh tensors per batch; the validation batch goes through the
-            # reference's test transform (raw=True: no intensity curve, no rotation) and is made once
-            return augmenter.next_batch(n, shard=(dp.rank, dp.world) if dp.active else None, raw=not training)
+            # --use_step_graph: training batches go into the augmenter's persistent [3B, 2, W, W] buffer, which the captured step reads as its
+            # static input (nothing is copied); eager steps get fresh tensors per batch.  The validation batch goes through the reference's
+            # test transform (raw=True: no intensity curve, no rotation), is made once and keeps tensors of its own
+            return augmenter.next_batch(n, reuse_output=training and bool(args_dict.get("use_step_graph")),
+                                        shard=(dp.rank, dp.world) if dp.active else None, raw=not training)
         if augmenter is not None:
             # training batches go into the augmenter's persistent output buffer, which the captured step reads directly (data parallel: the
             # rank's own triplets only -- every rank draws the whole global batch's random numbers); the validation batch is kept for the
@@ -181,8 +186,12 @@ def main(argv=None, brain=False):
     validation_batch = make_batch(args_dict["seed"] - 1, args_dict["test_batch_size"], training=False)
     image_dict_val = None       # train_cardiac_aesr.py:49-53,183: a few in-memory 4-D patients, previewed as whole volumes at every validation
     if args_dict.get("val_volumes_dir"):
-        from .data_device import load_image_dict
-        if brain_volumes:
+        from .data_device import load_image_dict, load_labelled_image_dict
+        if labelled:
+            # images with their label maps: validate() previews both and scores the synthesised label maps against the nearest-slice baseline
+            image_dict_val = load_labelled_image_dict(args_dict["val_volumes_dir"], args_dict["val_labels_dir"], args_dict.get("val_patients") or 2,
+                                                      resample=bool(args_dict.get("resample")), new_spacing=args_dict.get("new_spacing"))
+        elif brain_volumes:
             image_dict_val = load_image_dict(args_dict["val_volumes_dir"], args_dict.get("val_patients") or 2, device=args_dict["device"],
                                              **brain_opts)
             for data in image_dict_val.values():
@@ -208,9 +217,14 @@ def main(argv=None, brain=False):
                     trainer.show_loss_on_tensorboard(eval_type="test")
                     trainer.generate_train_images(epoch=int(epoch), batch_item=batch_item)
                     if dp.rank == 0:
-                        print("epoch {:4d} it {:6d} loss_ae {:.6f} val {:.6f}".format(int(epoch), trainer.iters,
-                                                                                     trainer.mean_losses["loss_ae"][-1],
-                                                                                     trainer.mean_losses_test["loss_ae"][-1]))
+                        line = "epoch {:4d} it {:6d} loss_ae {:.6f} val {:.6f}".format(int(epoch), trainer.iters,
+                                                                                      trainer.mean_losses["loss_ae"][-1],
+                                                                                      trainer.mean_losses_test["loss_ae"][-1])
+                        if val_result.get("label_scores"):
+                            # held-out label maps of the validation patients: mean Dice over classes and patients, model | nearest slice
+                            from .kwatsch.sr_multi_channel.trainer_ae import mean_label_dice
+                            line += " label dice {:.4f} (nearest slice {:.4f})".format(*mean_label_dice(val_result["label_scores"]))
+                        print(line)
                     trainer.reset_losses()
             trainer.end_epoch_processing(epoch=int(epoch), val_result_dict=val_result or {}, batch_item=batch_item)
         trainer.save_models(os.path.join(args_dict["dir_models"], "{:0d}.models".format(int(epoch))), int(epoch))
