@@ -72,7 +72,7 @@ def eval_on_different_patch_size(trainer, test_images, patch_size=(32, 32)):
 
 
 def create_super_volume(trainer, images, alpha_range=None, use_original=False, hierarchical=False, downsample_steps=None,
-                        generate_inbetween_slices=False, train_patch_size=None, feature_dict=None, labels=None):
+                        generate_inbetween_slices=False, train_patch_size=None, feature_dict=None, labels=None, *, grid=None):
     """images [z,y,x] -> {'upsampled_image' [z',y,x] (CPU, clamped to [0,1]), 'upsampled_labels' None, 'pred_alphas'
     [(z_kept-1)*n, 1, y, x]} with the reference's conventions (:134-235).  ``labels`` [z,y,x] (class ids; a multi-channel model):
     'upsampled_labels' [z',y,x] follows the same slot order -- reconstructed or original label maps at the kept slots, the decoded
@@ -81,13 +81,26 @@ def create_super_volume(trainer, images, alpha_range=None, use_original=False, h
     * ``generate_inbetween_slices`` without ``downsample_steps`` sub-samples by ``len(alpha_range)+1``;
     * the last ``(z-1) % downsample_steps`` slices cannot be paired: they are cut before sub-sampling and, when in-between
       slices are generated, the ORIGINAL slices are appended after the synthesised stack;
-    * ``alpha_range`` defaults to (0.25, 0.5, 0.75); alpha weights the LATER slice of each pair."""
+    * ``alpha_range`` defaults to (0.25, 0.5, 0.75); alpha weights the LATER slice of each pair.
+
+    ``grid`` (an ``evaluate.z_grid.ZGrid`` for these z slices): the slices of a target slice spacing instead -- [grid.J, y, x], and
+    'pred_alphas' [S, 1, y, x] holds the alpha of each of the S synthesised slices in ascending position.  ``alpha_range`` must then be
+    None or empty, and the sub-sampling protocol (``downsample_steps``, ``generate_inbetween_slices``) does not apply: a ValueError."""
     if hierarchical:
         raise NotImplementedError("hierarchical latents are outside this build")
     if images.dim() != 3:
         raise ValueError("create_super_volume expects a [z, y, x] volume, got shape %s" % (tuple(images.shape),))
     if labels is not None and tuple(labels.shape) != tuple(images.shape):
         raise ValueError("labels %s do not match the images %s" % (tuple(labels.shape), tuple(images.shape)))
+    if grid is not None:
+        if alpha_range is not None and len(alpha_range) > 0:
+            raise ValueError("alpha_range belongs to the integer grid: with grid=... it must be None or empty (the grid holds the alphas)")
+        if downsample_steps is not None or generate_inbetween_slices:
+            raise ValueError("downsample_steps / generate_inbetween_slices sub-sample by an integer: they do not go with grid=...")
+        out = _ghv.create_super_volume(trainer, images, None, use_original=use_original, labels=labels, grid=grid)
+        alphas = torch.from_numpy(grid.alpha[~grid.is_original].astype(np.float32))
+        return {"upsampled_image": out["upsampled_image"], "upsampled_labels": out["upsampled_labels"],
+                "pred_alphas": alphas[:, None, None, None].expand(-1, 1, images.shape[1], images.shape[2])}
     if generate_inbetween_slices and downsample_steps is None:
         downsample_steps = int(len(alpha_range) + 1)
     orig, orig_labels, remain = images, labels, 0

@@ -25,7 +25,14 @@ model's output.
 ``--labels_input_dir DIR`` (a multi-channel model, ``--dataset ACDCLBL``): every image has a label volume of the same file name in DIR; the
 label map goes through the network as the second channel and ``<name>_labels`` is written beside the super-resolved image -- the given
 labels at the kept slots, in between the arg-max maps decoded from the same mixed latents as the in-between slices -- as an unsigned
-8-bit volume with the image's new z spacing.  Such a model is refused without the flag."""
+8-bit volume with the image's new z spacing.  Such a model is refused without the flag.
+
+``--target_spacing_z MM`` / ``--isotropic`` (instead of ``--num_interpolations``): slices MM apart -- or as far apart as the written
+in-plane pixels -- on the grid of evaluate/z_grid.py: slice j at input coordinate j * MM / (the file's z spacing), the first slice the
+first input slice, none beyond the last.  Input slices the grid hits are passed through; every other slice is the mix of its two
+neighbours with its own alpha (``HipAE.decode_mixes_at``: one mixing launch per gap on the first convolution's pre-activations, one
+decoder batch).  ``--method linear|nearest`` write their baseline on the same grid through evaluate/reslice.py.  The file is written
+with z spacing MM and its origin and direction as they were; ``.npy`` volumes say their z spacing with ``--spacing_z``."""
 import argparse
 import os
 from pathlib import Path
@@ -74,13 +81,48 @@ def _interleave(orig, synth, n, clamp):
     return out.clamp_(clamp[0], clamp[1])
 
 
-def create_super_volume(trainer, images, alpha_range, use_original=False, labels=None, to_cpu=True):
+def _assemble(kept, synth, grid, clamp):
+    """kept [Z, H, W], synth [S, H, W] (the synthesised slices in ascending position) or None -> [grid.J, H, W]: every original slot of
+    the grid takes the kept slice it is, every other slot the next synthesised slice; ``clamp`` = (lo, hi).  By index on the device."""
+    out = torch.empty((grid.J,) + tuple(kept.shape[1:]), device=kept.device, dtype=torch.float32)
+    slots = torch.from_numpy(np.flatnonzero(grid.is_original)).to(kept.device)
+    out.index_copy_(0, slots, kept.float().index_select(0, torch.from_numpy(grid.source[grid.is_original]).to(kept.device)))
+    if synth is not None:
+        out.index_copy_(0, torch.from_numpy(np.flatnonzero(~grid.is_original)).to(kept.device), synth.float())
+    return out.clamp_(clamp[0], clamp[1])
+
+
+def _decode_on_grid(trainer, lat, grid):
+    """The decoded synthesised slices of ``grid`` in ascending position: ``decode_mixes_at`` where the model has it, else per-slice
+    coefficients on gathered latent pairs and one decode."""
+    model = trainer._use_sr_model(True)
+    model.eval()
+    dec = model.decode_mixes_at(lat, grid.gap_alphas) if hasattr(model, "decode_mixes_at") else None
+    if dec is None:
+        synth = ~grid.is_original
+        gap = torch.from_numpy(grid.gap[synth]).to(lat.device)
+        zpair = torch.cat([lat.index_select(0, gap + 1), lat.index_select(0, gap)], dim=0)      # later slices, then earlier ones
+        a = grid.alpha[synth]
+        a_from, a_to = torch.from_numpy(a.astype(np.float32)), torch.from_numpy((1.0 - a).astype(np.float32))
+        dec = trainer.decode(ops.lerp_mix(zpair, a_from.to(lat.device), a_to.to(lat.device)), use_sr_model=True)
+    return dec
+
+
+def create_super_volume(trainer, images, alpha_range, use_original=False, labels=None, to_cpu=True, *, grid=None):
     """images [z,1,y,x] or [z,y,x] -> {'upsampled_image': [(z-1)(n+1)+1, y, x] (CPU, clamped), 'upsampled_labels': None}.
     ``to_cpu=False`` leaves the result in HBM (callers that go on working on the device; bench.py times it that way).
 
     ``labels`` [z,1,y,x] or [z,y,x] (class ids; a multi-channel model, reference :23-69): the label maps go in as channel 1 and
     'upsampled_labels' [(z-1)(n+1)+1, y, x] holds the original (``use_original``: float, as given) or reconstructed (int64) label maps
-    at the kept slots and, in between, the arg-max maps decoded from the SAME mixed latents as the in-between slices."""
+    at the kept slots and, in between, the arg-max maps decoded from the SAME mixed latents as the in-between slices.
+
+    ``grid`` (an ``evaluate.z_grid.ZGrid`` for these z slices; ``alpha_range`` None or empty): the output slices of a target slice
+    spacing instead, [grid.J, y, x] -- the input (or reconstructed) slices at the grid's original slots, at every other slot the mix of
+    its two neighbours with the slot's own alpha; everything else as above."""
+    if grid is not None:
+        if alpha_range is not None and len(alpha_range) > 0:
+            raise ValueError("alpha_range belongs to the integer grid: with grid=... it must be None or empty (the grid holds the alphas)")
+        return _create_super_volume_on_grid(trainer, images, grid, use_original, labels, to_cpu)
     if images.dim() == 3:
         images = torch.unsqueeze(images, dim=1)
     with_labels = labels is not None
@@ -122,6 +164,54 @@ def create_super_volume(trainer, images, alpha_range, use_original=False, labels
             recon = vol[:, 0:1] if use_original else recon["image"]
             dec = None if dec is None else dec["image"]
         out = _interleave(recon[:, 0], dec, n, (0.0, 1.0))
+    if to_cpu:
+        out = out.cpu()
+        out_labels = None if out_labels is None else out_labels.cpu()
+        if vol.is_cuda:
+            _hip.check_device_watchdogs("create_super_volume")       # the volume leaves the device here: never a silent garbage volume
+    return {"upsampled_image": out, "upsampled_labels": out_labels}
+
+
+def _create_super_volume_on_grid(trainer, images, grid, use_original, labels, to_cpu):
+    """``create_super_volume(..., grid=grid)``: the same steps with the grid's own alphas per gap and assembly by index."""
+    if images.dim() == 3:
+        images = torch.unsqueeze(images, dim=1)
+    with_labels = labels is not None
+    if with_labels and labels.dim() == 3:
+        labels = torch.unsqueeze(labels, dim=1)
+    dev = trainer.args["device"]
+    vol = images.float().to(dev)
+    if with_labels:
+        if tuple(labels.shape) != tuple(images.shape):
+            raise ValueError("labels %s do not match the images %s" % (tuple(labels.shape), tuple(images.shape)))
+        vol = torch.cat([vol, labels.float().to(dev)], dim=1)
+    Z = vol.shape[0]
+    if grid.Z != Z:
+        raise ValueError("grid is for %d slices, the volume has %d" % (grid.Z, Z))
+    out_labels = None
+    with torch.no_grad():
+        lat = _encode(trainer, vol)                                   # every slice encoded exactly once
+        recon = vol if use_original else trainer.decode(lat, use_sr_model=True)
+        if with_labels and not use_original and not isinstance(recon, dict):
+            raise ValueError("labels were given, but this model has no label head (MultiChannelAE is the one that has)")
+        if not with_labels:
+            _no_label_model(recon)
+        dec = None
+        if grid.num_synthesised > 0:
+            dec = _decode_on_grid(trainer, lat, grid)
+            if not with_labels:
+                _no_label_model(dec)
+            if with_labels and not isinstance(dec, dict):
+                raise ValueError("labels were given, but this model has no label head (MultiChannelAE is the one that has)")
+        if with_labels:
+            kept = vol[:, 1] if use_original else recon["pred_labels"][:, 0].float()
+            synth = None if dec is None else dec["pred_labels"][:, 0]
+            out_labels = _assemble(kept, synth, grid, (-3.0e38, 3.0e38))          # small integers: exact as floats
+            if not use_original:
+                out_labels = out_labels.long()
+            recon = vol[:, 0:1] if use_original else recon["image"]
+            dec = None if dec is None else dec["image"]
+        out = _assemble(recon[:, 0], None if dec is None else dec[:, 0], grid, (0.0, 1.0))
     if to_cpu:
         out = out.cpu()
         out_labels = None if out_labels is None else out_labels.cpu()
@@ -172,21 +262,31 @@ def load_images(input_dir, suffix=".nii*"):
     return [(f, np.load(str(f))) for f in files]
 
 
-def upsample_volume(trainer, vol_np, num_interpolations, labels_np=None):
+def _alpha_range(num_interpolations, grid):
+    """The integer grid's alphas, or None where a ``grid`` holds them (``num_interpolations`` must then be None)."""
+    if grid is None:
+        return np.linspace(0, 1, num_interpolations + 2, endpoint=True)[1:-1]
+    if num_interpolations is not None:
+        raise ValueError("num_interpolations=%r belongs to the integer grid: with grid=... it must be None" % (num_interpolations,))
+    return None
+
+
+def upsample_volume(trainer, vol_np, num_interpolations, labels_np=None, *, grid=None):
     """[z,y,x] or [t,z,y,x] numpy -> through-plane upsampled numpy with the same leading layout.  ``labels_np`` (same shape, class ids; a
-    multi-channel model): returns (volume, label volume as uint8) instead."""
-    alpha_range = np.linspace(0, 1, num_interpolations + 2, endpoint=True)[1:-1]
+    multi-channel model): returns (volume, label volume as uint8) instead.  ``grid`` (evaluate/z_grid.py, ``num_interpolations`` None): the
+    slices of a target spacing; every frame of a 4-D volume gets the same grid."""
+    alpha_range = _alpha_range(num_interpolations, grid)
     if labels_np is not None and tuple(labels_np.shape) != tuple(vol_np.shape):
         raise ValueError("the label volume %s does not match the image volume %s" % (tuple(labels_np.shape), tuple(vol_np.shape)))
     if vol_np.ndim == 3:
         if labels_np is None:
-            return create_super_volume(trainer, array_to_torch(vol_np), alpha_range, use_original=True)["upsampled_image"].numpy()
+            return create_super_volume(trainer, array_to_torch(vol_np), alpha_range, use_original=True, grid=grid)["upsampled_image"].numpy()
         lab = torch.from_numpy(np.ascontiguousarray(labels_np, dtype=np.float32)).unsqueeze(dim=1)
-        out = create_super_volume(trainer, array_to_torch(vol_np), alpha_range, use_original=True, labels=lab)
+        out = create_super_volume(trainer, array_to_torch(vol_np), alpha_range, use_original=True, labels=lab, grid=grid)
         return out["upsampled_image"].numpy(), np.rint(out["upsampled_labels"].numpy()).astype(np.uint8)
     if labels_np is None:
-        return np.stack([upsample_volume(trainer, v, num_interpolations) for v in vol_np])
-    pairs = [upsample_volume(trainer, v, num_interpolations, l) for v, l in zip(vol_np, labels_np)]
+        return np.stack([upsample_volume(trainer, v, num_interpolations, grid=grid) for v in vol_np])
+    pairs = [upsample_volume(trainer, v, num_interpolations, l, grid=grid) for v, l in zip(vol_np, labels_np)]
     return np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
 
 
@@ -236,13 +336,13 @@ def normalize_on_device(x, perc=(1, 99)):
     return ((x - lo) / (hi - lo)).clamp_(0, 1)
 
 
-def upsample_volume_resampled(trainer, vol_np, num_interpolations, spacing, new_spacing=(1.4, 1.4), clamp_edges=False):
+def upsample_volume_resampled(trainer, vol_np, num_interpolations, spacing, new_spacing=(1.4, 1.4), clamp_edges=False, *, grid=None):
     """``upsample_volume`` for a volume whose in-plane ``spacing`` (y, x) is not the training spacing: one upload, resample to
     ``new_spacing`` (one launch for all frames and slices), per frame normalise and synthesise (zero-padded to the network's stride where
     the resampled size needs it), resample back to ``spacing`` (one launch), one download.  [z,y,x] or [t,z,y,x] numpy -> numpy with the same leading layout; the in-plane shape is what the round trip of
-    ``int(round(n * zoom))`` gives (the input's own for the usual sizes), as in the reference."""
+    ``int(round(n * zoom))`` gives (the input's own for the usual sizes), as in the reference.  ``grid`` as in ``upsample_volume``."""
     from .datasets.common import apply_2d_zoom_3d, apply_2d_zoom_4d
-    alpha_range = np.linspace(0, 1, num_interpolations + 2, endpoint=True)[1:-1]
+    alpha_range = _alpha_range(num_interpolations, grid)
     zoom = apply_2d_zoom_3d if vol_np.ndim == 3 else apply_2d_zoom_4d
     vol = torch.from_numpy(np.ascontiguousarray(vol_np, dtype=np.float32)).to(trainer.args["device"])
     vol = zoom(vol, spacing, new_spacing, clamp_edges=clamp_edges)
@@ -258,7 +358,7 @@ def upsample_volume_resampled(trainer, vol_np, num_interpolations, spacing, new_
         f = normalize_on_device(f)
         if pad != (0, 0):
             f = torch.nn.functional.pad(f, (0, pad[0], 0, pad[1]))
-        up = create_super_volume(trainer, f.unsqueeze(1), alpha_range, use_original=True, to_cpu=False)["upsampled_image"]
+        up = create_super_volume(trainer, f.unsqueeze(1), alpha_range, use_original=True, to_cpu=False, grid=grid)["upsampled_image"]
         hr.append(up[:, :H, :W].contiguous() if pad != (0, 0) else up)
     hr = hr[0] if vol.dim() == 3 else torch.stack(hr)
     out = zoom(hr, new_spacing, spacing, clamp_edges=clamp_edges).cpu().numpy()
@@ -278,7 +378,44 @@ def expand_volume(vol_np, num_interpolations, method, align="itk", radius=5):
     return z_interp.z_expand(x, num_interpolations + 1, method, align=align, radius=radius).cpu().numpy()
 
 
-def main(argv=None):
+def check_method_on_grid(method):
+    """The methods that can write the grid of a target slice spacing: the model and the two that ``aesr_reslice_affine`` interpolates."""
+    if method not in ("ae", "linear", "nearest"):
+        raise ValueError("--method %s cannot be combined with a target slice spacing: aesr_z_expand takes integer factors only "
+                         "(ae, linear and nearest can)" % method)
+
+
+def expand_volume_on_grid(vol_np, grid, method):
+    """[z,y,x] or [t,z,y,x] numpy -> the conventional baseline ``method`` (linear or nearest) at the slices of ``grid`` (float32 numpy, same
+    leading layout): ``evaluate.reslice`` with the matrix diag(1, 1, target_spacing_z / spacing_z), one upload, one launch for all frames,
+    one download.  The grid ends inside the volume, so the zero padding of the linear interpolation is never read."""
+    from .evaluate import reslice
+    check_method_on_grid(method)
+    if method == "ae":
+        raise ValueError("expand_volume_on_grid writes a conventional baseline: linear or nearest")
+    if vol_np.ndim not in (3, 4):
+        raise ValueError("expected a [z,y,x] or [t,z,y,x] volume, got shape %s" % (vol_np.shape,))
+    if vol_np.shape[-3] != grid.Z:
+        raise ValueError("grid is for %d slices, the volume has %d" % (grid.Z, vol_np.shape[-3]))
+    matrix = np.zeros((3, 4), dtype=np.float64)
+    matrix[0, 0] = matrix[1, 1] = 1.0
+    matrix[2, 2] = grid.target_spacing_z / grid.spacing_z
+    return reslice.reslice_affine(np.asarray(vol_np), matrix, (grid.J,) + tuple(vol_np.shape[-2:]), interp=method)
+
+
+def isotropic_target(spacing_yx, name=""):
+    """``--isotropic``: the in-plane spacing the volume is written at is the z spacing asked for; the smaller of the two where the
+    pixels are not square (said on stdout)."""
+    sy, sx = float(spacing_yx[0]), float(spacing_yx[1])
+    if sy != sx:
+        print("INFO - {}in-plane spacing {:g} x {:g} mm is not square: --isotropic takes the smaller, {:g} mm".format(
+            name and "{}: ".format(name), sy, sx, min(sy, sx)))
+    return min(sy, sx)
+
+
+def parse_args(argv=None):
+    """(parser, args) with every check that needs the arguments alone made: ``args.num_interpolations`` is resolved (6 where neither it
+    nor a target spacing is given, None with a target) and ``args.on_grid`` says whether a target slice spacing was asked for."""
     p = argparse.ArgumentParser(description="Generate through-plane super-resolved volumes")
     p.add_argument("--method", choices=("ae", "linear", "bspline", "lanczos", "nearest"), default="ae",
                    help="ae: the trained model (default); otherwise a conventional interpolation along z, no --exper_dir needed")
@@ -296,7 +433,15 @@ def main(argv=None):
                    help="with --resample: repeat the edge where scipy (and the reference) leave an all-zero last row / column")
     p.add_argument("--exper_dir", type=str, default=None)
     p.add_argument("--model_nbr", type=int, default=None)
-    p.add_argument("--num_interpolations", type=int, default=6)
+    p.add_argument("--num_interpolations", type=int, default=None,
+                   help="slices put into every gap (default 6); not together with --target_spacing_z / --isotropic")
+    target = p.add_mutually_exclusive_group()
+    target.add_argument("--target_spacing_z", type=float, default=None, metavar="MM",
+                        help="write slices MM apart instead of an integer number per gap (evaluate/z_grid.py); --method ae, linear or nearest")
+    target.add_argument("--isotropic", action="store_true",
+                        help="--target_spacing_z = the in-plane spacing the volume is written at (the smaller of y and x)")
+    p.add_argument("--spacing_z", type=float, default=None, metavar="MM",
+                   help="slice spacing of .npy volumes (they carry none); required for them with --target_spacing_z / --isotropic")
     p.add_argument("--data_input_dir", type=str, default=None)
     p.add_argument("--labels_input_dir", type=str, default=None,
                    help="label volumes (class ids) with the same file names as the images: needs a multi-channel model; writes <name>_labels "
@@ -320,13 +465,31 @@ def main(argv=None):
         p.error("--output_dir is needed when there is no --exper_dir")
     if args.labels_input_dir is not None and (args.method != "ae" or args.resample):
         p.error("--labels_input_dir belongs to --method ae without --resample (label maps are not resampled in-plane)")
+    args.on_grid = args.target_spacing_z is not None or args.isotropic
+    if args.on_grid and args.num_interpolations is not None:
+        p.error("--num_interpolations is the integer grid: it does not go with --target_spacing_z / --isotropic")
+    if args.on_grid:
+        check_method_on_grid(args.method)
+    else:
+        args.num_interpolations = 6 if args.num_interpolations is None else args.num_interpolations
+    return p, args
+
+
+def main(argv=None):
+    p, args = parse_args(argv)
+    on_grid = args.on_grid
     from .kwatsch.get_trainer import get_trainer_dynamic
-    out_dir = Path(args.output_dir if args.output_dir is not None else os.path.join(args.exper_dir, "ni0{}".format(args.num_interpolations)))
+    tag = "ni0{}".format(args.num_interpolations) if not on_grid else ("iso" if args.isotropic else "sz{:g}".format(args.target_spacing_z))
+    out_dir = Path(args.output_dir if args.output_dir is not None else os.path.join(args.exper_dir, tag))
     out_dir.mkdir(parents=True, exist_ok=True)
     images = load_images(Path(args.data_input_dir))
     print("INFO - Found {} files to process in {}".format(len(images), args.data_input_dir))
     if args.resample and args.spacing is None and any(isinstance(img, np.ndarray) for _, img in images):
         p.error("--resample: .npy volumes carry no spacing; give their in-plane spacing with --spacing Y X")
+    if on_grid and args.spacing_z is None and any(isinstance(img, np.ndarray) for _, img in images):
+        p.error("--target_spacing_z / --isotropic: .npy volumes carry no spacing; give their slice spacing with --spacing_z MM")
+    if args.isotropic and args.spacing is None and any(isinstance(img, np.ndarray) for _, img in images):
+        p.error("--isotropic: .npy volumes carry no spacing; give their in-plane spacing with --spacing Y X")
     trainer = None
     if args.method == "ae":
         trainer, _ = get_trainer_dynamic(src_path=args.exper_dir, model_nbr=args.model_nbr, model_nbr_sr=None, eval_mode=True)
@@ -351,22 +514,35 @@ def main(argv=None):
             return lab.array
         return lab if isinstance(lab, np.ndarray) else sitk.GetArrayFromImage(lab)
 
-    def upsample(arr, spacing_yx, fname=None):
+    def file_grid(arr, spacing_yx, spacing_z, fname):
+        """One grid per file (every frame of a 4-D file gets it), None for the integer grid; the written in-plane spacing is the file's
+        own, also after --resample (the result is resampled back)."""
+        if not on_grid:
+            return None
+        from .evaluate.z_grid import target_grid
+        d = isotropic_target(spacing_yx, fname.name) if args.isotropic else args.target_spacing_z
+        return target_grid(arr.shape[-3], spacing_z, d)
+
+    def upsample(arr, spacing_yx, fname=None, grid=None):
         if label_files:
-            hr_img, hr_lab = upsample_volume(trainer, arr, args.num_interpolations, label_array(fname))
+            hr_img, hr_lab = upsample_volume(trainer, arr, args.num_interpolations, label_array(fname), grid=grid)
             return hr_img, clean_label_volume(hr_lab, args.largest_component, args.min_component_size)
         if args.method != "ae":
+            if grid is not None:
+                return expand_volume_on_grid(arr, grid, args.method)
             return expand_volume(arr, args.num_interpolations, args.method, args.align, args.lanczos_radius)
         if not args.resample:
-            return upsample_volume(trainer, arr, args.num_interpolations)
-        return upsample_volume_resampled(trainer, arr, args.num_interpolations, spacing_yx, args.new_spacing, clamp_edges=args.clamp_edges)
+            return upsample_volume(trainer, arr, args.num_interpolations, grid=grid)
+        return upsample_volume_resampled(trainer, arr, args.num_interpolations, spacing_yx, args.new_spacing, clamp_edges=args.clamp_edges,
+                                         grid=grid)
 
     for fname, img in images:
         if isinstance(img, volume_io.Volume):
-            hr = upsample(img.array, (img.spacing[1], img.spacing[0]), fname)
+            grid = file_grid(img.array, (img.spacing[1], img.spacing[0]), img.spacing[2], fname)
+            hr = upsample(img.array, (img.spacing[1], img.spacing[0]), fname, grid)
             hr, hr_labels = hr if label_files else (hr, None)
             spacing = list(img.spacing)
-            spacing[2] = spacing[2] / (args.num_interpolations + 1)
+            spacing[2] = spacing[2] / (args.num_interpolations + 1) if grid is None else grid.target_spacing_z
             results.append((out_dir / fname.name, hr))
             if args.save:
                 volume_io.write_volume(out_dir / fname.name, img, hr.astype(np.float32), spacing)
@@ -375,7 +551,7 @@ def main(argv=None):
                 if args.save:
                     volume_io.write_volume(out_dir / labels_name(fname.name), img, hr_labels, spacing)
         elif isinstance(img, np.ndarray):
-            hr = upsample(img, args.spacing, fname)
+            hr = upsample(img, args.spacing, fname, file_grid(img, args.spacing, args.spacing_z, fname))
             hr, hr_labels = hr if label_files else (hr, None)
             results.append((out_dir / fname.name, hr))
             if args.save:
@@ -386,11 +562,12 @@ def main(argv=None):
                     np.save(str(out_dir / labels_name(fname.name)), hr_labels)
         else:
             arr = sitk.GetArrayFromImage(img)
-            hr = upsample(arr, (img.GetSpacing()[1], img.GetSpacing()[0]), fname)
+            grid = file_grid(arr, (img.GetSpacing()[1], img.GetSpacing()[0]), img.GetSpacing()[2], fname)
+            hr = upsample(arr, (img.GetSpacing()[1], img.GetSpacing()[0]), fname, grid)
             hr, hr_labels = hr if label_files else (hr, None)
             spacing = list(img.GetSpacing())
             zi = 2 if arr.ndim == 3 else 2
-            spacing[zi] = spacing[zi] / (args.num_interpolations + 1)
+            spacing[zi] = spacing[zi] / (args.num_interpolations + 1) if grid is None else grid.target_spacing_z
             if hr.ndim == 4:
                 out = sitk.JoinSeries([sitk.GetImageFromArray(v, False) for v in hr])
             else:

@@ -141,5 +141,16 @@ class MultiChannelAE(HipAE):
             probs, amax = ops.softmax_argmax(out["logits"])
         return {"image": out["image"], "soft_probs": engine.to_nchw_view(probs), "pred_labels": amax.unsqueeze(1).long()}
 
+    def decode_mixes_at(self, z, gap_alphas):
+        """``HipAE.decode_mixes_at`` for the two-headed decoder: {'image' [S, 1, H, W], 'soft_probs', 'pred_labels'} for the S mixes,
+        gap-major in ascending position, or None as the base does."""
+        trunk = super().decode_mixes_at(z, gap_alphas)
+        if trunk is None:
+            return None
+        with torch.no_grad():
+            out = self._heads(trunk, [trunk.shape[0]], [False])[0]
+            probs, amax = ops.softmax_argmax(out["logits"])
+        return {"image": out["image"], "soft_probs": engine.to_nchw_view(probs), "pred_labels": amax.unsqueeze(1).long()}
+
     def forward(self, img):
         return self.decode(self.encode(img))

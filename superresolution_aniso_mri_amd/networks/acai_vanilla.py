@@ -207,6 +207,41 @@ class HipAE(nn.Module):
             out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
         return engine.to_nchw_view(out)
 
+    def decode_mixes_at(self, z, gap_alphas):
+        """``decode_mixes`` with alphas of its own for every gap (a target slice spacing, evaluate/z_grid.py): z [Z, C, h, w],
+        ``gap_alphas[i]`` the ascending alphas of gap i (possibly none) -> the decoded mixes gap-major, in ascending position:
+        dec(a * z[i + 1] + (1 - a) * z[i]) for a in gap_alphas[0], then gap 1's, ...  The same structure: the first convolution once
+        per slice, then one ``ops.lerp_multi`` launch per non-empty gap on the two-slice window of its pre-activations, each writing its
+        rows of ONE mixed tensor, and the rest of the decoder in pieces under the same size rule.  None where ``decode_mixes`` gives None."""
+        from .. import _hip, ops
+        if self.training:
+            raise RuntimeError("decode_mixes_at is an inference path (model.eval())")
+        gap_alphas = [[float(a) for a in al] for al in gap_alphas]
+        total = sum(len(al) for al in gap_alphas)
+        if len(gap_alphas) != z.shape[0] - 1 or total == 0:
+            raise ValueError("gap_alphas: %d lists with %d alphas for %d slices (one list per gap, one alpha or more in all)"
+                             % (len(gap_alphas), total, z.shape[0]))
+        r = self._runner("dec")
+        s0 = r.steps[0]
+        if s0.kind != "conv" or s0.s2d or s0.act not in (_hip.ACT_NONE, _hip.ACT_LRELU, _hip.ACT_RELU) or len(r.steps) < 2 or \
+                (s0.act == _hip.ACT_LRELU and not 0.0 <= s0.slope <= 1.0):
+            return None
+        zn = engine.to_nhwc(z)
+        N = zn.shape[0]
+        with torch.no_grad():
+            pre, _, _ = r.forward(zn, (0, N), False, save=False, first=0, last=1, raw_last=True)
+            mixed = torch.empty((total,) + tuple(pre.shape[1:]), device=pre.device, dtype=torch.float32)
+            row = 0
+            for i, al in enumerate(gap_alphas):
+                if al:
+                    ops.lerp_multi(pre[i:i + 2], al, s0.act, s0.slope, out=mixed[row:row + len(al)])
+                    row += len(al)
+            n_max = max(1, (1 << 28) // r.max_elems_per_image(mixed.shape[1], mixed.shape[2], mixed.shape[3], first=1))
+            outs = [r.forward(mixed[i:i + n_max], (0, min(n_max, mixed.shape[0] - i)), False, save=False, first=1)[0]
+                    for i in range(0, mixed.shape[0], n_max)]
+            out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+        return engine.to_nchw_view(out)
+
     def max_elems_per_image(self, what, chw):
         """Largest activation tensor (elements per image) of ``encode`` / ``decode`` / ``forward`` for one C x H x W input image, or None
         when this network is not an ``enc`` / ``dec`` pair of compiled stacks (BaseTrainer._run_eval then keeps its conservative guess)."""

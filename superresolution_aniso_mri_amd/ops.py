@@ -115,13 +115,20 @@ def lerp_mix(z, alpha_from, alpha_to):
     return engine.to_nchw_view(out) if z.dim() == 4 else out
 
 
-def lerp_multi(z_nhwc, alphas, act=_hip.ACT_NONE, slope=0.0):
+def lerp_multi(z_nhwc, alphas, act=_hip.ACT_NONE, slope=0.0, out=None):
     """All mixes of neighbouring slices in ONE launch: z_nhwc [Z, ...] -> [n * (Z - 1), ...], row k * (Z - 1) + i =
-    act(alphas[k] * z[i + 1] + (1 - alphas[k]) * z[i]) (no gradient: inference)."""
+    act(alphas[k] * z[i + 1] + (1 - alphas[k]) * z[i]) (no gradient: inference).  ``out``: write there (a contiguous fp32 tensor of
+    exactly that shape, e.g. the rows of one gap in the mixed tensor of a whole volume) instead of into a new tensor."""
     _hip.require_gpu_tensor(z_nhwc, "z")
     Z, n = z_nhwc.shape[0], len(alphas)
     per = z_nhwc[0].numel()
-    out = torch.empty((n * (Z - 1),) + tuple(z_nhwc.shape[1:]), device=z_nhwc.device, dtype=torch.float32)
+    shape = (n * (Z - 1),) + tuple(z_nhwc.shape[1:])
+    if out is None:
+        out = torch.empty(shape, device=z_nhwc.device, dtype=torch.float32)
+    else:
+        _hip.require_gpu_tensor(out, "out")
+        if tuple(out.shape) != shape or out.device != z_nhwc.device:
+            raise ValueError("out is %s on %s, %s on %s expected" % (tuple(out.shape), out.device, shape, z_nhwc.device))
     for k0 in range(0, n, 16):
         part = [float(a) for a in alphas[k0:k0 + 16]]
         check(lib.aesr_lerp_multi(ptr(z_nhwc), ptr(out[k0 * (Z - 1):]), Z, per, _hip.float_array(part), len(part), int(act), float(slope),
