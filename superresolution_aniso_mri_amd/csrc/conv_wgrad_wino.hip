@@ -70,12 +70,33 @@ __device__ __forceinline__ void ww_dma(__amdgpu_buffer_rsrc_t rs, float* lds_wav
 #define WW_M_HH "op_sel:[1,1] op_sel_hi:[1,1] neg_lo:[0,0] neg_hi:[0,1]"            /* (a.hi + b.hi, a.hi - b.hi) */
 #define WW_M_SELF "op_sel:[0,1] op_sel_hi:[0,1] neg_lo:[0,0] neg_hi:[0,1]"          /* with b = a: (a.lo + a.hi, a.lo - a.hi) */
 
+// a - b on two register pairs (the compiler packs the additions and multiplications of a float4 itself, but issues a subtraction
+// as two v_sub_f32); not volatile: the scheduler may move it
+__device__ __forceinline__ f32x4 ww_sub4(f32x4 a, f32x4 b) {
+    f32x2 lo, hi;
+    const f32x2 alo = a.xy, ahi = a.zw, blo = b.xy, bhi = b.zw;
+    asm("v_pk_add_f32 %0, %1, %2 " WW_M_SUB : "=v"(lo) : "v"(alo), "v"(blo));
+    asm("v_pk_add_f32 %0, %1, %2 " WW_M_SUB : "=v"(hi) : "v"(ahi), "v"(bhi));
+    return (f32x4){lo.x, lo.y, hi.x, hi.y};
+}
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));       // a 16-byte store to an address that is only 4-byte aligned
+
 // A spatial tile this workgroup visits; all uniform (SGPRs)
 struct WwTile {
     int n, ty, tx;              // image, tile row, tile column
 };
 
-template <int TH, int TW, bool STAMP>
+// LEAN (the default; AESR_WGRAD_WINO_LEAN=0 selects the other instantiation, same results bit for bit): what a launch does outside its
+// tile loop.  The first k-step waits for this wave's DMAs of tile 0 only -- tile 1 keeps landing behind it, the loop's own wait and barrier
+// in front of k-step 1 cover it -- and the 256 accumulation registers are zeroed between the DMA issue and that wait instead of in front
+// of the loop, where nothing ran beside them.  The epilogue waits for no reload from scratch, packs its subtractions and stores the slab
+// in 16-byte pieces (see there).  The tile loop is the same text in both.
+// STAMP (debug, AESR_WGRAD_WINO_DBG=1): cycles in the k-step loop / at its barrier / in the fill, and wall-clock stamps (s_memrealtime,
+// 10 ns) of a wave's life -> a.dbgbuf: WW_NTS 64-bit ticks per wave behind the cycle counters
+constexpr int WW_NTS = 10;          // 0 entry, 1 DMAs of tiles 0 / 1 issued, 2 tile 0 landed + barrier, 3 first MFMA, 4 loop end, 5 drain wait + barrier,
+                                    // 6 dg done, 7 exchange barrier, 8 slab stores issued, 9 stores retired (exit)
+constexpr int WW_DBG_WAVES = 4096 * 4;
+template <int TH, int TW, bool STAMP, bool LEAN>
 __global__ __launch_bounds__(256, 1) void conv_wgrad_wino_f32(WgradArgs a) {
     constexpr int CIT = 32, COT = 32;
     static_assert((TH == 16 && TW == 8) || (TH == 8 && TW == 16), "tiles: 8 k-steps, rows of whole 8-pixel DMA segments");
@@ -88,6 +109,14 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_wino_f32(WgradArgs a) {
     static_assert(2 * (XFL + DFL) * 4 <= 160 * 1024 && (PH * SPR) % 4 == 0 && (TH * SPRD) % 4 == 0, "LDS / segment split");
 
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    unsigned long long ts[WW_NTS] = {};
+#define WW_TS(k)                                          \
+    if constexpr (STAMP) {                                \
+        __builtin_amdgcn_sched_barrier(0);                \
+        ts[k] = __builtin_amdgcn_s_memrealtime();         \
+        __builtin_amdgcn_sched_barrier(0);                \
+    }
+    WW_TS(0)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, g = lane >> 4;
@@ -169,12 +198,14 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_wino_f32(WgradArgs a) {
     };
 
     f32x4 acc[16][2][2];                    // [position][ci block][co block]: D rows = ci 4g..4g+3, column = co l15
+    if constexpr (!LEAN) {
 #pragma unroll
-    for (int x = 0; x < 16; ++x)
+        for (int x = 0; x < 16; ++x)
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+            for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int o = 0; o < 2; ++o) acc[x][i][o] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                for (int o = 0; o < 2; ++o) acc[x][i][o] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
     float accb[2] = {0.f, 0.f};
 
     // this lane's channel inside a pixel: quad l15 >> 2 (+ 4 for the second 16-channel block), element l15 & 3; the swizzle swaps
@@ -289,12 +320,35 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_wino_f32(WgradArgs a) {
     t2 = advance(t1);
     fetch(t0, 0);
     fetch(t1, 1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    WW_TS(1)
+    if constexpr (LEAN) {
+        // the accumulators are zeroed HERE, behind the DMA issue (the empty asm makes each zero a value of its own that exists from this
+        // point on: left as plain constants they are written in front of the loop, after the wait)
+        __builtin_amdgcn_sched_barrier(0);
+        ww_rep<64>([&](auto Qc) {
+            constexpr int q = decltype(Qc)::value;
+            f32x4& acc_ = acc[q >> 2][(q >> 1) & 1][q & 1];
+            acc_ = (f32x4){0.f, 0.f, 0.f, 0.f};
+            asm volatile("" : "+a"(acc_));
+        });
+        __builtin_amdgcn_sched_barrier(0);
+        // Only tile 0 is needed to begin.  Loads retire in order, so "at most as many outstanding as this wave issued for tile 1" means
+        // its tile-0 DMAs have landed: NDS of dY and, unless the wave's X segment lies past the patch's last column (8x16 tile, segment
+        // 3: it may have issued none), NXS of X.  Tiles past the end issue their zero fills all the same.  The barrier is a bare one: a
+        // fence in front of it would wait for tile 1 again.
+        if (8 * sgx < TW + 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NXS + NDS) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NDS) : "memory");
+        __builtin_amdgcn_s_barrier();
+    } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    WW_TS(2)
     int buf = 0;
     op_read(step_xu(0, 0), step_du(0, 0), 0);
     op_transform(0);
     WW_STAMP(2)
+    WW_TS(3)
     if (t0.n < a.N) do {
         // k-step 0 of the tile: MFMAs on operand set 0, the operands of k-step 1 into set 1
         __builtin_amdgcn_sched_barrier(0);
@@ -327,78 +381,166 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_wino_f32(WgradArgs a) {
         buf ^= 1;
     } while (t0.n < a.N);
     WW_STAMP(0)
+    WW_TS(4)
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();            // DMAs still in flight (zero fills past the last tile) must land before the exchange reuses the LDS
+    WW_TS(5)
     if (STAMP && lane == 0)
         for (int k = 0; k < 3; ++k) a.dbgbuf[(blockIdx.x * 4 + wave) * 3 + k] = (float)tph[k];
 
     // ---- epilogue: signs of A, dg = G^T dU G, sum of the four waves through LDS, ONE slab per workgroup ----
     // G^T = [[1, 1/2, 1/2, 0], [0, 1/2, -1/2, 0], [0, 1/2, 1/2, 1]]
-    f32x4 dg[9][2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int o = 0; o < 2; ++o) {
-            f32x4 R[3][4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f32x4 u0_ = acc[0 + j][i][o], u1 = acc[4 + j][i][o], u2 = acc[8 + j][i][o], u3 = -acc[12 + j][i][o];
-                const f32x4 s = j == 3 ? (f32x4){-1.f, -1.f, -1.f, -1.f} : (f32x4){1.f, 1.f, 1.f, 1.f};
-                R[0][j] = s * (u0_ + 0.5f * (u1 + u2));
-                R[1][j] = s * (0.5f * (u1 - u2));
-                R[2][j] = s * (0.5f * (u1 + u2) + u3);
-            }
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                dg[r * 3 + 0][i][o] = R[r][0] + 0.5f * (R[r][1] + R[r][2]);
-                dg[r * 3 + 1][i][o] = 0.5f * (R[r][1] - R[r][2]);
-                dg[r * 3 + 2][i][o] = 0.5f * (R[r][1] + R[r][2]) + R[r][3];
-            }
-        }
-#pragma unroll
-    for (int o = 0; o < 2; ++o) {
-        accb[o] += __shfl_xor(accb[o], 16, 64);
-        accb[o] += __shfl_xor(accb[o], 32, 64);
-    }
-    // the planes are dead (barrier at the end of the last tile): every wave parks its partial sums in LDS and then adds up and stores a
-    // QUARTER of the slab (9 of the 36 [tap][ci block][co block] pieces) -- waves 0..3 in the same fixed order as before (wave 0 alone
-    // used to read 108 KB and issue all 144 stores while the other three waves idled)
-    f32x4* ex = (f32x4*)lds;                               // [wave][36][64 lanes]
-    float* exb = lds + 4 * 36 * 64 * 4;                    // [wave][2][16]
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
+    if constexpr (!LEAN) {
+        f32x4 dg[9][2][2];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int o = 0; o < 2; ++o) ex[(wave * 36 + (t * 4 + i * 2 + o)) * 64 + lane] = dg[t][i][o];
-    if (g == 0) {
-        exb[wave * 32 + l15] = accb[0];
-        exb[wave * 32 + 16 + l15] = accb[1];
-    }
-    __syncthreads();
-    const size_t plane = (size_t)a.CinP * a.CoutP;
-    float* sl = a.slab + (size_t)split * 10 * plane;
+            for (int o = 0; o < 2; ++o) {
+                f32x4 R[3][4];
 #pragma unroll
-    for (int q = 0; q < 9; ++q) {
-        const int blk = wave * 9 + q;                      // uniform: piece (t, i, o)
-        const int t = blk >> 2, i = (blk >> 1) & 1, o = blk & 1;
-        f32x4 v = ex[(0 * 36 + blk) * 64 + lane];
+                for (int j = 0; j < 4; ++j) {
+                    const f32x4 u0_ = acc[0 + j][i][o], u1 = acc[4 + j][i][o], u2 = acc[8 + j][i][o], u3 = -acc[12 + j][i][o];
+                    const f32x4 s = j == 3 ? (f32x4){-1.f, -1.f, -1.f, -1.f} : (f32x4){1.f, 1.f, 1.f, 1.f};
+                    R[0][j] = s * (u0_ + 0.5f * (u1 + u2));
+                    R[1][j] = s * (0.5f * (u1 - u2));
+                    R[2][j] = s * (0.5f * (u1 + u2) + u3);
+                }
 #pragma unroll
-        for (int w = 1; w < 4; ++w) v += ex[(w * 36 + blk) * 64 + lane];
-        const int co = co0 + o * 16 + l15;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int ci = ci0 + i * 16 + g * 4 + e;
-            sl[t * plane + (size_t)ci * a.CoutP + co] = v[e];
-        }
-    }
-    if (wave == 0 && do_bias && g == 0) {
+                for (int r = 0; r < 3; ++r) {
+                    dg[r * 3 + 0][i][o] = R[r][0] + 0.5f * (R[r][1] + R[r][2]);
+                    dg[r * 3 + 1][i][o] = 0.5f * (R[r][1] - R[r][2]);
+                    dg[r * 3 + 2][i][o] = 0.5f * (R[r][1] + R[r][2]) + R[r][3];
+                }
+            }
 #pragma unroll
         for (int o = 0; o < 2; ++o) {
-            float bsum = exb[0 * 32 + o * 16 + l15];
+            accb[o] += __shfl_xor(accb[o], 16, 64);
+            accb[o] += __shfl_xor(accb[o], 32, 64);
+        }
+        WW_TS(6)
+        // the planes are dead (barrier at the end of the last tile): every wave parks its partial sums in LDS and then adds up and stores a
+        // QUARTER of the slab (9 of the 36 [tap][ci block][co block] pieces) -- waves 0..3 in the same fixed order as before (wave 0 alone
+        // used to read 108 KB and issue all 144 stores while the other three waves idled)
+        f32x4* ex = (f32x4*)lds;                               // [wave][36][64 lanes]
+        float* exb = lds + 4 * 36 * 64 * 4;                    // [wave][2][16]
 #pragma unroll
-            for (int w = 1; w < 4; ++w) bsum += exb[w * 32 + o * 16 + l15];
-            sl[9 * plane + co0 + o * 16 + l15] = bsum;
+        for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int o = 0; o < 2; ++o) ex[(wave * 36 + (t * 4 + i * 2 + o)) * 64 + lane] = dg[t][i][o];
+        if (g == 0) {
+            exb[wave * 32 + l15] = accb[0];
+            exb[wave * 32 + 16 + l15] = accb[1];
+        }
+        __syncthreads();
+        WW_TS(7)
+        const size_t plane = (size_t)a.CinP * a.CoutP;
+        float* sl = a.slab + (size_t)split * 10 * plane;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+            const int blk = wave * 9 + q;                      // uniform: piece (t, i, o)
+            const int t = blk >> 2, i = (blk >> 1) & 1, o = blk & 1;
+            f32x4 v = ex[(0 * 36 + blk) * 64 + lane];
+#pragma unroll
+            for (int w = 1; w < 4; ++w) v += ex[(w * 36 + blk) * 64 + lane];
+            const int co = co0 + o * 16 + l15;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int ci = ci0 + i * 16 + g * 4 + e;
+                sl[t * plane + (size_t)ci * a.CoutP + co] = v[e];
+            }
+        }
+        if (wave == 0 && do_bias && g == 0) {
+#pragma unroll
+            for (int o = 0; o < 2; ++o) {
+                float bsum = exb[0 * 32 + o * 16 + l15];
+#pragma unroll
+                for (int w = 1; w < 4; ++w) bsum += exb[w * 32 + o * 16 + l15];
+                sl[9 * plane + co0 + o * 16 + l15] = bsum;
+            }
+        }
+    } else {
+        // The same sums in the same order, element by element (every result bit as above), issued in fewer instructions:
+        //  * the lane's indices come from the hardware again (v_mbcnt): the ones from the kernel's entry had been spilled across the loop,
+        //    and their two reloads from scratch were waited for here, a memory round trip each;
+        //  * the signs of A are not multiplied in: the j == 3 column keeps -R, and wherever it or -dU_3j is added, it is subtracted
+        //    (x + (-y) == x - y, -1 * x == -x: no rounding differs); subtractions are packed like the additions (ww_sub4);
+        //  * a piece (t, i, o) goes to LDS as soon as it exists, element-major ([e][lane]: conflict free), so that the adding wave reads
+        //    FOUR consecutive co of one ci row per lane and the slab takes 9 16-byte stores per wave in place of 36 4-byte ones, each with
+        //    a 32-bit lane offset behind a uniform base in place of a 64-bit multiply per store.
+        const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        const int e15 = ln & 15, eg = ln >> 4;
+        float* const exf = lds;                                // [wave][36 pieces][4 e][64 lanes]: element e of lane (g, l15) = (ci 4 g + e, co l15)
+        float* const exb = lds + 4 * 36 * 64 * 4;              // [wave][2][16]
+        ww_rep<4>([&](auto Pc) {
+            constexpr int i = decltype(Pc)::value >> 1, o = decltype(Pc)::value & 1;
+            f32x4 R[3][4];                                      // R[.][3]: the NEGATED column
+            ww_rep<4>([&](auto Jc) {
+                constexpr int j = decltype(Jc)::value;
+                const f32x4 u0_ = acc[0 + j][i][o], u1 = acc[4 + j][i][o], u2 = acc[8 + j][i][o], u3n = acc[12 + j][i][o];
+                const f32x4 h = 0.5f * (u1 + u2);
+                R[0][j] = u0_ + h;
+                R[1][j] = 0.5f * ww_sub4(u1, u2);
+                R[2][j] = ww_sub4(h, u3n);
+            });
+            ww_rep<3>([&](auto Rc) {
+                constexpr int r = decltype(Rc)::value;
+                const f32x4 h = 0.5f * (R[r][1] + R[r][2]);
+                const f32x4 d[3] = {R[r][0] + h, 0.5f * ww_sub4(R[r][1], R[r][2]), ww_sub4(h, R[r][3])};
+                ww_rep<3>([&](auto Cc) {
+                    constexpr int c = decltype(Cc)::value, blk = (r * 3 + c) * 4 + i * 2 + o;
+                    float* const p = exf + (wave * 36 + blk) * 256 + ln;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) p[e * 64] = d[c][e];
+                });
+            });
+        });
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            accb[o] += __shfl_xor(accb[o], 16, 64);
+            accb[o] += __shfl_xor(accb[o], 32, 64);
+        }
+        if (eg == 0) {
+            exb[wave * 32 + e15] = accb[0];
+            exb[wave * 32 + 16 + e15] = accb[1];
+        }
+        WW_TS(6)
+        __syncthreads();
+        WW_TS(7)
+        const size_t plane = (size_t)a.CinP * a.CoutP;
+        float* sl = a.slab + (size_t)split * 10 * plane;
+        const int rci = ln >> 2, rco = (ln & 3) * 4;            // the adding lane: ci row rci of the piece, co rco .. rco + 3
+        const float* const rd = exf + (rci & 3) * 64 + (rci >> 2) * 16 + rco;
+        // byte offsets inside this workgroup's slab are 32-bit (the launcher takes this instantiation only where 40 planes stay below 4 GB)
+        const unsigned off = (unsigned)(rci * a.CoutP + rco) * 4u, plane4 = (unsigned)plane * 4u;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) {
+            const int blk = wave * 9 + q;                      // uniform: piece (t, i, o)
+            const int t = blk >> 2, i = (blk >> 1) & 1, o = blk & 1;
+            f32x4 v = *(const f32x4*)(rd + (0 * 36 + blk) * 256);
+#pragma unroll
+            for (int w = 1; w < 4; ++w) v += *(const f32x4*)(rd + (w * 36 + blk) * 256);
+            const unsigned ub = (unsigned)t * plane4 + (unsigned)((ci0 + i * 16) * a.CoutP + co0 + o * 16) * 4u;      // uniform
+            *(f32x4u*)((char*)sl + (size_t)(ub + off)) = v;
+        }
+        if (wave == 0 && do_bias && eg == 0) {
+#pragma unroll
+            for (int o = 0; o < 2; ++o) {
+                float bsum = exb[0 * 32 + o * 16 + e15];
+#pragma unroll
+                for (int w = 1; w < 4; ++w) bsum += exb[w * 32 + o * 16 + e15];
+                sl[9 * plane + co0 + o * 16 + e15] = bsum;
+            }
+        }
+    }
+    if constexpr (STAMP) {
+        WW_TS(8)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        WW_TS(9)
+        if (lane == 0) {
+            unsigned long long* out = (unsigned long long*)(a.dbgbuf + WW_DBG_WAVES * 3) + (size_t)(blockIdx.x * 4 + wave) * WW_NTS;
+            for (int k = 0; k < WW_NTS; ++k) out[k] = ts[k];
         }
     }
 }
@@ -413,32 +555,55 @@ size_t aesr_wgrad_wino_lds_bytes(int TH, int TW) {
 // the tiles the kernel is built for: 8 k-steps ((TH / 2) * (TW / 8)), rows of whole 8-pixel DMA segments split evenly over 4 waves
 bool aesr_wgrad_wino_tile_ok(int TH, int TW) { return (TH == 16 && TW == 8) || (TH == 8 && TW == 16); }
 
-template <int TH, int TW>
+template <int TH, int TW, bool LEAN>
 static int launch_wgrad_wino(const WgradArgs& a, hipStream_t st) {
     const size_t shmem = aesr_wgrad_wino_lds_bytes(TH, TW);
     static bool attr_set[AESR_MAX_DEVICES] = {}, attr_set_dbg[AESR_MAX_DEVICES] = {};
-    if (int e = aesr_lds_opt_in((const void*)conv_wgrad_wino_f32<TH, TW, false>, "conv_wgrad_wino_f32", attr_set)) return e;
-    (void)aesr_lds_opt_in((const void*)conv_wgrad_wino_f32<TH, TW, true>, "conv_wgrad_wino_f32", attr_set_dbg);        // the stamped form
+    if (int e = aesr_lds_opt_in((const void*)conv_wgrad_wino_f32<TH, TW, false, LEAN>, "conv_wgrad_wino_f32", attr_set)) return e;
+    (void)aesr_lds_opt_in((const void*)conv_wgrad_wino_f32<TH, TW, true, LEAN>, "conv_wgrad_wino_f32", attr_set_dbg);        // the stamped form
     dim3 grid(a.S * (a.CinP / 32) * (a.CoutP / 32));
-    if (getenv("AESR_WGRAD_WINO_DBG") && grid.x <= 4096) {     // debug: per-phase cycle stamps, printed after a host sync
+    if (getenv("AESR_WGRAD_WINO_DBG") && grid.x * 4 <= (unsigned)WW_DBG_WAVES) {     // debug: per-phase stamps, printed after a host sync
+        constexpr size_t dbytes = (size_t)WW_DBG_WAVES * (3 * sizeof(float) + WW_NTS * sizeof(unsigned long long));
         static float* dbuf = nullptr;
-        if (!dbuf) (void)hipMalloc(&dbuf, 4096 * 4 * 3 * sizeof(float));
+        if (!dbuf) (void)hipMalloc(&dbuf, dbytes);
         WgradArgs b = a;
         b.dbgbuf = dbuf;
-        hipLaunchKernelGGL((conv_wgrad_wino_f32<TH, TW, true>), grid, dim3(256), shmem, st, b);
+        hipLaunchKernelGGL((conv_wgrad_wino_f32<TH, TW, true, LEAN>), grid, dim3(256), shmem, st, b);
         (void)hipStreamSynchronize(st);
-        static float host[4096 * 4 * 3];
-        (void)hipMemcpy(host, dbuf, (size_t)grid.x * 4 * 3 * sizeof(float), hipMemcpyDeviceToHost);
+        static float host[dbytes / sizeof(float)];
+        (void)hipMemcpy(host, dbuf, dbytes, hipMemcpyDeviceToHost);
+        const unsigned nw = grid.x * 4;
         double s3[3] = {0, 0, 0};
-        for (unsigned i = 0; i < grid.x * 4; ++i) for (int k = 0; k < 3; ++k) s3[k] += host[i * 3 + k];
+        for (unsigned i = 0; i < nw; ++i) for (int k = 0; k < 3; ++k) s3[k] += host[i * 3 + k];
         const double visits = (double)((a.ntiles + a.S - 1) / a.S);
         const int nks = (TH >> 1) * (TW >> 3);
-        fprintf(stderr, "[wgrad-wino stamps] grid=%u tile %dx%d S=%d (%.0f visits, %d k-steps = %d MFMA cycles per wave and visit) per visit, cycles: "
-                "k-step loop %.0f | barrier %.0f || fill %.0f\n", grid.x, TH, TW, a.S, visits, nks, nks / 4 * 64 * 32,
+        fprintf(stderr, "[wgrad-wino stamps] grid=%u tile %dx%d S=%d lean=%d (%.0f visits, %d k-steps = %d MFMA cycles per wave and visit) per visit, cycles: "
+                "k-step loop %.0f | barrier %.0f || fill %.0f\n", grid.x, TH, TW, a.S, (int)LEAN, visits, nks, nks / 4 * 64 * 32,
                 s3[0] / grid.x / 4 / visits, s3[1] / grid.x / 4 / visits, s3[2] / grid.x / 4);
+        // the wave's life in wall-clock time (10 ns ticks): mean over the waves of every phase, entry skew behind the grid's first wave
+        const unsigned long long* ts = (const unsigned long long*)(host + WW_DBG_WAVES * 3);
+        unsigned long long first = ~0ull, last = 0;
+        for (unsigned i = 0; i < nw; ++i) {
+            if (ts[(size_t)i * WW_NTS] < first) first = ts[(size_t)i * WW_NTS];
+            if (ts[(size_t)i * WW_NTS + WW_NTS - 1] > last) last = ts[(size_t)i * WW_NTS + WW_NTS - 1];
+        }
+        double ph[WW_NTS] = {}, skew = 0, skew_max = 0;
+        for (unsigned i = 0; i < nw; ++i) {
+            const unsigned long long* t = ts + (size_t)i * WW_NTS;
+            const double e = (double)(t[0] - first) * 0.01;
+            skew += e;
+            if (e > skew_max) skew_max = e;
+            for (int k = 1; k < WW_NTS; ++k) ph[k] += (double)(t[k] - t[k - 1]) * 0.01;
+        }
+        for (int k = 1; k < WW_NTS; ++k) ph[k] /= nw;
+        fprintf(stderr, "[wgrad-wino life] %d->%d N=%d %dx%d lean=%d: span %.2f us | per wave, us: entry behind first wave %.2f (max %.2f) | DMA issue %.2f | "
+                "tile wait+barrier %.2f | first operands %.2f | loop %.2f (%.2f per visit) | drain wait+barrier %.2f | dg %.2f | exchange+barrier %.2f | "
+                "slab stores issued %.2f | stores retired %.2f || outside the loop %.2f\n", a.Cin, a.Cout, a.N, a.H, a.W, (int)LEAN,
+                (double)(last - first) * 0.01, skew / nw, skew_max, ph[1], ph[2], ph[3], ph[4], ph[4] / visits, ph[5], ph[6], ph[7], ph[8], ph[9],
+                ph[1] + ph[2] + ph[3] + ph[5] + ph[6] + ph[7] + ph[8] + ph[9]);
         return AESR_OK;
     }
-    hipLaunchKernelGGL((conv_wgrad_wino_f32<TH, TW, false>), grid, dim3(256), shmem, st, a);
+    hipLaunchKernelGGL((conv_wgrad_wino_f32<TH, TW, false, LEAN>), grid, dim3(256), shmem, st, a);
     AESR_LAUNCH_CHECK("conv_wgrad_wino_f32");
     return AESR_OK;
 }
@@ -462,6 +627,10 @@ int aesr_launch_conv_wgrad_wino(const WgradArgs& a, hipStream_t st) {
         aesr_set_error("conv_wgrad_wino: channel counts must be multiples of 32 and the tile grid consistent (S=%d, %d tiles)", a.S, a.ntiles);
         return AESR_ERR_ARG;
     }
-    if (a.TH == 16) return launch_wgrad_wino<16, 8>(a, st);
-    return launch_wgrad_wino<8, 16>(a, st);
+    // AESR_WGRAD_WINO_LEAN=0: the prologue and epilogue of the earlier form (wait for both tiles, accumulators zeroed in front of the
+    // loop, 4-byte slab stores); read once
+    static const bool lean_env = [] { const char* e = getenv("AESR_WGRAD_WINO_LEAN"); return !(e && *e && atoi(e) == 0); }();
+    const bool lean = lean_env && (size_t)a.CinP * a.CoutP * 40 < ((size_t)1 << 32);      // its 32-bit byte offsets inside one slab (10 planes)
+    if (a.TH == 16) return lean ? launch_wgrad_wino<16, 8, true>(a, st) : launch_wgrad_wino<16, 8, false>(a, st);
+    return lean ? launch_wgrad_wino<8, 16, true>(a, st) : launch_wgrad_wino<8, 16, false>(a, st);
 }
