@@ -14,7 +14,7 @@ A pass may carry several *statistic groups* (sub-batches with independent BatchN
 leading prefix of the batch needs gradients.
 """
 import os
-from ctypes import c_float
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -33,20 +33,27 @@ class KernelProfiler:
 
     def __init__(self):
         self.records = []      # (kind, flops, bytes, start_event, end_event)
+        self.closed = set()    # id() of the records whose end event has been recorded
 
     def begin(self, kind, flops, nbytes=0.0):
+        """-> the record, which ``end`` takes: records may nest, and one that an exception left open closes no other"""
         e0 = torch.cuda.Event(enable_timing=True)
         e1 = torch.cuda.Event(enable_timing=True)
         e0.record(torch.cuda.current_stream())
         self.records.append((kind, flops, nbytes, e0, e1))
+        return self.records[-1]
 
-    def end(self):
-        self.records[-1][4].record(torch.cuda.current_stream())
+    def end(self, record):
+        record[4].record(torch.cuda.current_stream())
+        self.closed.add(id(record))
 
     def summary(self):
         torch.cuda.synchronize()
         out = {}
-        for kind, flops, nbytes, e0, e1 in self.records:
+        for rec in self.records:
+            if id(rec) not in self.closed:      # no end event: nothing to time
+                continue
+            kind, flops, nbytes, e0, e1 = rec
             d = out.setdefault(kind, {"launches": 0, "flops": 0.0, "bytes": 0.0, "ms": 0.0})
             d["launches"] += 1
             d["flops"] += flops
@@ -91,10 +98,14 @@ def bn_fused_pays(N, H, W, C):
     step and 15-20 us per C3 step (profiles/r05_bn_fused_ab.txt: same box, three alternating rounds), at 6 triplets 9 us; at 3 triplets
     it wins 5 us, below that nothing either way (profiles/r05_bn_fused_threshold.txt).  Default: calls of at most 9 images
     (AESR_BN_FUSED_MAX_IMAGES; AESR_BN_FUSED_MAX_MB bounds the layer's bytes for experiments).  The opt-in peer exchange
-    (AESR_SYNCBN=p2p) needs the kernel and keeps its own rule (_p2p_fits)."""
-    if N > int(os.environ.get("AESR_BN_FUSED_MAX_IMAGES", "9")):
-        return False
-    return float(N) * H * W * C * 4.0 <= float(os.environ.get("AESR_BN_FUSED_MAX_MB", "1000")) * 1e6
+    (AESR_SYNCBN=p2p) needs the kernel and keeps its own rule (the "p2p" clause of SequentialRunner.bn_route)."""
+    return N <= BN_FUSED_MAX_IMAGES and float(N) * H * W * C * 4.0 <= BN_FUSED_MAX_MB * 1e6
+
+
+# thresholds of the one-launch BatchNorm routes, read once (experiment scripts set them per process)
+BN_FUSED_MAX_IMAGES = int(os.environ.get("AESR_BN_FUSED_MAX_IMAGES", "9"))
+BN_FUSED_MAX_MB = float(os.environ.get("AESR_BN_FUSED_MAX_MB", "1000"))
+P2P_MAX_MB = float(os.environ.get("AESR_P2P_MAX_MB", "12"))
 
 
 def wino_ok(cin, cout, ks, pad, transpose):
@@ -120,18 +131,33 @@ def wgrad_kind(cin, cout, ks, pad):
     return "conv_wgrad_wino_f32" if (ks == 3 and pad == 1 and lib.aesr_conv2d_wgrad_up2_supported(int(cin), int(cout))) else "conv_wgrad_f32"
 
 
-def _pb(kind, flops, nbytes=0.0):
-    """``kind``: a kernel label, or ("wino" | "wgrad", layer arguments...) resolved through the library only while profiling.  ``nbytes``:
-    algorithmic bytes of a bandwidth-bound call (its tensors read / written once)."""
-    if PROFILER is not None:
-        if isinstance(kind, tuple):
-            kind = wino_kind(*kind[1:]) if kind[0] == "wino" else wgrad_kind(*kind[1:])
-        PROFILER.begin(kind, flops, nbytes)
+class profiled:
+    """``with profiled(kind, flops, nbytes):`` one profiler record around the block (several launches, a callback), closed by an exception
+    too.  ``kind``: a kernel label, or ("wino" | "wgrad", layer arguments...) resolved through the library only while profiling.
+    ``nbytes``: algorithmic bytes of a bandwidth-bound call (its tensors read / written once)."""
+    def __init__(self, kind, flops, nbytes=0.0):
+        self.profiler = PROFILER
+        if self.profiler is not None:
+            if isinstance(kind, tuple):
+                kind = wino_kind(*kind[1:]) if kind[0] == "wino" else wgrad_kind(*kind[1:])
+            self.record = self.profiler.begin(kind, flops, nbytes)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        if self.profiler is not None:
+            self.profiler.end(self.record)
 
 
-def _pe():
-    if PROFILER is not None:
-        PROFILER.end()
+def launch(name, *args, kind=None, flops=0.0, nbytes=0.0, what=None):
+    """One call of the library's entry point ``name`` on the current stream, checked; ``what``: the label of the error message where it
+    says more than the name.  ``lib`` is looked up here, at call time (tests install spies there).  With ``kind`` the call is one profiler
+    record of its own (``profiled``)."""
+    if kind is None or PROFILER is None:
+        return check(getattr(lib, name)(*args, stream()), what or name)
+    with profiled(kind, flops, nbytes):
+        check(getattr(lib, name)(*args, stream()), what or name)
 
 
 def _act_of(m):
@@ -176,10 +202,47 @@ class ConvStep:
     def mfma_fwd(self):
         return self.cin % 4 == 0
 
+    # The single-output 3x3 "thin" convolution (Cout == 1, padding 1), one predicate per kernel that serves it.  They differ on purpose: each
+    # is as wide as the engine has always asked, and the library refuses what its kernel does not take (csrc/aesr_api.hip).
+    @property
+    def _cout1_3x3(self):
+        return self.cout == 1 and self.ks == 3 and self.pad == 1
+
+    @property
+    def cout1_fwd(self):
+        """aesr_conv2d_cout1_fwd: any multiple of 4 input channels (the library bounds it by 256)"""
+        return self._cout1_3x3 and self.cin % 4 == 0
+
+    @property
+    def cout1_wgrad(self):
+        """aesr_conv2d_cout1_wgrad: no channel rule here, the library picks a kernel by Cin (4 * 2^k, or another divisor of 256) or refuses"""
+        return self._cout1_3x3
+
+    @property
+    def cout1_dgrad(self):
+        """aesr_conv2d_cout1_dgrad / _dgrad_pre: Cin = 4 * 2^k <= 256 (thin_channels_ok of aesr_api.hip); ``conv_dgrad_route`` serves the rest"""
+        return self._cout1_3x3 and _thin_channels(self.cin)
+
+    @property
+    def cout1_flip(self):
+        """the flipped filter of PREP_COUT1_FLIP: what ``cout1_dgrad`` and ``cout1_bwd`` read, so their channel rule"""
+        return self._cout1_3x3 and _thin_channels(self.cin) and not self.s2d
+
+    @property
+    def cout1_bwd(self):
+        """aesr_conv2d_cout1_bwd (the whole backward in one pass): the data gradient's channel rule, a bias, the input at the convolution's size"""
+        return self._cout1_3x3 and _thin_channels(self.cin) and not self.s2d and not self.in_up2 and self.mod.bias is not None
+
     def out_hw(self, h, w):
         if self.s2d:
             return h // 2, w // 2
         return h + 2 * self.pad - self.ks + 1, w + 2 * self.pad - self.ks + 1
+
+    def out_shape(self, h, w, c):
+        """(H, W, C) behind the step for an h x w x c tensor in front of it; a folded Upsample(x2) doubles the size first"""
+        if self.in_up2:
+            h, w = 2 * h, 2 * w
+        return self.out_hw(h, w) + (self.cout,)
 
     def weight_for_kernels(self):
         """[Cout,Cin,K,K] filter the kernels see (s2d: channels ordered (ky, kx, c) like aesr_space_to_depth2)."""
@@ -204,8 +267,8 @@ class StemConvStep:
         self.folded = None
         self.folded_epoch = -1
 
-    def out_hw(self, h, w):
-        return h + 2 * self.stem_pad, w + 2 * self.stem_pad
+    def out_shape(self, h, w, c):
+        return h + 2 * self.stem_pad, w + 2 * self.stem_pad, self.cout
 
 
 def _thin_channels(c):
@@ -236,14 +299,14 @@ class BnStep:
     def run_mode(self):
         return _hip.BN_NONE if self.fold_up else self.mode
 
-    def out_hw(self, h, w):
+    def out_shape(self, h, w, c):
         if self.fold_up:
-            return h, w
+            return h, w, c
         if self.mode == _hip.BN_POOL:
-            return h // 2, w // 2
+            return h // 2, w // 2, c
         if self.mode == _hip.BN_UP:
-            return 2 * h, 2 * w
-        return h, w
+            return 2 * h, 2 * w, c
+        return h, w, c
 
 
 class ResampleStep:
@@ -254,8 +317,8 @@ class ResampleStep:
     def __init__(self, mode):
         self.mode = mode
 
-    def out_hw(self, h, w):
-        return (h // 2, w // 2) if self.mode == _hip.RS_POOL else (2 * h, 2 * w)
+    def out_shape(self, h, w, c):
+        return (h // 2, w // 2, c) if self.mode == _hip.RS_POOL else (2 * h, 2 * w, c)
 
 
 def _resample_of(m):
@@ -324,6 +387,61 @@ def _empty(shape, like, dtype=torch.float32):
     return torch.empty(shape, device=like.device, dtype=dtype)
 
 
+# What every step of one pass is told.  Forward: group boundaries, their number, train / eval, keep tensors for a backward pass.  Backward: the
+# leading ngrad images (groups ns) get gradients; the steps fill in grads {parameter: tensor or None} and the pending weight-gradient reductions.
+ForwardPass = namedtuple("ForwardPass", "nstart G train save")
+BackwardPass = namedtuple("BackwardPass", "ngrad ns grads reduce_jobs need_input_grad")
+
+
+def conv_forward_route(s, N, H, W, f, nxt, raw):
+    """Kernel of convolution ``s`` on N images of H x W (the convolution's own size) in pass ``f``; ``nxt``: the step behind it, ``raw``: it
+    leaves out its activation.  up2 | cout1 | fused_eval_bn | wino | igemm | smallcin"""
+    if s.in_up2:
+        return "up2"
+    if s.cout1_fwd:
+        return "cout1"
+    if (s.wino_fwd and FUSE_EVAL_BN and not f.train and not f.save and f.G == 1 and nxt is not None and nxt.kind == "bn"
+            and nxt.run_mode in (_hip.BN_NONE, _hip.BN_POOL) and nxt.mod.running_mean is not None and not raw
+            and (nxt.run_mode == _hip.BN_NONE or (H >= 2 and W >= 2)) and lib.aesr_conv2d_wino_fwd_bn_supported(N, H, W, s.cin, s.cout)):
+        return "fused_eval_bn"
+    if s.wino_fwd:
+        return "wino"
+    if s.mfma_fwd:
+        return "igemm"
+    if s.cin <= 4:
+        return "smallcin"
+    raise NotImplementedError("conv with Cin=%d (neither <=4 nor a multiple of 4)" % s.cin)
+
+
+def conv_wgrad_route(s, has_bias):
+    """s2d_reduce_now | partial (MFMA slabs, summed at the end of the pass) | smallcin_1x1 | cout1"""
+    if s.cin % 4 == 0 and s.cout % 4 == 0:
+        return "s2d_reduce_now" if s.s2d else "partial"
+    if s.cin <= 4 and s.ks == 1 and has_bias:
+        return "smallcin_1x1"
+    if s.cout1_wgrad and has_bias:
+        return "cout1"
+    raise NotImplementedError("no wgrad kernel for conv %d->%d k%d" % (s.cin, s.cout, s.ks))
+
+
+def conv_dgrad_route(s, masked, flipped_fresh):
+    """sum2 | smallcin | wino | igemm | cout1_pre | cout1 | smallcin_as_fwd.  ``masked``: the derivative of the producer's activation is
+    applied; ``flipped_fresh``: the flipped filter of ``cout1_pre`` is current."""
+    if s.in_up2:
+        return "sum2"
+    if s.cin <= 4 and not masked:
+        return "smallcin"
+    if s.wino_dgrad:
+        return "wino"
+    if s.cout % 4 == 0:
+        return "igemm"
+    if s.cout1_dgrad:
+        return "cout1_pre" if flipped_fresh else "cout1"
+    if s.cout <= 4:
+        return "smallcin_as_fwd"
+    raise NotImplementedError("no dgrad kernel for conv %d->%d" % (s.cin, s.cout))
+
+
 class SequentialRunner:
     """Executes one compiled stack.  ``weights_epoch`` must be bumped whenever parameters change in place."""
 
@@ -333,13 +451,15 @@ class SequentialRunner:
         self.steps_fused = fuse_stem(self.steps) if FUSE_STEM else None
         self.weights_epoch = 0
         self.params = [p for p in seq.parameters()]
+        self._bn_updates = 0        # times a kernel may have written BatchNorm running statistics through raw pointers
+        self._eval_bn = {}          # id(BatchNorm module) -> (state key, eval-mode statistics): _eval_bn_stats
 
     def mark_weights_dirty(self):
         """Host counters only (no launch).  Every state a kernel may have written through raw pointers counts as changed: the parameters
         (packed operands, folded stem) and the BatchNorm running statistics (eval-mode scale / shift cache) -- a replayed step graph
         updates both without any tensor version or Python-side counter moving, so the trainer calls this after every replay."""
         self.weights_epoch += 1
-        self._bn_updates = getattr(self, "_bn_updates", 0) + 1
+        self._bn_updates += 1
 
     # ---- weight preparation ---------------------------------------------------------------------------------
     def _prep_jobs(self, steps):
@@ -370,7 +490,7 @@ class SequentialRunner:
                 continue
             _hip.require_gpu_tensor(w, "conv weight")
             wk = s.weight_for_kernels()
-            forms = ((0, "packed", s.cin % 4 == 0 and not s.wino_fwd, _hip.PREP_PACK), (1, "packed_t", s.cout % 4 == 0 and not s.wino_dgrad, _hip.PREP_PACK),
+            forms = ((0, "packed", s.mfma_fwd and not s.wino_fwd, _hip.PREP_PACK), (1, "packed_t", s.cout % 4 == 0 and not s.wino_dgrad, _hip.PREP_PACK),
                      (0, "packed_w", s.wino_fwd, _hip.PREP_WINO_PACK), (1, "packed_wt", s.wino_dgrad, _hip.PREP_WINO_PACK))
             for transpose, attr, ok, kind in forms:
                 if not ok:
@@ -382,15 +502,12 @@ class SequentialRunner:
                     buf = _empty((n,), wk)
                     setattr(s, attr, buf)
                 jobs.append(_hip.PrepJob(wk.data_ptr(), None, None, buf.data_ptr(), kind, s.cout, s.cin, s.ks, transpose))
-            if s.cout == 1 and s.ks == 3 and s.pad == 1 and _thin_channels(s.cin) and not s.s2d:
+            if s.cout1_flip:
                 if s.flipped is None or s.flipped.numel() != 9 * s.cin:
                     s.flipped = _empty((9 * s.cin,), wk)
                 jobs.append(_hip.PrepJob(wk.data_ptr(), None, None, s.flipped.data_ptr(), _hip.PREP_COUT1_FLIP, 1, s.cin, 3, 0))
             commits.append(lambda s=s, epoch=epoch: setattr(s, "packed_epoch", epoch))
         return jobs, commits
-
-    def _ensure_prepared(self, steps):
-        prepare_weights([(self, steps)])
 
     def train_steps(self):
         """The step list a training pass runs (the stem-folded one when it exists): what ``prepare_weights`` readies ahead of the pass."""
@@ -402,127 +519,27 @@ class SequentialRunner:
         ``first`` / ``last``: run only steps [first, last) of the UNFUSED list (inference: the decoder's first convolution apart from
         the rest); ``raw_last``: the last step that runs is a convolution and leaves out its activation (pre-activations)."""
         _hip.require_gpu_tensor(x, "input")
-        N, H, W, C = x.shape
-        G = len(nstart) - 1
-        saved = []
-        cur = x
+        f = ForwardPass(nstart, len(nstart) - 1, train, save)
         partial = first != 0 or last is not None
         steps = self.steps_fused if (fused and self.steps_fused is not None and not partial) else self.steps
-        self._ensure_prepared(steps)
+        prepare_weights([(self, steps)])
         if partial:
             if save:
                 raise RuntimeError("a partial pass keeps nothing for a backward pass")
             steps = steps[first:last]
             if raw_last and (not steps or steps[-1].kind != "conv"):
                 raise RuntimeError("raw_last needs a convolution as the last step of the range")
-        skip = False
-        for idx, s in enumerate(steps):
-            if skip:                # a BatchNorm that went into the epilogue of the convolution in front of it (eval mode)
-                skip = False
-                continue
-            if s.kind == "stemconv":
-                if C != 1:
-                    raise RuntimeError("channel mismatch: tensor has %d channels, the stem expects 1" % C)
-                Ho, Wo = s.out_hw(H, W)
-                out = _empty((N, Ho, Wo, s.cout), x)
-                _pb("thin_expand", 0.0, 4.0 * (cur.numel() + out.numel()))
-                check(lib.aesr_stemconv_fwd(ptr(cur), ptr(s.folded), ptr(s.mod.bias), ptr(out), N, H, W, s.cout, s.stem_pad,
-                                            s.act, s.slope, stream()), "aesr_stemconv_fwd")
-                _pe()
-                if save:
-                    saved.append((cur, out))
-                if TRACE is not None:
-                    TRACE.append((self.seq, s.mod, s.act, out))
-                cur, H, W, C = out, Ho, Wo, s.cout
-            elif s.kind == "conv":
-                act_k = _hip.ACT_NONE if (raw_last and s is steps[-1]) else s.act
-                if s.s2d:
-                    if C != s.cin_full:
-                        raise RuntimeError("channel mismatch: tensor has %d channels, conv expects %d" % (C, s.cin_full))
-                    xs = _empty((N, H // 2, W // 2, 4 * C), x)
-                    check(lib.aesr_space_to_depth2(ptr(cur), ptr(xs), N, H, W, C, stream()), "aesr_space_to_depth2")
-                    full_hw = (H, W)
-                    cur, H, W, C = xs, H // 2, W // 2, 4 * C
-                if C != s.cin:
-                    raise RuntimeError("channel mismatch: tensor has %d channels, conv expects %d" % (C, s.cin))
-                if s.in_up2:
-                    H, W = 2 * H, 2 * W                    # the convolution's size; ``cur`` stays at half resolution
-                Ho, Wo = (H, W) if s.s2d else s.out_hw(H, W)
-                out = _empty((N, Ho, Wo, s.cout), x)
-                bias = s.mod.bias
-                if s.in_up2:
-                    _pb(("wino", N, Ho, Wo, s.cin, s.cout, 0), 2.0 * N * Ho * Wo * s.cout * 9 * s.cin)
-                    check(lib.aesr_conv2d_wino_fwd_up2(ptr(cur), ptr(s.packed_w), ptr(bias), ptr(out), N, H, W, s.cin, s.cout, act_k,
-                                                       s.slope, stream()), "aesr_conv2d_wino_fwd_up2")
-                    _pe()
-                elif s.cout == 1 and s.ks == 3 and s.pad == 1 and s.cin % 4 == 0:
-                    _pb("thin_collapse", 0.0, 4.0 * (cur.numel() + out.numel()))
-                    check(lib.aesr_conv2d_cout1_fwd(ptr(cur), ptr(s.mod.weight), ptr(bias), ptr(out), N, H, W, s.cin, act_k,
-                                                    s.slope, stream()), "aesr_conv2d_cout1_fwd")
-                    _pe()
-                elif (s.wino_fwd and FUSE_EVAL_BN and not train and not save and G == 1 and idx + 1 < len(steps) and steps[idx + 1].kind == "bn"
-                      and steps[idx + 1].run_mode in (_hip.BN_NONE, _hip.BN_POOL) and steps[idx + 1].mod.running_mean is not None
-                      and not (raw_last and s is steps[-1]) and (steps[idx + 1].run_mode == _hip.BN_NONE or (H >= 2 and W >= 2))
-                      and lib.aesr_conv2d_wino_fwd_bn_supported(N, H, W, s.cin, s.cout)):
-                    # eval mode: BatchNorm is a per-channel affine of the running statistics (cached per layer state) -- it and the pooling
-                    # behind it go into this convolution's epilogue; the activation tensor in between is never written
-                    nxt = steps[idx + 1]
-                    st = self._bn_forward_stats(nxt.mod, cur, N, Ho, Wo, s.cout, nstart, False)
-                    Hb, Wb = nxt.out_hw(Ho, Wo)
-                    out = _empty((N, Hb, Wb, s.cout), x)
-                    _pb(("wino", N, Ho, Wo, s.cin, s.cout, 0), 2.0 * N * Ho * Wo * s.cout * 9 * s.cin)
-                    check(lib.aesr_conv2d_wino_fwd_bn(ptr(cur), ptr(s.packed_w), ptr(bias), ptr(st["scale"]), ptr(st["shift"]), ptr(out), N, H, W,
-                                                      s.cin, s.cout, act_k, s.slope, int(nxt.run_mode == _hip.BN_POOL), stream()),
-                          "aesr_conv2d_wino_fwd_bn")
-                    _pe()
-                    Ho, Wo, skip = Hb, Wb, True
-                elif s.wino_fwd:
-                    _pb(("wino", N, Ho, Wo, s.cin, s.cout, 0), 2.0 * N * Ho * Wo * s.cout * 9 * s.cin)
-                    ws, nws = wino_workspace(cur, N, H, W, s.cin, s.cout, 0)
-                    check(lib.aesr_conv2d_wino_fwd_ws(ptr(cur), ptr(s.packed_w), ptr(bias), ptr(out), ptr(ws), nws, N, H, W, s.cin, s.cout,
-                                                      act_k, s.slope, stream()), "aesr_conv2d_wino_fwd_ws")
-                    _pe()
-                elif s.mfma_fwd:
-                    _pb("conv_igemm_f32", 2.0 * N * Ho * Wo * s.cout * s.ks * s.ks * s.cin)
-                    nws = lib.aesr_conv2d_workspace_floats(N, H, W, s.cin, s.cout, s.ks, s.pad)    # > 0: few, deep work items
-                    ws = _empty((nws,), x) if nws else None
-                    check(lib.aesr_conv2d_fwd_ws(ptr(cur), ptr(s.packed), ptr(bias), ptr(out), ptr(ws), N, H, W, s.cin, s.cout,
-                                                 s.ks, s.pad, act_k, s.slope, stream()), "aesr_conv2d_fwd_ws")
-                    _pe()
-                elif s.cin <= 4:
-                    check(lib.aesr_conv2d_smallcin_fwd(ptr(cur), ptr(s.mod.weight), ptr(bias), None, ptr(out), N, H, W,
-                                                       s.cin, s.cout, s.ks, s.pad, act_k, _hip.ACT_NONE, s.slope, 0, 0,
-                                                       None, None, stream()), "aesr_conv2d_smallcin_fwd")
-                else:
-                    raise NotImplementedError("conv with Cin=%d (neither <=4 nor a multiple of 4)" % s.cin)
-                if save:
-                    saved.append((cur, out, full_hw) if s.s2d else (cur, out))
-                if TRACE is not None and not skip:
-                    TRACE.append((self.seq, s.mod, act_k, out))
-                cur, H, W, C = out, Ho, Wo, s.cout
-            elif s.kind == "resample":
-                if C % 4 != 0:
-                    raise NotImplementedError("stand-alone pooling / upsampling of %d channels (needs a multiple of 4)" % C)
-                Ho, Wo = s.out_hw(H, W)
-                out = _empty((N, Ho, Wo, C), x)
-                check(lib.aesr_resample2_fwd(ptr(cur), ptr(out), N, H, W, C, s.mode, stream()), "aesr_resample2_fwd")
-                if save:
-                    saved.append((cur,))
-                cur, H, W = out, Ho, Wo
-            else:
-                bn = s.mod
-                Ho, Wo = s.out_hw(H, W)
-                out = _empty((N, Ho, Wo, C), x)
-                m = _empty((N, Ho, Wo, C), x) if self._bn_pool_once(bn, N, H, W, C, s.run_mode, G, train) else None
-                _pb("bn_fwd", 0.0, 4.0 * (cur.numel() + out.numel() + (0 if m is None else m.numel())))
-                st = self._bn_forward_stats(bn, cur, N, H, W, C, nstart, train, out, s.run_mode, m)
-                if not st.pop("applied", False):
-                    check(lib.aesr_bn_apply(ptr(cur), ptr(st["scale"]), ptr(st["shift"]), ptr(out), N, H, W, C, s.run_mode, G,
-                                            _hip.int_array(nstart), stream()), "aesr_bn_apply")
-                _pe()
-                if save:
-                    saved.append((cur, st))
-                cur, H, W = out, Ho, Wo
+        saved, cur, k = [], x, 0
+        while k < len(steps):
+            s = steps[k]
+            raw = raw_last and k == len(steps) - 1 and s.kind == "conv"
+            # ``took`` 2: a BatchNorm that went into the epilogue of the convolution in front of it (eval mode)
+            cur, keep, took = self._FORWARD[s.kind](self, s, cur, f, steps[k + 1] if k + 1 < len(steps) else None, raw)
+            if save:
+                saved.append(keep)
+            if TRACE is not None and took == 1 and s.kind in ("conv", "stemconv"):
+                TRACE.append((self.seq, s.mod, _hip.ACT_NONE if raw else s.act, cur))
+            k += took
         return cur, saved, steps
 
     def max_elems_per_image(self, H, W, C, first=0, last=None):
@@ -534,149 +551,37 @@ class SequentialRunner:
         """(largest activation tensor in elements per image, (H, W, C) of the output) of a pass over ``steps[first:last]``."""
         best = H * W * C
         for s in self.steps[first:last]:
-            if s.kind == "conv":
-                if s.s2d:
-                    H, W = H // 2, W // 2
-                elif s.in_up2:
-                    H, W = 2 * H, 2 * W
-                    H, W = s.out_hw(H, W)
-                else:
-                    H, W = s.out_hw(H, W)
-                C = s.cout
-            elif s.kind == "stemconv":
-                H, W = s.out_hw(H, W)
-                C = s.cout
-            else:
-                H, W = s.out_hw(H, W)
+            H, W, C = s.out_shape(H, W, C)
             best = max(best, H * W * C)
         return best, (H, W, C)
 
-    def _bn_barrier(self, dev):
-        """Grid-barrier state of this runner's one-launch BatchNorm kernels (csrc/bn_fused.hip): zeroed once, then owned by the kernels.
-        Created by an eager step (a tensor born inside a graph capture would live in the graph's pool and be zeroed by every replay)."""
-        t = self.__dict__.get("_bn_bar")
-        if t is None or t.device != torch.device(dev):
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("one-launch BatchNorm: run the pass eagerly once before capturing it into a HIP graph")
-            t = self._bn_bar = torch.zeros((int(lib.aesr_bn_fused1_barrier_words()),), device=dev, dtype=torch.int32)
-        return t
+    def backward(self, gout, saved, nstart, ngrad, need_input_grad, steps=None):
+        """gout: NHWC gradient of the pass output (all N images; only the first ``ngrad`` are used).
+        Returns (dx or None, {param: grad})."""
+        steps = self.steps if steps is None else steps
+        G = 0
+        while G < len(nstart) - 1 and nstart[G + 1] <= ngrad:
+            G += 1
+        if G == 0 or nstart[G] != ngrad:
+            raise RuntimeError("the images that need gradients must be whole leading statistic groups")
+        g = gout[:ngrad].contiguous()
+        # reduce_jobs: (job, workspace, dw, db, direct): the tensors stay referenced until the reduction has been enqueued
+        b = BackwardPass(ngrad, list(nstart[:G + 1]), {}, [], need_input_grad)
+        for k in range(len(steps) - 1, -1, -1):
+            g = self._BACKWARD[steps[k].kind](self, steps, k, saved, g, b)
+            if g is None:          # nothing in front of this step needs a gradient
+                break
+        if _DEFERRED is not None:
+            # only reductions that write straight into ``p.grad`` may wait for the end of the sweep (ONE launch for all passes,
+            # deferred_wgrad_reductions).  A destination that is a temporary goes back to autograd when this function returns, and
+            # autograd adds it to ``p.grad`` at once: it must be complete NOW (a parameter differentiated by a second pass of the
+            # sweep, an optimizer other than HipAdam, gradients that were not freshly zeroed)
+            _DEFERRED.extend(j for j in b.reduce_jobs if j[4])
+            flush_wgrad_reductions([j for j in b.reduce_jobs if not j[4]])
+        else:
+            flush_wgrad_reductions(b.reduce_jobs)
+        return g, b.grads
 
-    sync_p2p = None     # optional parallel.PeerExchange: the SyncBN exchange inside the one-launch BatchNorm kernels (AESR_SYNCBN=p2p)
-
-    def _p2p_fits(self, N, H, W, C, run_mode, G, backward):
-        """Data parallel with the peer exchange: does this BatchNorm call take the one-launch kernel?  Decided on the LARGEST shard of
-        the step (uneven shards), so that every rank answers the same -- a rank in the kernel would wait for a rank in the all-reduce."""
-        p = self.sync_p2p
-        if p is None or not bn_fused_enabled():
-            return False
-        nmax = max(N, int(round(N * p.nscale)))
-        # big layers are not for the one-launch kernel: it streams at 1.7-1.8 TB/s, and with the 18.9 MB second BatchNorm of a 2-triplet C4 shard
-        # (6 x 111 x 111 x 64) in it the rank step read 3.13 instead of 2.65 ms unprofiled -- not as kernel time under rocprofv3, where kernels do
-        # not overlap at their boundaries: its 256 workgroups of ~140 KB LDS each can only start once the previous kernel has left EVERY CU, and the
-        # early ones spin at the grid barrier meanwhile (profiles/r05_p2p_c4_layer_cap.txt).  Above AESR_P2P_MAX_MB (12) a call keeps the all-reduce
-        # form.  Decided on the largest shard of the step, like the fit, so that every rank answers alike.
-        if float(nmax) * H * W * C * 4.0 > float(os.environ.get("AESR_P2P_MAX_MB", "12")) * 1e6:
-            return False
-        return bool(lib.aesr_bn_fused1_supported(nmax, H, W, C, run_mode, G, backward))
-
-    sync_bn = None      # optional callable(sums[G,2,C] double) -> all-reduced in place across ranks (data parallel SyncBN)
-    count_scale = 1.0   # data parallel: global / local sub-batch size (B_global / B_local of this rank)
-
-    def _bn_one_launch(self, N, H, W, C, run_mode, G, backward):
-        """Single process: does this BatchNorm call take the one-launch kernel (csrc/bn_fused.hip)?"""
-        return bool(self.sync_bn is None and bn_fused_enabled() and bn_fused_pays(N, H, W, C)
-                    and lib.aesr_bn_fused1_supported(N, H, W, C, run_mode, G, backward))
-
-    def _bn_pool_once(self, bn, N, H, W, C, run_mode, G, train):
-        """Does this forward call pool once in its statistics pass (``BN_POOL_ONCE``)?  Only the single-process three-launch route with batch
-        statistics and AvgPool2d(2) behind it; SyncBN, the one-launch form, eval mode and the other modes stay as they are."""
-        if not BN_POOL_ONCE or run_mode != _hip.BN_POOL or self.sync_bn is not None or not (train or bn.running_mean is None):
-            return False
-        return not self._bn_one_launch(N, H, W, C, run_mode, G, 0) and bool(lib.aesr_bn_pool_supported(N, H, W, C, G))
-
-    def _bn_forward_stats(self, bn, y, N, H, W, C, nstart, train, out=None, run_mode=0, m=None):
-        """Statistics of a BatchNorm call -> {mean, invstd, scale, shift, counts}.  Data parallel (``sync_bn``) with ``out`` given: the
-        finalize runs inside the apply launch (``"applied": True`` in the result -- the caller must not apply again).  ``m`` (the caller asked
-        ``_bn_pool_once``): the pooled-once route, which fills ``m`` and ``out``; ``m`` stays in the result for the backward pass."""
-        G = len(nstart) - 1
-        dev = y.device
-        st = {k: torch.empty((G, C), device=dev, dtype=torch.float32) for k in ("mean", "invstd", "scale", "shift")}
-        use_batch = train or bn.running_mean is None
-        momentum = 0.1 if bn.momentum is None else float(bn.momentum)
-        update = bool(train and bn.track_running_stats and bn.running_mean is not None)
-        if update:
-            self._bn_updates = getattr(self, "_bn_updates", 0) + 1       # the kernels write the running statistics through raw pointers
-        if not use_batch:
-            # eval mode: scale / shift follow from the running statistics alone -- computed once per state of the layer, not once per call
-            # (slice synthesis runs 6 BatchNorm calls per volume: 6 launches of a few hundred threads each)
-            ver = lambda t: (-1, 0) if t is None else (t._version, t.data_ptr())         # affine=False: no weight / bias
-            key = (self.weights_epoch, getattr(self, "_bn_updates", 0), ver(bn.weight), ver(bn.bias), ver(bn.running_mean), ver(bn.running_var),
-                   G, str(dev))
-            cache = self.__dict__.setdefault("_eval_bn", {})
-            hit = cache.get(id(bn))
-            if hit is not None and hit[0] == key and not torch.cuda.is_current_stream_capturing():
-                return dict(hit[1])
-        sums = None
-        counts = [float((nstart[g + 1] - nstart[g]) * H * W) * self.count_scale for g in range(G)] if use_batch else None   # host values
-        st["counts"] = counts
-        if use_batch:
-            partial = torch.empty((G * _hip.BN_NWG * 2 * C,), device=dev, dtype=torch.float32)
-            local = out is not None and self._bn_one_launch(N, H, W, C, run_mode, G, 0)
-            if local or (self.sync_bn is not None and out is not None and self._p2p_fits(N, H, W, C, run_mode, G, 0)):
-                # small batch: statistics, finalize and apply in ONE launch, the layer resident in LDS in between.  Data parallel with the peer
-                # exchange: the same launch; workgroup 0 writes this rank's sums into every rank's region and every workgroup adds all
-                # ranks' sums in rank order before it normalises
-                ws = torch.empty((lib.aesr_bn_fused1_workspace_floats(C, G),), device=dev, dtype=torch.float32)
-                args = (ptr(y), ptr(out), ptr(ws), ptr(self._bn_barrier(dev)), _hip.double_array(counts), ptr(bn.weight), ptr(bn.bias),
-                        ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked), ptr(st["mean"]), ptr(st["invstd"]),
-                        ptr(st["scale"]), ptr(st["shift"]), N, H, W, C, run_mode, G, _hip.int_array(nstart), momentum, float(bn.eps), int(update))
-                if local:
-                    check(lib.aesr_bn_fused1_fwd(*args, stream()), "aesr_bn_fused1_fwd")
-                else:
-                    p = self.sync_p2p
-                    check(lib.aesr_bn_fused1_fwd_p2p(*args, p.peers, p.world, p.rank, p.next_slot(), ptr(p.gen), stream()), "aesr_bn_fused1_fwd_p2p")
-                st["applied"] = True
-                return st
-            if m is not None:               # single process, AvgPool2d(2) behind: the statistics pass pools, the apply streams the means
-                nsa = _hip.int_array(nstart)
-                check(lib.aesr_bn_pool_stats_finalize(ptr(y), ptr(m), ptr(partial), _hip.double_array(counts), ptr(bn.weight), ptr(bn.bias),
-                                                      ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked),
-                                                      ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]), ptr(st["shift"]), N, H, W, C,
-                                                      G, nsa, momentum, float(bn.eps), int(update), stream()),
-                      "aesr_bn_pool_stats_finalize")
-                check(lib.aesr_bn_pool_apply(ptr(m), ptr(st["scale"]), ptr(st["shift"]), ptr(out), N, H // 2, W // 2, C, G, nsa, stream()),
-                      "aesr_bn_pool_apply")
-                st["m"] = m
-                st["applied"] = True
-                return st
-            if self.sync_bn is None:        # single process: statistics -> finalize without the sums round trip
-                check(lib.aesr_bn_stats_finalize(ptr(y), ptr(partial), _hip.double_array(counts), ptr(bn.weight), ptr(bn.bias),
-                                                 ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked),
-                                                 ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]), ptr(st["shift"]), H * W, C,
-                                                 G, _hip.int_array(nstart), momentum, float(bn.eps), int(update), stream()),
-                      "aesr_bn_stats_finalize")
-                return st
-            sums = torch.empty((G, 2, C), device=dev, dtype=torch.float64)
-            check(lib.aesr_bn_stats(ptr(y), ptr(partial), ptr(sums), H * W, C, G, _hip.int_array(nstart), stream()),
-                  "aesr_bn_stats")
-            self.sync_bn(sums)
-            if out is not None and lib.aesr_bn_fused_supported(C, G):
-                check(lib.aesr_bn_finalize_apply(ptr(sums), _hip.double_array(counts), ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
-                                                 ptr(bn.running_var), ptr(bn.num_batches_tracked), ptr(st["mean"]), ptr(st["invstd"]),
-                                                 ptr(st["scale"]), ptr(st["shift"]), ptr(y), ptr(out), N, H, W, C, run_mode, G,
-                                                 _hip.int_array(nstart), momentum, float(bn.eps), int(update), stream()),
-                      "aesr_bn_finalize_apply")
-                st["applied"] = True
-                return st
-        check(lib.aesr_bn_finalize(ptr(sums), _hip.double_array(counts) if counts else None, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
-                                   ptr(bn.running_var), ptr(bn.num_batches_tracked), ptr(st["mean"]), ptr(st["invstd"]),
-                                   ptr(st["scale"]), ptr(st["shift"]), C, G, momentum, float(bn.eps), int(use_batch),
-                                   int(update), stream()), "aesr_bn_finalize")
-        if not use_batch and not torch.cuda.is_current_stream_capturing():
-            self.__dict__.setdefault("_eval_bn", {})[id(bn)] = (key, dict(st))
-        return st
-
-    # ---- backward --------------------------------------------------------------------------------------------
     @staticmethod
     def _grad_dst(p, grads):
         """Where a parameter gradient is written: straight into ``p.grad`` when that buffer is known to be freshly zeroed
@@ -685,233 +590,361 @@ class SequentialRunner:
             p._aesr_grad_fresh = False
             grads[p] = None
             return p.grad
-        t = torch.empty_like(p)
-        grads[p] = t
+        grads[p] = torch.empty_like(p)
+        return grads[p]
+
+    @staticmethod
+    def _mask_of(steps, k, saved):
+        """(mask tensor or None, activation, slope): the derivative a data gradient applies for the step in front of step k -- the
+        activation of a convolution there, taken from that convolution's saved output (none in front of step 0: a convolution, compile_steps)"""
+        prev = steps[k - 1] if k > 0 else None
+        if prev is None or prev.kind not in ("conv", "stemconv") or prev.act == _hip.ACT_NONE:
+            return None, _hip.ACT_NONE, 0.0
+        return saved[k - 1][1], prev.act, prev.slope
+
+    # ---- the folded encoder stem -----------------------------------------------------------------------------
+    def _stemconv_forward(self, s, cur, f, nxt, raw):
+        N, H, W, C = cur.shape
+        if C != 1:
+            raise RuntimeError("channel mismatch: tensor has %d channels, the stem expects 1" % C)
+        out = _empty((N,) + s.out_shape(H, W, C), cur)
+        launch("aesr_stemconv_fwd", ptr(cur), ptr(s.folded), ptr(s.mod.bias), ptr(out), N, H, W, s.cout, s.stem_pad, s.act, s.slope,
+               kind="thin_expand", nbytes=4.0 * (cur.numel() + out.numel()))
+        return out, (cur, out), 1
+
+    def _stemconv_backward(self, steps, k, saved, g, b):
+        s = steps[k]
+        if b.need_input_grad:
+            raise RuntimeError("the stem-folded pass has no input gradient (run the pass with fused=False)")
+        xin, (_, H, W, _) = saved[k][0], saved[k][0].shape
+        dws, dbs = self._grad_dst(s.stem.weight, b.grads), self._grad_dst(s.stem.bias, b.grads)
+        dw1 = self._grad_dst(s.mod.weight, b.grads)
+        db1 = self._grad_dst(s.mod.bias, b.grads) if s.mod.bias is not None else None
+        ws = _empty((lib.aesr_stemconv_workspace_floats(s.cout),), g)
+        launch("aesr_stemconv_wgrad", ptr(xin), ptr(g), ptr(s.stem.weight), ptr(s.stem.bias), ptr(s.mod.weight), ptr(dws), ptr(dbs), ptr(dw1),
+               ptr(db1), ptr(ws), b.ngrad, H, W, s.cs, s.cout, s.stem_pad, kind="thin_reduce", nbytes=4.0 * (b.ngrad * H * W + g.numel()))
+        return None
+
+    # ---- convolutions ------------------------------------------------------------------------------------------
+    def _conv_forward(self, s, cur, f, nxt, raw):
+        N, H, W, C = cur.shape
+        Ho, Wo, _ = s.out_shape(H, W, C)
+        act = _hip.ACT_NONE if raw else s.act
+        full_hw = (H, W)
+        if s.s2d:
+            if C != s.cin_full:
+                raise RuntimeError("channel mismatch: tensor has %d channels, conv expects %d" % (C, s.cin_full))
+            xs = _empty((N, H // 2, W // 2, 4 * C), cur)
+            launch("aesr_space_to_depth2", ptr(cur), ptr(xs), N, H, W, C)
+            cur, H, W, C = xs, H // 2, W // 2, 4 * C
+        if C != s.cin:
+            raise RuntimeError("channel mismatch: tensor has %d channels, conv expects %d" % (C, s.cin))
+        if s.in_up2:
+            H, W = 2 * H, 2 * W                    # the convolution's size; ``cur`` stays at half resolution
+        route = conv_forward_route(s, N, H, W, f, nxt, raw)
+        bias = s.mod.bias
+        wino = dict(kind=("wino", N, Ho, Wo, s.cin, s.cout, 0), flops=2.0 * N * Ho * Wo * s.cout * 9 * s.cin)
+        if route == "fused_eval_bn":
+            # eval mode: BatchNorm is a per-channel affine of the running statistics (cached per layer state) -- it and the pooling
+            # behind it go into this convolution's epilogue; the activation tensor in between is never written
+            st = self._eval_bn_stats(nxt.mod, s.cout, f.G, cur.device)
+            out = _empty((N,) + nxt.out_shape(Ho, Wo, s.cout), cur)
+            launch("aesr_conv2d_wino_fwd_bn", ptr(cur), ptr(s.packed_w), ptr(bias), ptr(st["scale"]), ptr(st["shift"]), ptr(out), N, H, W, s.cin,
+                   s.cout, act, s.slope, int(nxt.run_mode == _hip.BN_POOL), **wino)
+            return out, None, 2
+        out = _empty((N, Ho, Wo, s.cout), cur)
+        if route == "up2":
+            launch("aesr_conv2d_wino_fwd_up2", ptr(cur), ptr(s.packed_w), ptr(bias), ptr(out), N, H, W, s.cin, s.cout, act, s.slope, **wino)
+        elif route == "cout1":
+            launch("aesr_conv2d_cout1_fwd", ptr(cur), ptr(s.mod.weight), ptr(bias), ptr(out), N, H, W, s.cin, act, s.slope,
+                   kind="thin_collapse", nbytes=4.0 * (cur.numel() + out.numel()))
+        elif route == "wino":
+            ws, nws = wino_workspace(cur, N, H, W, s.cin, s.cout, 0)
+            launch("aesr_conv2d_wino_fwd_ws", ptr(cur), ptr(s.packed_w), ptr(bias), ptr(out), ptr(ws), nws, N, H, W, s.cin, s.cout, act, s.slope,
+                   **wino)
+        elif route == "igemm":
+            nws = lib.aesr_conv2d_workspace_floats(N, H, W, s.cin, s.cout, s.ks, s.pad)    # > 0: few, deep work items
+            ws = _empty((nws,), cur) if nws else None
+            launch("aesr_conv2d_fwd_ws", ptr(cur), ptr(s.packed), ptr(bias), ptr(out), ptr(ws), N, H, W, s.cin, s.cout, s.ks, s.pad, act, s.slope,
+                   kind="conv_igemm_f32", flops=2.0 * N * Ho * Wo * s.cout * s.ks * s.ks * s.cin)
+        else:
+            launch("aesr_conv2d_smallcin_fwd", ptr(cur), ptr(s.mod.weight), ptr(bias), None, ptr(out), N, H, W, s.cin, s.cout, s.ks, s.pad,
+                   act, _hip.ACT_NONE, s.slope, 0, 0, None, None)
+        return out, ((cur, out, full_hw) if s.s2d else (cur, out)), 1
+
+    def _conv_dgrad_route(self, steps, k, saved, need_input_grad):
+        """(route, mask, mask activation, slope) of the data gradient of convolution k: ``fused_cout1_bwd`` (which also does the weight
+        gradient), None where nothing in front needs a gradient, else ``conv_dgrad_route``."""
+        s, xin, w = steps[k], saved[k][0], steps[k].mod.weight
+        mask, mask_act, mslope = self._mask_of(steps, k, saved)
+        # the flipped filter was made with the rest of the step's operands (prepare_weights) and the weights have not moved since
+        fresh = s.flipped is not None and s.packed_epoch == (self.weights_epoch, w._version, w.data_ptr())
+        # the one-pass kernel takes the derivative mask from the convolution's own saved input: that must BE the producer's saved output
+        if (FUSE_COUT1_BWD and k == len(steps) - 1 and s.cout1_bwd and (k > 0 or need_input_grad) and fresh
+                and (mask is None or mask.data_ptr() == xin.data_ptr())):
+            return "fused_cout1_bwd", mask, mask_act, mslope
+        if k == 0 and not need_input_grad:
+            return None, mask, mask_act, mslope
+        return conv_dgrad_route(s, mask is not None, fresh), mask, mask_act, mslope
+
+    def _conv_backward(self, steps, k, saved, g, b):
+        s = steps[k]
+        xin, yout = saved[k][0], saved[k][1]
+        N, (_, H, W, _) = b.ngrad, xin.shape
+        if s.in_up2:
+            H, W = 2 * H, 2 * W                    # the convolution's size; xin is the half-resolution tensor
+        Ho, Wo = (H, W) if s.s2d else s.out_hw(H, W)
+        route, mask, mask_act, mslope = self._conv_dgrad_route(steps, k, saved, b.need_input_grad)
+        if route == "fused_cout1_bwd":
+            dw, db = self._grad_dst(s.mod.weight, b.grads), self._grad_dst(s.mod.bias, b.grads)
+            ws = _empty((lib.aesr_conv2d_cout1_bwd_workspace_floats(s.cin),), g)
+            dx = _empty((N, H, W, s.cin), g)
+            launch("aesr_conv2d_cout1_bwd", ptr(xin), ptr(g), ptr(yout) if s.act != _hip.ACT_NONE else None, ptr(s.flipped), ptr(dw), ptr(db),
+                   ptr(dx), ptr(ws), N, H, W, s.cin, s.act, s.slope, mask_act, mslope,
+                   kind="thin_reduce", nbytes=4.0 * (2 * N * H * W * s.cin + 2 * N * H * W))
+            return dx
+        if k == len(steps) - 1 and s.act != _hip.ACT_NONE:
+            dpre = torch.empty_like(g)
+            launch("aesr_act_bwd", ptr(g), ptr(yout), ptr(dpre), g.numel(), s.act, s.slope)
+            g = dpre
+        # -- weight / bias gradient
+        dw_final = self._grad_dst(s.mod.weight, b.grads)
+        dw = torch.empty((s.cout, s.cin, 1, 1), device=g.device) if s.s2d else dw_final
+        db = self._grad_dst(s.mod.bias, b.grads) if s.mod.bias is not None else None
+        wroute = conv_wgrad_route(s, db is not None)
+        if wroute in ("s2d_reduce_now", "partial"):
+            ws = _empty((lib.aesr_conv2d_wgrad_workspace_floats(N, H, W, s.cin, s.cout, s.ks, s.pad),), g)
+            mfma = dict(kind=("wgrad", s.cin, s.cout, s.ks, s.pad), flops=2.0 * N * Ho * Wo * s.cout * s.ks * s.ks * s.cin)
+            if wroute == "s2d_reduce_now":        # its result is re-laid out right below: reduce at once
+                launch("aesr_conv2d_wgrad", ptr(xin), ptr(g), ptr(dw), ptr(db), ptr(ws), N, H, W, s.cin, s.cout, s.ks, s.pad, **mfma)
+            else:
+                # partial slabs now; the slabs of all layers of this pass are summed by ONE launch at the end of the pass
+                launch("aesr_conv2d_wgrad_partial", ptr(xin), ptr(g), ptr(ws), N, H, W, s.cin, s.cout, s.ks, s.pad, int(s.in_up2), **mfma)
+                direct = b.grads[s.mod.weight] is None and (db is None or b.grads[s.mod.bias] is None)
+                b.reduce_jobs.append((_hip.WgradReduceJob(ws.data_ptr(), dw.data_ptr(), db.data_ptr() if db is not None else None,
+                                                          N, H, W, s.cin, s.cout, s.ks, s.pad), ws, dw, db, direct))
+        elif wroute == "smallcin_1x1":
+            ws = _empty((lib.aesr_small_wgrad_workspace_floats(s.cout * (s.cin + 1)),), g)
+            launch("aesr_conv2d_smallcin_wgrad", ptr(xin), ptr(g), ptr(dw), ptr(db), ptr(ws), N, H, W, s.cin, s.cout, s.pad)
+        else:
+            ws = _empty((lib.aesr_conv2d_cout1_workspace_floats(s.cin),), g)
+            launch("aesr_conv2d_cout1_wgrad", ptr(xin), ptr(g), ptr(dw), ptr(db), ptr(ws), N, H, W, s.cin,
+                   kind="thin_reduce", nbytes=4.0 * (N * H * W * s.cin + g.numel()))
+        if s.s2d:       # [Cout, (ky,kx,c)] -> [Cout, c, ky, kx]
+            dw_final.copy_(dw.reshape(s.cout, 2, 2, s.cin_full).permute(0, 3, 1, 2))
+        # -- data gradient (fused with the derivative of the activation that produced our input)
+        if route is None:
+            return None
+        dx = _empty((N, H // 2, W // 2, s.cin) if s.in_up2 else (N, H, W, s.cin), g)
+        wino = dict(kind=("wino", N, H, W, s.cin, s.cout, 1), flops=2.0 * N * H * W * s.cin * 9 * s.cout)
+        if route == "sum2":
+            # adjoint of the folded upsampling: 2x2 block sums of the data gradient, at half resolution (no mask: the
+            # producer is a BatchNorm)
+            launch("aesr_conv2d_wino_dgrad_sum2", ptr(g), ptr(s.packed_wt), ptr(dx), N, H, W, s.cin, s.cout, **wino)
+        elif route == "smallcin":
+            launch("aesr_conv2d_smallcin_dgrad", ptr(g), ptr(s.mod.weight), ptr(dx), N, H, W, s.cin, s.cout, s.ks, s.pad, 0, None)
+        elif route == "wino":
+            ws, nws = wino_workspace(g, N, H, W, s.cin, s.cout, 1)
+            launch("aesr_conv2d_wino_dgrad_ws", ptr(g), ptr(s.packed_wt), ptr(mask), ptr(dx), ptr(ws), nws, N, H, W, s.cin, s.cout, mask_act,
+                   mslope, **wino)
+        elif route == "igemm":
+            nws = lib.aesr_conv2d_dgrad_workspace_floats(N, H, W, s.cin, s.cout, s.ks, s.pad)
+            ws = _empty((nws,), g) if nws else None
+            launch("aesr_conv2d_dgrad_ws", ptr(g), ptr(s.packed_t), ptr(mask), ptr(dx), ptr(ws), N, H, W, s.cin, s.cout, s.ks, s.pad, mask_act,
+                   mslope, kind="conv_igemm_f32", flops=2.0 * N * H * W * s.cin * s.ks * s.ks * s.cout)
+        elif route == "cout1_pre":        # one launch
+            launch("aesr_conv2d_cout1_dgrad_pre", ptr(g), ptr(s.flipped), ptr(mask), ptr(dx), N, H, W, s.cin, mask_act, mslope,
+                   kind="thin_expand", nbytes=4.0 * (g.numel() + dx.numel() * (2 if mask is not None else 1)))
+        elif route == "cout1":            # the kernel flips the filter into a workspace first
+            wsf = _empty((9 * s.cin,), g)
+            launch("aesr_conv2d_cout1_dgrad", ptr(g), ptr(s.mod.weight), ptr(mask), ptr(dx), ptr(wsf), N, H, W, s.cin, mask_act, mslope)
+        else:
+            # data gradient of a tiny-Cout conv == small-Cin forward conv with the flipped/transposed filter
+            launch("aesr_conv2d_smallcin_fwd", ptr(g), ptr(s.mod.weight), None, ptr(mask), ptr(dx), N, Ho, Wo, s.cout, s.cin, s.ks,
+                   s.ks - 1 - s.pad, _hip.ACT_NONE, mask_act, mslope, 1, 0, None, None, what="aesr_conv2d_smallcin_fwd(dgrad)")
+        if s.s2d:
+            if mask is not None:
+                raise NotImplementedError("activation mask in front of a stride-2 convolution")
+            fh, fw = saved[k][2]
+            dfull = _empty((N, fh, fw, s.cin_full), g)
+            launch("aesr_depth_to_space2", ptr(dx), ptr(dfull), N, fh, fw, s.cin_full)
+            dx = dfull
+        return dx
+
+    # ---- stand-alone pooling / upsampling --------------------------------------------------------------------
+    def _resample_forward(self, s, cur, f, nxt, raw):
+        N, H, W, C = cur.shape
+        if C % 4 != 0:
+            raise NotImplementedError("stand-alone pooling / upsampling of %d channels (needs a multiple of 4)" % C)
+        out = _empty((N,) + s.out_shape(H, W, C), cur)
+        launch("aesr_resample2_fwd", ptr(cur), ptr(out), N, H, W, C, s.mode)
+        return out, (cur,), 1
+
+    def _resample_backward(self, steps, k, saved, g, b):
+        _, H, W, C = saved[k][0].shape
+        mask, mask_act, mslope = self._mask_of(steps, k, saved)          # the producer's saved output IS this step's saved input
+        dx = _empty((b.ngrad, H, W, C), g)
+        launch("aesr_resample2_bwd", ptr(g), ptr(mask), ptr(dx), b.ngrad, H, W, C, steps[k].mode, mask_act, mslope)
+        return dx
+
+    # ---- BatchNorm ---------------------------------------------------------------------------------------------
+    sync_bn = None      # optional callable(sums[G,2,C] double) -> all-reduced in place across ranks (data parallel SyncBN)
+    sync_p2p = None     # optional parallel.PeerExchange: the SyncBN exchange inside the one-launch BatchNorm kernels (AESR_SYNCBN=p2p)
+    count_scale = 1.0   # data parallel: global / local sub-batch size (B_global / B_local of this rank)
+    _bn_bar = None      # grid-barrier words of the one-launch kernels: an instance attribute once ``_bn_barrier`` has made them
+
+    def bn_route(self, s, N, H, W, C, G, train, has_out, backward):
+        """How one BatchNorm call of one direction runs; asked once per call and direction (the backward pass decides for itself: it may
+        differentiate fewer images and groups than ran forward).  eval: scale / shift from the running statistics.  Single process:
+        one_launch (small batch: statistics, finalize and apply in ONE launch, the layer resident in LDS in between), pool_once (AvgPool2d(2)
+        behind: the statistics pass pools, the apply streams the means), three_launch (statistics -> finalize without the sums round trip,
+        then apply).  Data parallel: p2p (the one-launch kernels with the peer exchange: workgroup 0 writes this rank's sums into every rank's
+        region and every workgroup adds all ranks' sums in rank order before it normalises), allreduce_fused (forward: statistics,
+        ``sync_bn``, finalize inside the apply launch), allreduce (statistics / reduction, ``sync_bn``, finalize, apply).  ``has_out``: the
+        call also applies; both callers pass True today (the convolution's eval epilogue takes ``_eval_bn_stats`` without asking)."""
+        mode = s.run_mode
+        if not backward and not (train or s.mod.running_mean is None):
+            return "eval"
+        if self.sync_bn is None:
+            if (has_out and bn_fused_enabled() and bn_fused_pays(N, H, W, C)
+                    and lib.aesr_bn_fused1_supported(N, H, W, C, mode, G, int(backward))):
+                return "one_launch"
+            # backward: the caller falls back to three_launch where the forward pass stored no means (another route, the switch off)
+            if mode == _hip.BN_POOL and (backward or BN_POOL_ONCE) and lib.aesr_bn_pool_supported(N, H, W, C, G):
+                return "pool_once"
+            return "three_launch"
+        p = self.sync_p2p
+        if has_out and p is not None and bn_fused_enabled():
+            # decided on the LARGEST shard of the step (uneven shards): every rank must answer alike -- one in the kernel would wait for the others
+            nmax = max(N, int(round(N * p.nscale)))
+            # big layers are not for the one-launch kernel: it streams at 1.7-1.8 TB/s, and with the 18.9 MB second BatchNorm of a 2-triplet C4 shard
+            # (6 x 111 x 111 x 64) in it the rank step read 3.13 instead of 2.65 ms unprofiled -- not as kernel time under rocprofv3, where kernels do
+            # not overlap at their boundaries: its 256 workgroups of ~140 KB LDS each can only start once the previous kernel has left EVERY CU, the
+            # early ones spin at the grid barrier meanwhile (profiles/r05_p2p_c4_layer_cap.txt).  Above AESR_P2P_MAX_MB (12): the all-reduce form.
+            if float(nmax) * H * W * C * 4.0 <= P2P_MAX_MB * 1e6 and lib.aesr_bn_fused1_supported(nmax, H, W, C, mode, G, int(backward)):
+                return "p2p"
+        return "allreduce_fused" if (not backward and has_out and lib.aesr_bn_fused_supported(C, G)) else "allreduce"
+
+    def _bn_barrier(self, dev):
+        """Grid-barrier state of this runner's one-launch BatchNorm kernels (csrc/bn_fused.hip): zeroed once, then owned by the kernels.
+        Created by an eager step (a tensor born inside a graph capture would live in the graph's pool and be zeroed by every replay)."""
+        t = self._bn_bar
+        if t is None or t.device != torch.device(dev):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("one-launch BatchNorm: run the pass eagerly once before capturing it into a HIP graph")
+            t = self._bn_bar = torch.zeros((int(lib.aesr_bn_fused1_barrier_words()),), device=dev, dtype=torch.int32)
         return t
 
-    def backward(self, gout, saved, nstart, ngrad, need_input_grad, steps=None):
-        """gout: NHWC gradient of the pass output (all N images; only the first ``ngrad`` are used).
-        Returns (dx or None, {param: grad})."""
-        steps = self.steps if steps is None else steps
-        grads = {}
-        G = 0
-        while G < len(nstart) - 1 and nstart[G + 1] <= ngrad:
-            G += 1
-        if G == 0 or nstart[G] != ngrad:
-            raise RuntimeError("the images that need gradients must be whole leading statistic groups")
-        ns = list(nstart[:G + 1])
-        g = gout[:ngrad]
-        if not g.is_contiguous():
-            g = g.contiguous()
-        reduce_jobs = []          # (job, workspace, dw, db, direct): the tensors stay referenced until the reduction has been enqueued
-        g = self._backward_steps(steps, saved, g, ngrad, need_input_grad, grads, G, ns, reduce_jobs)
-        if _DEFERRED is not None:
-            # only reductions that write straight into ``p.grad`` may wait for the end of the sweep (ONE launch for all passes,
-            # deferred_wgrad_reductions).  A destination that is a temporary goes back to autograd when this function returns, and
-            # autograd adds it to ``p.grad`` at once: it must be complete NOW (a parameter differentiated by a second pass of the
-            # sweep, an optimizer other than HipAdam, gradients that were not freshly zeroed)
-            _DEFERRED.extend(j for j in reduce_jobs if j[4])
-            flush_wgrad_reductions([j for j in reduce_jobs if not j[4]])
-        else:
-            flush_wgrad_reductions(reduce_jobs)
-        return g, grads
+    @staticmethod
+    def _bn_stats_block(bn, G, C, dev):
+        """(st = {mean, invstd, scale, shift} [G, C] each, the nine pointers of every statistics entry point: parameters, running statistics, st)"""
+        st = {k: torch.empty((G, C), device=dev, dtype=torch.float32) for k in ("mean", "invstd", "scale", "shift")}
+        return st, (ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked), ptr(st["mean"]),
+                    ptr(st["invstd"]), ptr(st["scale"]), ptr(st["shift"]))
 
-    def _backward_steps(self, steps, saved, g, ngrad, need_input_grad, grads, G, ns, reduce_jobs):
-        for k in range(len(steps) - 1, -1, -1):
-            s = steps[k]
-            if s.kind == "stemconv":
-                if need_input_grad:
-                    raise RuntimeError("the stem-folded pass has no input gradient (run the pass with fused=False)")
-                xin = saved[k][0]
-                _, H, W, _ = xin.shape
-                dws, dbs = self._grad_dst(s.stem.weight, grads), self._grad_dst(s.stem.bias, grads)
-                dw1 = self._grad_dst(s.mod.weight, grads)
-                db1 = self._grad_dst(s.mod.bias, grads) if s.mod.bias is not None else None
-                ws = _empty((lib.aesr_stemconv_workspace_floats(s.cout),), g)
-                _pb("thin_reduce", 0.0, 4.0 * (ngrad * H * W + g.numel()))
-                check(lib.aesr_stemconv_wgrad(ptr(xin), ptr(g), ptr(s.stem.weight), ptr(s.stem.bias), ptr(s.mod.weight),
-                                              ptr(dws), ptr(dbs), ptr(dw1), ptr(db1), ptr(ws), ngrad, H, W, s.cs, s.cout,
-                                              s.stem_pad, stream()), "aesr_stemconv_wgrad")
-                _pe()
-                g = None
-                break
-            if s.kind == "conv":
-                xin, yout = saved[k][0], saved[k][1]
-                N, H, W, _ = xin.shape
-                N = ngrad
-                if s.in_up2:
-                    H, W = 2 * H, 2 * W                    # the convolution's size; xin is the half-resolution tensor
-                Ho, Wo = (H, W) if s.s2d else s.out_hw(H, W)
-                if (FUSE_COUT1_BWD and k == len(steps) - 1 and s.cout == 1 and s.ks == 3 and s.pad == 1 and _thin_channels(s.cin)
-                        and not s.s2d and not s.in_up2 and s.mod.bias is not None and (k > 0 or need_input_grad) and s.flipped is not None
-                        and s.packed_epoch == (self.weights_epoch, s.mod.weight._version, s.mod.weight.data_ptr())):
-                    mask_act, mslope = _hip.ACT_NONE, 0.0
-                    if k > 0 and steps[k - 1].kind in ("conv", "stemconv") and steps[k - 1].act != _hip.ACT_NONE:
-                        mask_act, mslope = steps[k - 1].act, steps[k - 1].slope
-                    # the kernel takes the derivative mask from the convolution's own saved input: that must BE the producer's saved output
-                    if mask_act == _hip.ACT_NONE or saved[k - 1][1].data_ptr() == xin.data_ptr():
-                        dw, db = self._grad_dst(s.mod.weight, grads), self._grad_dst(s.mod.bias, grads)
-                        ws = _empty((lib.aesr_conv2d_cout1_bwd_workspace_floats(s.cin),), g)
-                        dx = _empty((N, H, W, s.cin), g)
-                        _pb("thin_reduce", 0.0, 4.0 * (2 * N * H * W * s.cin + 2 * N * H * W))
-                        check(lib.aesr_conv2d_cout1_bwd(ptr(xin), ptr(g), ptr(yout) if s.act != _hip.ACT_NONE else None, ptr(s.flipped), ptr(dw),
-                                                        ptr(db), ptr(dx), ptr(ws), N, H, W, s.cin, s.act, s.slope, mask_act, mslope, stream()),
-                              "aesr_conv2d_cout1_bwd")
-                        _pe()
-                        g = dx
-                        continue
-                if k == len(steps) - 1 and s.act != _hip.ACT_NONE:
-                    dpre = torch.empty_like(g)
-                    check(lib.aesr_act_bwd(ptr(g), ptr(yout), ptr(dpre), g.numel(), s.act, s.slope, stream()), "aesr_act_bwd")
-                    g = dpre
-                # -- weight / bias gradient
-                dw_final = self._grad_dst(s.mod.weight, grads)
-                dw = torch.empty((s.cout, s.cin, 1, 1), device=g.device) if s.s2d else dw_final
-                db = self._grad_dst(s.mod.bias, grads) if s.mod.bias is not None else None
-                if s.cin % 4 == 0 and s.cout % 4 == 0:
-                    nws = lib.aesr_conv2d_wgrad_workspace_floats(N, H, W, s.cin, s.cout, s.ks, s.pad)
-                    ws = _empty((nws,), g)
-                    if s.s2d:        # its result is re-laid out right below: reduce at once
-                        _pb(("wgrad", s.cin, s.cout, s.ks, s.pad), 2.0 * N * Ho * Wo * s.cout * s.ks * s.ks * s.cin)
-                        check(lib.aesr_conv2d_wgrad(ptr(xin), ptr(g), ptr(dw), ptr(db), ptr(ws), N, H, W, s.cin, s.cout, s.ks,
-                                                    s.pad, stream()), "aesr_conv2d_wgrad")
-                        _pe()
-                    else:
-                        # partial slabs now; the slabs of all layers of this pass are summed by ONE launch at the end of the pass
-                        _pb(("wgrad", s.cin, s.cout, s.ks, s.pad), 2.0 * N * Ho * Wo * s.cout * s.ks * s.ks * s.cin)
-                        check(lib.aesr_conv2d_wgrad_partial(ptr(xin), ptr(g), ptr(ws), N, H, W, s.cin, s.cout, s.ks, s.pad,
-                                                            int(s.in_up2), stream()), "aesr_conv2d_wgrad_partial")
-                        _pe()
-                        direct = grads[s.mod.weight] is None and (db is None or grads[s.mod.bias] is None)
-                        reduce_jobs.append((_hip.WgradReduceJob(ws.data_ptr(), dw.data_ptr(), db.data_ptr() if db is not None else None,
-                                                                N, H, W, s.cin, s.cout, s.ks, s.pad), ws, dw, db, direct))
-                elif s.cin <= 4 and s.ks == 1 and db is not None:
-                    ws = _empty((lib.aesr_small_wgrad_workspace_floats(s.cout * (s.cin + 1)),), g)
-                    check(lib.aesr_conv2d_smallcin_wgrad(ptr(xin), ptr(g), ptr(dw), ptr(db), ptr(ws), N, H, W, s.cin, s.cout,
-                                                         s.pad, stream()), "aesr_conv2d_smallcin_wgrad")
-                elif s.cout == 1 and s.ks == 3 and s.pad == 1 and db is not None:
-                    ws = _empty((lib.aesr_conv2d_cout1_workspace_floats(s.cin),), g)
-                    _pb("thin_reduce", 0.0, 4.0 * (N * H * W * s.cin + g.numel()))
-                    check(lib.aesr_conv2d_cout1_wgrad(ptr(xin), ptr(g), ptr(dw), ptr(db), ptr(ws), N, H, W, s.cin, stream()),
-                          "aesr_conv2d_cout1_wgrad")
-                    _pe()
-                else:
-                    raise NotImplementedError("no wgrad kernel for conv %d->%d k%d" % (s.cin, s.cout, s.ks))
-                if s.s2d:       # [Cout, (ky,kx,c)] -> [Cout, c, ky, kx]
-                    dw_final.copy_(dw.reshape(s.cout, 2, 2, s.cin_full).permute(0, 3, 1, 2))
-                # -- data gradient (fused with the derivative of the activation that produced our input)
-                if k == 0 and not need_input_grad:
-                    g = None
-                    break
-                mask, mask_act, mslope = None, _hip.ACT_NONE, 0.0
-                if k > 0 and steps[k - 1].kind in ("conv", "stemconv"):
-                    mask, mask_act, mslope = saved[k - 1][1], steps[k - 1].act, steps[k - 1].slope
-                    if mask_act == _hip.ACT_NONE:
-                        mask = None
-                dx = _empty((N, H // 2, W // 2, s.cin) if s.in_up2 else (N, H, W, s.cin), g)
-                if s.in_up2:
-                    # adjoint of the folded upsampling: 2x2 block sums of the data gradient, at half resolution (no mask: the
-                    # producer is a BatchNorm)
-                    _pb(("wino", N, H, W, s.cin, s.cout, 1), 2.0 * N * H * W * s.cin * 9 * s.cout)
-                    check(lib.aesr_conv2d_wino_dgrad_sum2(ptr(g), ptr(s.packed_wt), ptr(dx), N, H, W, s.cin, s.cout, stream()),
-                          "aesr_conv2d_wino_dgrad_sum2")
-                    _pe()
-                elif s.cin <= 4 and mask is None:
-                    check(lib.aesr_conv2d_smallcin_dgrad(ptr(g), ptr(s.mod.weight), ptr(dx), N, H, W, s.cin, s.cout, s.ks,
-                                                         s.pad, 0, None, stream()), "aesr_conv2d_smallcin_dgrad")
-                elif s.wino_dgrad:
-                    _pb(("wino", N, H, W, s.cin, s.cout, 1), 2.0 * N * H * W * s.cin * 9 * s.cout)
-                    ws, nws = wino_workspace(g, N, H, W, s.cin, s.cout, 1)
-                    check(lib.aesr_conv2d_wino_dgrad_ws(ptr(g), ptr(s.packed_wt), ptr(mask), ptr(dx), ptr(ws), nws, N, H, W, s.cin, s.cout,
-                                                        mask_act, mslope, stream()), "aesr_conv2d_wino_dgrad_ws")
-                    _pe()
-                elif s.cout % 4 == 0:
-                    _pb("conv_igemm_f32", 2.0 * N * H * W * s.cin * s.ks * s.ks * s.cout)
-                    nws = lib.aesr_conv2d_dgrad_workspace_floats(N, H, W, s.cin, s.cout, s.ks, s.pad)
-                    ws = _empty((nws,), g) if nws else None
-                    check(lib.aesr_conv2d_dgrad_ws(ptr(g), ptr(s.packed_t), ptr(mask), ptr(dx), ptr(ws), N, H, W, s.cin, s.cout,
-                                                   s.ks, s.pad, mask_act, mslope, stream()), "aesr_conv2d_dgrad_ws")
-                    _pe()
-                elif s.cout == 1 and s.ks == 3 and s.pad == 1 and _thin_channels(s.cin):
-                    w = s.mod.weight
-                    if s.flipped is not None and s.packed_epoch == (self.weights_epoch, w._version, w.data_ptr()):
-                        # the flipped filter was made with the rest of the step's operands (prepare_weights): one launch
-                        _pb("thin_expand", 0.0, 4.0 * (g.numel() + dx.numel() * (2 if mask is not None else 1)))
-                        check(lib.aesr_conv2d_cout1_dgrad_pre(ptr(g), ptr(s.flipped), ptr(mask), ptr(dx), N, H, W, s.cin, mask_act, mslope,
-                                                              stream()), "aesr_conv2d_cout1_dgrad_pre")
-                        _pe()
-                    else:
-                        wsf = _empty((9 * s.cin,), g)
-                        check(lib.aesr_conv2d_cout1_dgrad(ptr(g), ptr(w), ptr(mask), ptr(dx), ptr(wsf), N, H, W, s.cin,
-                                                          mask_act, mslope, stream()), "aesr_conv2d_cout1_dgrad")
-                elif s.cout <= 4:
-                    # data gradient of a tiny-Cout conv == small-Cin forward conv with the flipped/transposed filter
-                    check(lib.aesr_conv2d_smallcin_fwd(ptr(g), ptr(s.mod.weight), None, ptr(mask), ptr(dx), N, Ho, Wo, s.cout,
-                                                       s.cin, s.ks, s.ks - 1 - s.pad, _hip.ACT_NONE, mask_act, mslope, 1, 0,
-                                                       None, None, stream()), "aesr_conv2d_smallcin_fwd(dgrad)")
-                else:
-                    raise NotImplementedError("no dgrad kernel for conv %d->%d" % (s.cin, s.cout))
-                if s.s2d:
-                    if mask is not None:
-                        raise NotImplementedError("activation mask in front of a stride-2 convolution")
-                    fh, fw = saved[k][2]
-                    dfull = _empty((N, fh, fw, s.cin_full), g)
-                    check(lib.aesr_depth_to_space2(ptr(dx), ptr(dfull), N, fh, fw, s.cin_full, stream()), "aesr_depth_to_space2")
-                    dx = dfull
-                g = dx
-            elif s.kind == "resample":
-                xin = saved[k][0]
-                _, H, W, C = xin.shape
-                prev = steps[k - 1]
-                mask_act, mslope = (prev.act, prev.slope) if prev.kind in ("conv", "stemconv") else (_hip.ACT_NONE, 0.0)
-                dx = _empty((ngrad, H, W, C), g)
-                check(lib.aesr_resample2_bwd(ptr(g), ptr(xin) if mask_act != _hip.ACT_NONE else None, ptr(dx), ngrad, H, W, C,
-                                             s.mode, mask_act, mslope, stream()), "aesr_resample2_bwd")
-                g = dx
+    def _eval_bn_stats(self, bn, C, G, dev):
+        """Eval mode: scale / shift follow from the running statistics alone -- computed once per state of the layer, not once per call
+        (slice synthesis runs 6 BatchNorm calls per volume: 6 launches of a few hundred threads each).  Not while a stream captures: a
+        tensor born in a graph's pool must not outlive the graph through this cache."""
+        ver = lambda t: (-1, 0) if t is None else (t._version, t.data_ptr())         # affine=False: no weight / bias
+        key = (self.weights_epoch, self._bn_updates, ver(bn.weight), ver(bn.bias), ver(bn.running_mean), ver(bn.running_var), G, str(dev))
+        capturing = torch.cuda.is_current_stream_capturing()
+        hit = self._eval_bn.get(id(bn))
+        if hit is not None and hit[0] == key and not capturing:
+            return dict(hit[1])
+        st, block = self._bn_stats_block(bn, G, C, dev)
+        st["counts"] = None
+        launch("aesr_bn_finalize", None, None, *block, C, G, 0.1 if bn.momentum is None else float(bn.momentum), float(bn.eps), 0, 0)
+        if not capturing:
+            self._eval_bn[id(bn)] = (key, dict(st))
+        return st
+
+    def _bn_forward(self, s, cur, f, nxt, raw):
+        bn, mode, G, dev = s.mod, s.run_mode, f.G, cur.device
+        N, H, W, C = cur.shape
+        out = _empty((N,) + s.out_shape(H, W, C), cur)
+        route = self.bn_route(s, N, H, W, C, G, f.train, True, False)
+        m = torch.empty_like(out) if route == "pool_once" else None
+        with profiled("bn_fwd", 0.0, 4.0 * (cur.numel() + out.numel() + (0 if m is None else m.numel()))):
+            if route == "eval":
+                st = self._eval_bn_stats(bn, C, G, dev)
             else:
-                y, st = saved[k]
-                prev = steps[k - 1]
-                _, H, W, C = y.shape
-                N = ngrad
-                dev = y.device
-                partial = torch.empty((G * _hip.BN_NWG * 2 * C,), device=dev, dtype=torch.float32)
-                nsa = _hip.int_array(ns)
-                coef = torch.empty((G, 2, C), device=dev, dtype=torch.float32)
-                dgamma, dbeta = self._grad_dst(s.mod.weight, grads), self._grad_dst(s.mod.bias, grads)
-                dpre = _empty((N, H, W, C), y)
-                local = self._bn_one_launch(N, H, W, C, s.run_mode, G, 1)
-                # the forward pass pooled once and kept the means: the reduction streams them and the pooled gradient instead of y
-                m = st.get("m") if (self.sync_bn is None and not local and lib.aesr_bn_pool_supported(N, H, W, C, G)) else None
-                _pb("bn_bwd", 0.0, 4.0 * (g.numel() + 2.0 * N * H * W * C + (0 if m is None else g.numel())))
-                if local or (self.sync_bn is not None and self._p2p_fits(N, H, W, C, s.run_mode, G, 1)):
+                st, block = self._bn_stats_block(bn, G, C, dev)
+                update = bool(f.train and bn.track_running_stats and bn.running_mean is not None)
+                if update:
+                    self._bn_updates += 1       # the kernels write the running statistics through raw pointers
+                st["counts"] = [float((f.nstart[g + 1] - f.nstart[g]) * H * W) * self.count_scale for g in range(G)]   # host values
+                counts, nsa = _hip.double_array(st["counts"]), _hip.int_array(f.nstart)
+                tail = (0.1 if bn.momentum is None else float(bn.momentum), float(bn.eps), int(update))
+                if route in ("one_launch", "p2p"):
                     ws = torch.empty((lib.aesr_bn_fused1_workspace_floats(C, G),), device=dev, dtype=torch.float32)
-                    args = (ptr(g), ptr(y), ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]), ptr(ws), ptr(self._bn_barrier(dev)),
-                            _hip.double_array(st["counts"][:G]), ptr(coef), ptr(dgamma), ptr(dbeta), ptr(dpre), N, H, W, C, s.run_mode, prev.act,
-                            prev.slope, G, nsa)
-                    if local:
-                        check(lib.aesr_bn_fused1_bwd(*args, stream()), "aesr_bn_fused1_bwd")
+                    args = (ptr(cur), ptr(out), ptr(ws), ptr(self._bn_barrier(dev)), counts) + block + (N, H, W, C, mode, G, nsa) + tail
+                    if route == "one_launch":
+                        launch("aesr_bn_fused1_fwd", *args)
                     else:
                         p = self.sync_p2p
-                        check(lib.aesr_bn_fused1_bwd_p2p(*args, p.peers, p.world, p.rank, p.next_slot(), ptr(p.gen), stream()), "aesr_bn_fused1_bwd_p2p")
-                elif m is not None:
-                    check(lib.aesr_bn_pool_bwd(ptr(g), ptr(y), ptr(m), ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]), ptr(partial),
-                                               _hip.double_array(st["counts"][:G]), ptr(coef), ptr(dgamma), ptr(dbeta), ptr(dpre), N, H, W,
-                                               C, prev.act, prev.slope, G, nsa, stream()), "aesr_bn_pool_bwd")
-                elif self.sync_bn is None:
-                    check(lib.aesr_bn_bwd(ptr(g), ptr(y), ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]), ptr(partial),
-                                          _hip.double_array(st["counts"][:G]), ptr(coef), ptr(dgamma), ptr(dbeta), ptr(dpre), N, H, W,
-                                          C, s.run_mode, prev.act, prev.slope, G, nsa, stream()), "aesr_bn_bwd")
+                        launch("aesr_bn_fused1_fwd_p2p", *args, p.peers, p.world, p.rank, p.next_slot(), ptr(p.gen))
+                else:
+                    partial = torch.empty((G * _hip.BN_NWG * 2 * C,), device=dev, dtype=torch.float32)
+                    if route == "pool_once":
+                        launch("aesr_bn_pool_stats_finalize", ptr(cur), ptr(m), ptr(partial), counts, *block, N, H, W, C, G, nsa, *tail)
+                        launch("aesr_bn_pool_apply", ptr(m), ptr(st["scale"]), ptr(st["shift"]), ptr(out), N, H // 2, W // 2, C, G, nsa)
+                        st["m"] = m         # kept for the backward pass
+                    elif route == "three_launch":
+                        launch("aesr_bn_stats_finalize", ptr(cur), ptr(partial), counts, *block, H * W, C, G, nsa, *tail)
+                    else:
+                        sums = torch.empty((G, 2, C), device=dev, dtype=torch.float64)
+                        launch("aesr_bn_stats", ptr(cur), ptr(partial), ptr(sums), H * W, C, G, nsa)
+                        self.sync_bn(sums)
+                        if route == "allreduce_fused":
+                            launch("aesr_bn_finalize_apply", ptr(sums), counts, *block, ptr(cur), ptr(out), N, H, W, C, mode, G, nsa, *tail)
+                        else:
+                            launch("aesr_bn_finalize", ptr(sums), counts, *block, C, G, tail[0], tail[1], 1, tail[2])
+            if route in ("eval", "three_launch", "allreduce"):
+                launch("aesr_bn_apply", ptr(cur), ptr(st["scale"]), ptr(st["shift"]), ptr(out), N, H, W, C, mode, G, _hip.int_array(f.nstart))
+        return out, (cur, st), 1
+
+    def _bn_backward(self, steps, k, saved, g, b):
+        s, prev = steps[k], steps[k - 1]
+        y, st = saved[k]
+        N, (_, H, W, C), G, dev = b.ngrad, y.shape, len(b.ns) - 1, y.device
+        route = self.bn_route(s, N, H, W, C, G, True, True, True)
+        # the forward pass pooled once and kept the means: the reduction streams them and the pooled gradient instead of y
+        m = st.get("m") if route == "pool_once" else None
+        if route == "pool_once" and m is None:
+            route = "three_launch"
+        coef = torch.empty((G, 2, C), device=dev, dtype=torch.float32)
+        dgamma, dbeta = self._grad_dst(s.mod.weight, b.grads), self._grad_dst(s.mod.bias, b.grads)
+        dpre = _empty((N, H, W, C), y)
+        # what the backward entry points share, in the order of their signatures (include/aesr_hip.h), around the one or two arguments of their own:
+        # head = dy, y, mean, invstd, scale; mid = counts, coef, dgamma, dbeta, dx, N, H, W, C; tail = act, slope, G, nstart (mode stands before it)
+        head = (ptr(g), ptr(y), ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]))
+        mid = (_hip.double_array(st["counts"][:G]), ptr(coef), ptr(dgamma), ptr(dbeta), ptr(dpre), N, H, W, C)
+        tail = (prev.act, prev.slope, G, _hip.int_array(b.ns))
+        with profiled("bn_bwd", 0.0, 4.0 * (g.numel() + 2.0 * N * H * W * C + (0 if m is None else g.numel()))):
+            if route in ("one_launch", "p2p"):
+                ws = torch.empty((lib.aesr_bn_fused1_workspace_floats(C, G),), device=dev, dtype=torch.float32)
+                args = head + (ptr(ws), ptr(self._bn_barrier(dev))) + mid + (s.run_mode,) + tail
+                if route == "one_launch":
+                    launch("aesr_bn_fused1_bwd", *args)
+                else:
+                    p = self.sync_p2p
+                    launch("aesr_bn_fused1_bwd_p2p", *args, p.peers, p.world, p.rank, p.next_slot(), ptr(p.gen))
+            else:
+                partial = torch.empty((G * _hip.BN_NWG * 2 * C,), device=dev, dtype=torch.float32)
+                if route == "pool_once":
+                    launch("aesr_bn_pool_bwd", *head[:2], ptr(m), *head[2:], ptr(partial), *mid, *tail)
+                elif route == "three_launch":
+                    launch("aesr_bn_bwd", *head, ptr(partial), *mid, s.run_mode, *tail)
                 else:
                     sums = torch.empty((G, 2, C), device=dev, dtype=torch.float64)
-                    check(lib.aesr_bn_bwd_reduce(ptr(g), ptr(y), ptr(st["mean"]), ptr(st["invstd"]), ptr(partial), ptr(sums), N,
-                                                 H, W, C, s.run_mode, G, nsa, stream()), "aesr_bn_bwd_reduce")
+                    launch("aesr_bn_bwd_reduce", *head[:4], ptr(partial), ptr(sums), N, H, W, C, s.run_mode, G, tail[3])
                     self.sync_bn(sums)
-                    check(lib.aesr_bn_bwd_apply(ptr(g), ptr(y), ptr(st["mean"]), ptr(st["invstd"]), ptr(st["scale"]), ptr(sums),
-                                                _hip.double_array(st["counts"][:G]), ptr(coef), ptr(dgamma), ptr(dbeta), ptr(dpre),
-                                                N, H, W, C, s.run_mode, prev.act, prev.slope, G, nsa, stream()), "aesr_bn_bwd_apply")
-                _pe()
-                g = dpre
-        return g
+                    launch("aesr_bn_bwd_apply", *head, ptr(sums), *mid, s.run_mode, *tail)
+        return dpre
+
+    _FORWARD = {"stemconv": _stemconv_forward, "conv": _conv_forward, "bn": _bn_forward, "resample": _resample_forward}
+    _BACKWARD = {"stemconv": _stemconv_backward, "conv": _conv_backward, "bn": _bn_backward, "resample": _resample_backward}
 
 
 def prepare_weights(pairs):
@@ -925,9 +958,7 @@ def prepare_weights(pairs):
         commits += c
     if jobs:
         arr = (_hip.PrepJob * len(jobs))(*jobs)
-        _pb("prep_many", 0.0, 0.0)
-        check(lib.aesr_weight_prep_many(arr, len(jobs), stream()), "aesr_weight_prep_many")
-        _pe()
+        launch("aesr_weight_prep_many", arr, len(jobs), kind="prep_many")
     for c in commits:
         c()
 
@@ -939,9 +970,7 @@ def flush_wgrad_reductions(jobs):
     for k in range(0, len(jobs), _hip.REDUCE_MAX_JOBS):
         part = jobs[k:k + _hip.REDUCE_MAX_JOBS]
         arr = (_hip.WgradReduceJob * len(part))(*[j[0] for j in part])
-        _pb("wgrad_reduce_many", 0.0, 4.0 * sum(j[1].numel() + j[2].numel() for j in part))
-        check(lib.aesr_conv2d_wgrad_reduce_many(arr, len(part), stream()), "aesr_conv2d_wgrad_reduce_many")
-        _pe()
+        launch("aesr_conv2d_wgrad_reduce_many", arr, len(part), kind="wgrad_reduce_many", nbytes=4.0 * sum(j[1].numel() + j[2].numel() for j in part))
 
 
 class deferred_wgrad_reductions(object):

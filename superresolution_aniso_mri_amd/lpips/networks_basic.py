@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from .. import _hip, engine
-from .._hip import check, lib, ptr, stream
+from .._hip import lib, ptr
 from .synthetic_vgg import VGG16_CFG, conv_indices, synthetic_vgg16_state
 
 SHIFT = (-.030, -.088, -.188)
@@ -153,10 +153,10 @@ class PNetLin(nn.Module):
                 if wino:
                     buf = torch.empty(lib.aesr_conv2d_wino_packed_floats(cout, cin, transpose), device=w.device)
                     job = (_hip.PackJob * 1)(_hip.PackJob(w.data_ptr(), buf.data_ptr(), cout, cin, 3, transpose))
-                    check(lib.aesr_conv2d_wino_pack_many(job, 1, stream()), "aesr_conv2d_wino_pack_many")
+                    engine.launch("aesr_conv2d_wino_pack_many", job, 1)
                 else:
                     buf = torch.empty(lib.aesr_conv2d_packed_floats(cout, cin, 3, transpose), device=w.device)
-                    check(lib.aesr_conv2d_pack(ptr(w), ptr(buf), cout, cin, 3, transpose, stream()), "aesr_conv2d_pack")
+                    engine.launch("aesr_conv2d_pack", ptr(w), ptr(buf), cout, cin, 3, transpose)
                 pk[key].append(buf)
                 pk[key + "_wino"].append(wino)
         for k, l in enumerate(self.lins):
@@ -214,17 +214,14 @@ class PNetLin(nn.Module):
         cur = torch.empty((N, H, W, 64), device=x.device)
         if FOLD_CONV1_1:
             folded, _ = self._conv1_1_folded(pk, mul, add)
-            engine._pb("thin_expand", 0.0, 4.0 * (x.numel() + cur.numel()))
-            check(lib.aesr_stemconv_fwd(ptr(x), ptr(folded), ptr(c0.bias), ptr(cur), N, H, W, 64, 0, _hip.ACT_RELU, 0.0, stream()),
-                  "aesr_stemconv_fwd(vgg conv1_1)")
-            engine._pe()
+            engine.launch("aesr_stemconv_fwd", ptr(x), ptr(folded), ptr(c0.bias), ptr(cur), N, H, W, 64, 0, _hip.ACT_RELU, 0.0,
+                          kind="thin_expand", nbytes=4.0 * (x.numel() + cur.numel()), what="aesr_stemconv_fwd(vgg conv1_1)")
         else:
             ca, cb = self._affine(mul, add)
             x4 = torch.empty((N, H, W, 4), device=x.device)
-            check(lib.aesr_scale_expand_fwd(ptr(x), ptr(x4), N * H * W, _hip.float_array(ca), _hip.float_array(cb), stream()),
-                  "aesr_scale_expand_fwd")
-            check(lib.aesr_conv2d_fwd(ptr(x4), ptr(pk["fwd"][0]), ptr(c0.bias), ptr(cur), N, H, W, 4, 64, 3, 1, _hip.ACT_RELU, 0.0,
-                                      stream()), "aesr_conv2d_fwd(vgg conv1_1)")
+            engine.launch("aesr_scale_expand_fwd", ptr(x), ptr(x4), N * H * W, _hip.float_array(ca), _hip.float_array(cb))
+            engine.launch("aesr_conv2d_fwd", ptr(x4), ptr(pk["fwd"][0]), ptr(c0.bias), ptr(cur), N, H, W, 4, 64, 3, 1, _hip.ACT_RELU, 0.0,
+                          what="aesr_conv2d_fwd(vgg conv1_1)")
         acts.append(cur)
         nconv, h, w, cin = 1, H, W, 64
         partials, hws = [], []
@@ -233,41 +230,36 @@ class PNetLin(nn.Module):
                 if h < 2 or w < 2:
                     raise ValueError("LPIPS-VGG needs images of at least 16x16 pixels")
                 out = torch.empty((N, h // 2, w // 2, cin), device=x.device)
-                engine._pb("maxpool2", 0.0, 4.0 * (cur.numel() + out.numel()))
-                check(lib.aesr_maxpool2_fwd(ptr(cur), ptr(out), N, h, w, cin, stream()), "aesr_maxpool2_fwd")
-                engine._pe()
+                engine.launch("aesr_maxpool2_fwd", ptr(cur), ptr(out), N, h, w, cin, kind="maxpool2", nbytes=4.0 * (cur.numel() + out.numel()))
                 pool_in[nconv] = cur
                 cur, h, w = out, h // 2, w // 2
                 continue
             c = convs[nconv]
             out = torch.empty((N, h, w, v), device=x.device)
             if pk["fwd_wino"][nconv]:
-                engine._pb(("wino", N, h, w, cin, v, 0), 2.0 * N * h * w * v * 9 * cin)
                 ws, nws = engine.wino_workspace(cur, N, h, w, cin, v, 0)
-                check(lib.aesr_conv2d_wino_fwd_ws(ptr(cur), ptr(pk["fwd"][nconv]), ptr(c.bias), ptr(out), ptr(ws), nws, N, h, w, cin, v,
-                                                  _hip.ACT_RELU, 0.0, stream()), "aesr_conv2d_wino_fwd_ws(vgg)")
-                engine._pe()
+                engine.launch("aesr_conv2d_wino_fwd_ws", ptr(cur), ptr(pk["fwd"][nconv]), ptr(c.bias), ptr(out), ptr(ws), nws, N, h, w, cin, v,
+                              _hip.ACT_RELU, 0.0,
+                              kind=("wino", N, h, w, cin, v, 0), flops=2.0 * N * h * w * v * 9 * cin, what="aesr_conv2d_wino_fwd_ws(vgg)")
             else:
                 nws = lib.aesr_conv2d_workspace_floats(N, h, w, cin, v, 3, 1)      # > 0: the small deep layers (conv4/5) get K-split
                 ws = torch.empty((nws,), device=x.device) if nws else None
-                check(lib.aesr_conv2d_fwd_ws(ptr(cur), ptr(pk["fwd"][nconv]), ptr(c.bias), ptr(out), ptr(ws), N, h, w, cin, v, 3, 1,
-                                             _hip.ACT_RELU, 0.0, stream()), "aesr_conv2d_fwd_ws(vgg)")
+                engine.launch("aesr_conv2d_fwd_ws", ptr(cur), ptr(pk["fwd"][nconv]), ptr(c.bias), ptr(out), ptr(ws), N, h, w, cin, v, 3, 1,
+                              _hip.ACT_RELU, 0.0, what="aesr_conv2d_fwd_ws(vgg)")
             cur, cin = out, v
             nconv += 1
             acts.append(cur)
             if nconv in TAP_AFTER_CONV:
                 k = len(taps)
                 part = torch.empty((B, _hip.LPIPS_NCH), device=x.device)
-                engine._pb("lpips_tap", 0.0, 4.0 * cur.numel())
-                check(lib.aesr_lpips_tap_fwd(ptr(cur), ptr(pk["lin"][k]), ptr(part), B, h * w, v, stream()), "aesr_lpips_tap_fwd")
-                engine._pe()
+                engine.launch("aesr_lpips_tap_fwd", ptr(cur), ptr(pk["lin"][k]), ptr(part), B, h * w, v, kind="lpips_tap", nbytes=4.0 * cur.numel())
                 taps.append((cur, h, w, v))
                 partials.append(part)
                 hws.append(h * w)
         d = torch.empty((B,), device=x.device)
         import ctypes
         parr = (ctypes.c_void_p * len(partials))(*[p.data_ptr() for p in partials])
-        check(lib.aesr_lpips_finalize(parr, _hip.int_array(hws), len(partials), ptr(d), B, stream()), "aesr_lpips_finalize")
+        engine.launch("aesr_lpips_finalize", parr, _hip.int_array(hws), len(partials), ptr(d), B)
         saved = (acts, taps, (B, H, W)) if save else None
         if _TRACE is not None:
             _TRACE.append(("acts", list(acts)))
@@ -288,20 +280,17 @@ class PNetLin(nn.Module):
             if n in tap_of:
                 k = tap_of[n]
                 gtap = torch.empty((B, h, w, c), device=dev)
-                engine._pb("lpips_tap", 0.0, 4.0 * (a.numel() + gtap.numel()))
-                check(lib.aesr_lpips_tap_bwd(ptr(a), ptr(pk["lin"][k]), ptr(gd), ptr(gtap), B, h * w, c, stream()), "aesr_lpips_tap_bwd")
-                engine._pe()
+                engine.launch("aesr_lpips_tap_bwd", ptr(a), ptr(pk["lin"][k]), ptr(gd), ptr(gtap), B, h * w, c,
+                              kind="lpips_tap", nbytes=4.0 * (a.numel() + gtap.numel()))
                 if n == 13:
                     g = torch.empty_like(gtap)
-                    engine._pb("act_bwd", 0.0, 12.0 * gtap.numel())
-                    check(lib.aesr_act_bwd(ptr(gtap), ptr(a), ptr(g), gtap.numel(), _hip.ACT_RELU, 0.0, stream()), "aesr_act_bwd")
-                    engine._pe()
+                    engine.launch("aesr_act_bwd", ptr(gtap), ptr(a), ptr(g), gtap.numel(), _hip.ACT_RELU, 0.0,
+                                  kind="act_bwd", nbytes=12.0 * gtap.numel())
                 else:
                     # g currently holds the gradient w.r.t. the pooled tensor feeding conv n+1
                     dpre = torch.empty((B, h, w, c), device=dev)
-                    engine._pb("maxpool2", 0.0, 4.0 * (g.numel() + 3 * dpre.numel()))
-                    check(lib.aesr_maxpool2_bwd(ptr(g), ptr(a), ptr(gtap), ptr(dpre), B, h, w, c, 1, stream()), "aesr_maxpool2_bwd")
-                    engine._pe()
+                    engine.launch("aesr_maxpool2_bwd", ptr(g), ptr(a), ptr(gtap), ptr(dpre), B, h, w, c, 1,
+                                  kind="maxpool2", nbytes=4.0 * (g.numel() + 3 * dpre.numel()))
                     g = dpre
             # now g = d/d(pre-activation of conv n); push it through conv n to its input
             if _TRACE is not None:
@@ -310,18 +299,16 @@ class PNetLin(nn.Module):
                 # data gradient of the folded layer with respect to the 1-channel slice: a 64 -> 1 convolution with the flipped filter
                 _, wflip = self._conv1_1_folded(pk, mul, None)
                 dx = torch.empty((B, H, W, 1), device=dev)
-                engine._pb("thin_collapse", 0.0, 4.0 * (g.numel() + dx.numel()))
-                check(lib.aesr_conv2d_cout1_fwd(ptr(g), ptr(wflip), None, ptr(dx), B, H, W, 64, _hip.ACT_NONE, 0.0, stream()),
-                      "aesr_conv2d_cout1_fwd(vgg conv1_1 dgrad)")
-                engine._pe()
+                engine.launch("aesr_conv2d_cout1_fwd", ptr(g), ptr(wflip), None, ptr(dx), B, H, W, 64, _hip.ACT_NONE, 0.0,
+                              kind="thin_collapse", nbytes=4.0 * (g.numel() + dx.numel()), what="aesr_conv2d_cout1_fwd(vgg conv1_1 dgrad)")
                 return dx
             if n == 1:
                 ca, _ = self._affine(mul, 0.0)
                 d4 = torch.empty((B, H, W, 4), device=dev)
-                check(lib.aesr_conv2d_dgrad(ptr(g), ptr(pk["bwd"][0]), None, ptr(d4), B, H, W, 4, 64, 3, 1, 0, 0.0, stream()),
-                      "aesr_conv2d_dgrad(vgg conv1_1)")
+                engine.launch("aesr_conv2d_dgrad", ptr(g), ptr(pk["bwd"][0]), None, ptr(d4), B, H, W, 4, 64, 3, 1, 0, 0.0,
+                              what="aesr_conv2d_dgrad(vgg conv1_1)")
                 dx = torch.empty((B, H, W, 1), device=dev)
-                check(lib.aesr_scale_expand_bwd(ptr(d4), ptr(dx), B * H * W, _hip.float_array(ca), stream()), "aesr_scale_expand_bwd")
+                engine.launch("aesr_scale_expand_bwd", ptr(d4), ptr(dx), B * H * W, _hip.float_array(ca))
                 return dx
             cv = convs[n - 1]
             prev = acts[n - 2]
@@ -329,18 +316,16 @@ class PNetLin(nn.Module):
             mask = None if producer_is_pool else prev
             dxs = torch.empty((B, h, w, cv.in_channels), device=dev)
             if pk["bwd_wino"][n - 1]:
-                engine._pb(("wino", B, h, w, cv.in_channels, cv.out_channels, 1), 2.0 * B * h * w * cv.in_channels * 9 * cv.out_channels)
                 wsd, nwsd = engine.wino_workspace(g, B, h, w, cv.in_channels, cv.out_channels, 1)
-                check(lib.aesr_conv2d_wino_dgrad_ws(ptr(g), ptr(pk["bwd"][n - 1]), ptr(mask), ptr(dxs), ptr(wsd), nwsd, B, h, w,
-                                                    cv.in_channels, cv.out_channels, _hip.ACT_RELU if mask is not None else 0, 0.0, stream()),
-                      "aesr_conv2d_wino_dgrad_ws(vgg)")
-                engine._pe()
+                engine.launch("aesr_conv2d_wino_dgrad_ws", ptr(g), ptr(pk["bwd"][n - 1]), ptr(mask), ptr(dxs), ptr(wsd), nwsd, B, h, w,
+                              cv.in_channels, cv.out_channels, _hip.ACT_RELU if mask is not None else 0, 0.0,
+                              kind=("wino", B, h, w, cv.in_channels, cv.out_channels, 1),
+                              flops=2.0 * B * h * w * cv.in_channels * 9 * cv.out_channels, what="aesr_conv2d_wino_dgrad_ws(vgg)")
             else:
                 nws = lib.aesr_conv2d_dgrad_workspace_floats(B, h, w, cv.in_channels, cv.out_channels, 3, 1)
                 ws = torch.empty((nws,), device=dev) if nws else None
-                check(lib.aesr_conv2d_dgrad_ws(ptr(g), ptr(pk["bwd"][n - 1]), ptr(mask), ptr(dxs), ptr(ws), B, h, w, cv.in_channels,
-                                               cv.out_channels, 3, 1, _hip.ACT_RELU if mask is not None else 0, 0.0, stream()),
-                      "aesr_conv2d_dgrad_ws(vgg)")
+                engine.launch("aesr_conv2d_dgrad_ws", ptr(g), ptr(pk["bwd"][n - 1]), ptr(mask), ptr(dxs), ptr(ws), B, h, w, cv.in_channels,
+                              cv.out_channels, 3, 1, _hip.ACT_RELU if mask is not None else 0, 0.0, what="aesr_conv2d_dgrad_ws(vgg)")
             g = dxs
         raise AssertionError("unreachable")
 

@@ -9,8 +9,8 @@ import numpy as np
 import torch
 
 from . import _hip, engine
-from .engine import _pb, _pe
-from ._hip import check, lib, ptr, stream
+from .engine import launch
+from ._hip import lib, ptr
 
 
 def _flat_pair(a, b):
@@ -28,7 +28,7 @@ class _LerpFn(torch.autograd.Function):
         B = z.shape[0] // 2
         per = z[0].numel()
         zmix = torch.empty((B,) + tuple(z.shape[1:]), device=z.device, dtype=torch.float32)
-        check(lib.aesr_lerp_fwd(ptr(z), ptr(a_from), ptr(a_to), ptr(zmix), B, per, stream()), "aesr_lerp_fwd")
+        launch("aesr_lerp_fwd", ptr(z), ptr(a_from), ptr(a_to), ptr(zmix), B, per)
         ctx.save_for_backward(a_from, a_to)
         return zmix
 
@@ -38,7 +38,7 @@ class _LerpFn(torch.autograd.Function):
         dzmix = dzmix.contiguous()
         B = dzmix.shape[0]
         dz = torch.empty((2 * B,) + tuple(dzmix.shape[1:]), device=dzmix.device, dtype=torch.float32)
-        check(lib.aesr_lerp_bwd(ptr(dzmix), ptr(a_from), ptr(a_to), ptr(dz), B, dzmix[0].numel(), stream()), "aesr_lerp_bwd")
+        launch("aesr_lerp_bwd", ptr(dzmix), ptr(a_from), ptr(a_to), ptr(dz), B, dzmix[0].numel())
         return dz, None, None
 
 
@@ -49,9 +49,8 @@ class _LerpCatFn(torch.autograd.Function):
     def forward(ctx, z, a_from, a_to):
         B = z.shape[0] // 2
         zcat = torch.empty((3 * B,) + tuple(z.shape[1:]), device=z.device, dtype=torch.float32)
-        _pb("lerp_cat", 0.0, 4.0 * (z.numel() + zcat.numel()))
-        check(lib.aesr_lerp_cat_fwd(ptr(z), ptr(a_from), ptr(a_to), ptr(zcat), B, z[0].numel(), stream()), "aesr_lerp_cat_fwd")
-        _pe()
+        launch("aesr_lerp_cat_fwd", ptr(z), ptr(a_from), ptr(a_to), ptr(zcat), B, z[0].numel(),
+               kind="lerp_cat", nbytes=4.0 * (z.numel() + zcat.numel()))
         ctx.save_for_backward(a_from, a_to)
         return zcat
 
@@ -61,9 +60,7 @@ class _LerpCatFn(torch.autograd.Function):
         g = g.contiguous()
         B = g.shape[0] // 3
         dz = torch.empty((2 * B,) + tuple(g.shape[1:]), device=g.device, dtype=torch.float32)
-        _pb("lerp_cat", 0.0, 4.0 * (g.numel() + dz.numel()))
-        check(lib.aesr_lerp_cat_bwd(ptr(g), ptr(a_from), ptr(a_to), ptr(dz), B, g[0].numel(), stream()), "aesr_lerp_cat_bwd")
-        _pe()
+        launch("aesr_lerp_cat_bwd", ptr(g), ptr(a_from), ptr(a_to), ptr(dz), B, g[0].numel(), kind="lerp_cat", nbytes=4.0 * (g.numel() + dz.numel()))
         return dz, None, None
 
 
@@ -131,8 +128,7 @@ def lerp_multi(z_nhwc, alphas, act=_hip.ACT_NONE, slope=0.0, out=None):
             raise ValueError("out is %s on %s, %s on %s expected" % (tuple(out.shape), out.device, shape, z_nhwc.device))
     for k0 in range(0, n, 16):
         part = [float(a) for a in alphas[k0:k0 + 16]]
-        check(lib.aesr_lerp_multi(ptr(z_nhwc), ptr(out[k0 * (Z - 1):]), Z, per, _hip.float_array(part), len(part), int(act), float(slope),
-                                  stream()), "aesr_lerp_multi")
+        launch("aesr_lerp_multi", ptr(z_nhwc), ptr(out[k0 * (Z - 1):]), Z, per, _hip.float_array(part), len(part), int(act), float(slope))
     return out
 
 
@@ -150,7 +146,7 @@ def interleave_clamp(orig, synth, n, lo=0.0, hi=1.0):
     else:
         synth, n = None, 0
     out = torch.empty(((Z - 1) * (n + 1) + 1,) + tuple(orig.shape[1:]), device=orig.device, dtype=torch.float32)
-    check(lib.aesr_interleave_clamp(ptr(orig), ptr(synth), ptr(out), Z, n, per, float(lo), float(hi), stream()), "aesr_interleave_clamp")
+    launch("aesr_interleave_clamp", ptr(orig), ptr(synth), ptr(out), Z, n, per, float(lo), float(hi))
     return out
 
 
@@ -167,9 +163,7 @@ class _MseFn(torch.autograd.Function):
     def forward(ctx, a, b):
         partial = torch.empty(_hip.MSE_NPART, device=a.device, dtype=torch.float64)
         loss = torch.empty(1, device=a.device, dtype=torch.float32)
-        _pb("mse", 0.0, 8.0 * a.numel())
-        check(lib.aesr_mse_fwd(ptr(a), ptr(b), ptr(partial), ptr(loss), a.numel(), stream()), "aesr_mse_fwd")
-        _pe()
+        launch("aesr_mse_fwd", ptr(a), ptr(b), ptr(partial), ptr(loss), a.numel(), kind="mse", nbytes=8.0 * a.numel())
         ctx.save_for_backward(a, b)
         return loss.reshape(())
 
@@ -180,10 +174,10 @@ class _MseFn(torch.autograd.Function):
         need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if need_b and not need_a:            # d/db = 2(b-a)g/n: the same kernel with the operands swapped, no negation pass
             db = torch.empty_like(b)
-            check(lib.aesr_mse_bwd(ptr(b), ptr(a), ptr(g), ptr(db), b.numel(), stream()), "aesr_mse_bwd")
+            launch("aesr_mse_bwd", ptr(b), ptr(a), ptr(g), ptr(db), b.numel())
             return None, db
         da = torch.empty_like(a)
-        check(lib.aesr_mse_bwd(ptr(a), ptr(b), ptr(g), ptr(da), a.numel(), stream()), "aesr_mse_bwd")
+        launch("aesr_mse_bwd", ptr(a), ptr(b), ptr(g), ptr(da), a.numel())
         return (da if need_a else None), (-da if need_b else None)
 
 
@@ -230,11 +224,9 @@ class _CombinedMseFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)       # the three logged outputs carry no gradient: no zero tensors for them
         res = torch.empty(4, device=o3.device, dtype=torch.float32)
         flat = o3.reshape(-1)
-        _pb("mse3", 0.0, 4.0 * (2 * (n1 + n2) + 2 * (z_mix.numel() if z_mix is not None else 0)))
-        check(lib.aesr_mse3_fwd(ptr(flat), ptr(x), n1, ptr(flat[n1:]), ptr(between), n2, ptr(z_mix), ptr(z_ref),
-                                z_mix.numel() if z_mix is not None else 0, ptr(lam), ptr(_mse3_workspace(o3.device, owner)), ptr(res), stream()),
-              "aesr_mse3_fwd")
-        _pe()
+        launch("aesr_mse3_fwd", ptr(flat), ptr(x), n1, ptr(flat[n1:]), ptr(between), n2, ptr(z_mix), ptr(z_ref),
+               z_mix.numel() if z_mix is not None else 0, ptr(lam), ptr(_mse3_workspace(o3.device, owner)), ptr(res),
+               kind="mse3", nbytes=4.0 * (2 * (n1 + n2) + 2 * (z_mix.numel() if z_mix is not None else 0)))
         ctx.save_for_backward(o3, x, between, lam)
         outs = tuple(res[i].reshape(()) for i in range(4))
         ctx.mark_non_differentiable(*outs[1:])
@@ -249,10 +241,8 @@ class _CombinedMseFn(torch.autograd.Function):
         g = g.reshape(1).contiguous().float()
         d = torch.empty_like(o3)
         flat, dflat = o3.reshape(-1), d.reshape(-1)
-        _pb("mse3", 0.0, 4.0 * 3 * (n1 + n2))
-        check(lib.aesr_mse3_bwd(ptr(flat), ptr(x), n1, ptr(flat[n1:]), ptr(between), n2, ptr(lam), ptr(g), ptr(dflat), ptr(dflat[n1:]),
-                                stream()), "aesr_mse3_bwd")
-        _pe()
+        launch("aesr_mse3_bwd", ptr(flat), ptr(x), n1, ptr(flat[n1:]), ptr(between), n2, ptr(lam), ptr(g), ptr(dflat), ptr(dflat[n1:]),
+               kind="mse3", nbytes=4.0 * 3 * (n1 + n2))
         return d, None, None, None, None, None, None
 
 
@@ -276,7 +266,7 @@ class _RowMeanFn(torch.autograd.Function):
     def forward(ctx, x):
         N, M = x.shape[0], x[0].numel()
         out = torch.empty(N, device=x.device, dtype=torch.float32)
-        check(lib.aesr_row_mean_fwd(ptr(x), ptr(out), N, M, stream()), "aesr_row_mean_fwd")
+        launch("aesr_row_mean_fwd", ptr(x), ptr(out), N, M)
         ctx.shape = tuple(x.shape)
         return out
 
@@ -284,7 +274,7 @@ class _RowMeanFn(torch.autograd.Function):
     def backward(ctx, g):
         g = g.contiguous().float()
         dx = torch.empty(ctx.shape, device=g.device, dtype=torch.float32)
-        check(lib.aesr_row_mean_bwd(ptr(g), ptr(dx), ctx.shape[0], dx[0].numel(), stream()), "aesr_row_mean_bwd")
+        launch("aesr_row_mean_bwd", ptr(g), ptr(dx), ctx.shape[0], dx[0].numel())
         return dx
 
 
@@ -386,11 +376,9 @@ class HipAdam(torch.optim.Adam):
         b1, b2 = g["betas"]
         if (float(b1), float(b2)) != self._state_betas:            # betas changed between steps: the running powers start over
             self._init_state(float(self.dev_state[0].item()))
-        _pb("adam_step", 0.0, 28.0 * self.numel)
-        check(lib.aesr_adam_step(ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v), ptr(self.dev_state),
-                                 self.numel, float(g["lr"]), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]),
-                                 0, stream()), "aesr_adam_step")
-        _pe()
+        launch("aesr_adam_step", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v), ptr(self.dev_state), self.numel,
+               float(g["lr"]), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), 0,
+               kind="adam_step", nbytes=28.0 * self.numel)
         self._host_step += 1
         if self.on_step is not None:
             self.on_step()
@@ -459,10 +447,9 @@ class _SoftmaxDiceFn(torch.autograd.Function):
         partial = torch.empty(lib.aesr_softmax_dice_workspace_floats(N, H, W, K), device=dev, dtype=torch.float32)
         sums = torch.empty((N, 3, K), device=dev, dtype=torch.float64)
         loss = torch.empty(1, device=dev, dtype=torch.float32)
-        _pb("softmax_dice", 0.0, 4.0 * (2 * logits.numel() + N * H * W * (2 if want_argmax else 1)))
-        check(lib.aesr_softmax_dice_fwd(ptr(logits), ptr(labels), int(label_stride), ptr(probs), ptr(argmax), ptr(partial), ptr(sums), ptr(loss),
-                                        N, H, W, K, stream()), "aesr_softmax_dice_fwd")
-        _pe()
+        launch("aesr_softmax_dice_fwd", ptr(logits), ptr(labels), int(label_stride), ptr(probs), ptr(argmax), ptr(partial), ptr(sums), ptr(loss),
+               N, H, W, K,
+               kind="softmax_dice", nbytes=4.0 * (2 * logits.numel() + N * H * W * (2 if want_argmax else 1)))
         ctx.save_for_backward(probs, labels, sums)
         ctx.label_stride = int(label_stride)
         ctx.set_materialize_grads(False)
@@ -478,10 +465,8 @@ class _SoftmaxDiceFn(torch.autograd.Function):
         N, H, W, K = probs.shape
         g = g.reshape(1).contiguous().float()
         d = torch.empty_like(probs)
-        _pb("softmax_dice", 0.0, 4.0 * (2 * probs.numel() + N * H * W))
-        check(lib.aesr_softmax_dice_bwd(ptr(probs), ptr(labels), ctx.label_stride, ptr(sums), ptr(g), ptr(d), N, H, W, K, stream()),
-              "aesr_softmax_dice_bwd")
-        _pe()
+        launch("aesr_softmax_dice_bwd", ptr(probs), ptr(labels), ctx.label_stride, ptr(sums), ptr(g), ptr(d), N, H, W, K,
+               kind="softmax_dice", nbytes=4.0 * (2 * probs.numel() + N * H * W))
         return d, None, None, None
 
 
@@ -502,8 +487,7 @@ def _softmax_argmax_raw(logits_nhwc, want_argmax):
     N, H, W, K = _seg_check_logits(logits_nhwc)
     probs = torch.empty_like(logits_nhwc)
     argmax = torch.empty((N, H, W), device=logits_nhwc.device, dtype=torch.int32) if want_argmax else None
-    check(lib.aesr_softmax_dice_fwd(ptr(logits_nhwc), None, 0, ptr(probs), ptr(argmax), None, None, None, N, H, W, K, stream()),
-          "aesr_softmax_dice_fwd")
+    launch("aesr_softmax_dice_fwd", ptr(logits_nhwc), None, 0, ptr(probs), ptr(argmax), None, None, None, N, H, W, K)
     return probs, argmax
 
 
@@ -571,8 +555,8 @@ def surface_borders(result, reference, classes, ndim=3, connectivity=1, workspac
     elif workspace.numel() < nbytes or not workspace.is_cuda or workspace.dtype != torch.uint8:
         raise ValueError("workspace must be a CUDA uint8 tensor of at least %d bytes" % nbytes)
     counts = torch.empty((N, max(C, 1), _hip.SURFACE_COUNTS), device=result.device, dtype=torch.int64)
-    check(lib.aesr_surface_borders(ptr(result), ptr(reference), ptr(workspace), ptr(counts), N, Z, H, W, _hip.int_array(classes), C, int(ndim),
-                                   int(connectivity), stream()), "aesr_surface_borders")
+    launch("aesr_surface_borders", ptr(result), ptr(reference), ptr(workspace), ptr(counts), N, Z, H, W, _hip.int_array(classes), C, int(ndim),
+           int(connectivity))
     return counts, workspace
 
 
@@ -596,8 +580,8 @@ def surface_distances(workspace, counts, shape, spacing, ndim=3, counts_host=Non
     total = int(lengths.sum())
     distances = torch.empty(max(total, 1), device=counts.device, dtype=torch.float64)
     stats = torch.empty((N, C, 2, 2), device=counts.device, dtype=torch.float64)
-    check(lib.aesr_surface_distances(ptr(workspace), ptr(counts), counts_host.ctypes.data_as(_hip.LLP), ptr(distances), total if total else 1,
-                                     ptr(stats), N, Z, H, W, C, int(ndim), _hip.double_array(spacing), stream()), "aesr_surface_distances")
+    launch("aesr_surface_distances", ptr(workspace), ptr(counts), counts_host.ctypes.data_as(_hip.LLP), ptr(distances), total if total else 1,
+           ptr(stats), N, Z, H, W, C, int(ndim), _hip.double_array(spacing))
     return distances[:total], stats, lengths
 
 
@@ -638,8 +622,8 @@ def components_label(vol, classes, ndim=3, connectivity=1, workspace=None):
     workspace = _components_workspace(workspace, shape, C, vol.device)
     labels = torch.empty(shape, device=vol.device, dtype=torch.int32)
     ncomp = torch.empty((max(components_units(shape, ndim), 1), max(C, 1)), device=vol.device, dtype=torch.int32)
-    check(lib.aesr_components_label(ptr(vol), ptr(labels), ptr(ncomp), ptr(workspace), *shape, _hip.int_array(classes), C, int(ndim),
-                                    int(connectivity), stream()), "aesr_components_label")
+    launch("aesr_components_label", ptr(vol), ptr(labels), ptr(ncomp), ptr(workspace), *shape, _hip.int_array(classes), C, int(ndim),
+           int(connectivity))
     return labels, ncomp, workspace
 
 
@@ -659,8 +643,8 @@ def components_tables(vol, labels, n_components, classes, ndim=3, workspace=None
     rows = int(host.astype(np.int64).sum())
     workspace = _components_workspace(workspace, shape, len(classes), vol.device)
     table = torch.empty((max(rows, 1), _hip.COMPONENTS_COLUMNS), device=vol.device, dtype=torch.int64)
-    check(lib.aesr_components_tables(ptr(vol), ptr(labels), ptr(n_components), host.ctypes.data_as(_hip.IP), ptr(workspace), ptr(table),
-                                     max(rows, 1), *shape, _hip.int_array(classes), len(classes), int(ndim), stream()), "aesr_components_tables")
+    launch("aesr_components_tables", ptr(vol), ptr(labels), ptr(n_components), host.ctypes.data_as(_hip.IP), ptr(workspace), ptr(table),
+           max(rows, 1), *shape, _hip.int_array(classes), len(classes), int(ndim))
     return table[:rows], host
 
 
@@ -674,12 +658,12 @@ def components_overlaps(vol_a, labels_a, vol_b, labels_b, classes, ndim=3, works
     workspace = _components_workspace(workspace, shape, len(classes), vol_a.device)
     count = torch.empty(1, device=vol_a.device, dtype=torch.int64)
     cls = _hip.int_array(classes)
-    check(lib.aesr_components_overlap_count(ptr(vol_a), ptr(labels_a), ptr(vol_b), ptr(labels_b), ptr(workspace), ptr(count), *shape, cls,
-                                            len(classes), int(ndim), stream()), "aesr_components_overlap_count")
+    launch("aesr_components_overlap_count", ptr(vol_a), ptr(labels_a), ptr(vol_b), ptr(labels_b), ptr(workspace), ptr(count), *shape, cls,
+           len(classes), int(ndim))
     K = int(count.item())
     runs = torch.empty((max(K, 1), 4), device=vol_a.device, dtype=torch.int32)
-    check(lib.aesr_components_overlap_runs(ptr(vol_a), ptr(labels_a), ptr(vol_b), ptr(labels_b), ptr(workspace), K, ptr(runs), max(K, 1), *shape,
-                                           cls, len(classes), int(ndim), stream()), "aesr_components_overlap_runs")
+    launch("aesr_components_overlap_runs", ptr(vol_a), ptr(labels_a), ptr(vol_b), ptr(labels_b), ptr(workspace), K, ptr(runs), max(K, 1), *shape,
+           cls, len(classes), int(ndim))
     return runs[:K]
 
 
@@ -692,7 +676,6 @@ def components_apply_table(vol, labels, n_components, table, classes, ndim=3, wo
     _hip.require_gpu_tensor(table, "table")
     workspace = _components_workspace(workspace, shape, len(classes), vol.device)
     out = torch.empty(shape, device=vol.device, dtype=torch.float32)
-    check(lib.aesr_components_apply_table(ptr(vol), ptr(labels), ptr(n_components), host.ctypes.data_as(_hip.IP), ptr(workspace), ptr(table),
-                                          int(table.numel()), ptr(out), *shape, _hip.int_array(classes), len(classes), int(ndim), stream()),
-          "aesr_components_apply_table")
+    launch("aesr_components_apply_table", ptr(vol), ptr(labels), ptr(n_components), host.ctypes.data_as(_hip.IP), ptr(workspace), ptr(table),
+           int(table.numel()), ptr(out), *shape, _hip.int_array(classes), len(classes), int(ndim))
     return out
