@@ -233,6 +233,16 @@ SIGNATURES_COMPONENTS = {
     "aesr_components_overlap_runs": (c_int, [P] * 5 + [ctypes.c_longlong, P, c_size_t] + [c_int] * 4 + [IP, c_int, c_int, P]),
     "aesr_components_apply_table": (c_int, [P, P, P, IP, P, P, c_size_t, P] + [c_int] * 4 + [IP, c_int, c_int, P]),
 }
+# Shape-based label interpolation (csrc/shape_interp.hip).  NOT in HEADERS, and on purpose not named SIGNATURES*: libaesr_hip.so exports
+# these three symbols, but they are declared in csrc/shape_interp.h, not under include/ -- the public ABI is pinned header by header
+# (tests/test_abi.py, tests/golden/abi_symbols.json, with the GPU test module that guards each header), and they join it in a change whose
+# subject is the ABI.  _load() binds this table beside the public ones; tests/test_shape_interp_golden.py checks it against the prototypes.
+SHAPE_INTERP_ENTRIES = {
+    "aesr_shape_workspace_bytes": (c_size_t, [c_int] * 5),
+    "aesr_shape_signed_distances": (c_int, [P, P, P, c_size_t] + [c_int] * 4 + [IP, c_int, c_double, c_double, P]),
+    "aesr_shape_interpolate": (c_int, [P, P, P, P] + [c_int] * 6 + [IP, P]),
+}
+SHAPE_MAX_CLASSES, SHAPE_MAX_W = 8, 4096          # AESR_SHAPE_* of csrc/shape_interp.h
 # The C ABI, header by header in the order the headers were added: each table must list every symbol its header under include/ declares,
 # with the types of the prototype, and no symbol may stand in two (tests/test_abi.py checks all of it against the headers and the library).
 # _load() binds exactly these tables; include/ is not read at run time.
@@ -275,7 +285,7 @@ def _load():
             "libaesr_hip.so not found at %s -- build it with `python __graft_entry__.py` (or `make -C "
             "superresolution_aniso_mri_amd/csrc`). The HIP extension is mandatory: there is no CPU/eager fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for table in HEADERS.values():
+    for table in list(HEADERS.values()) + [SHAPE_INTERP_ENTRIES]:
         for name, (res, args) in table.items():
             fn = getattr(lib, name, None)
             if fn is None:

@@ -161,15 +161,23 @@ def surface_distance_lists(result, reference, spacing, classes=None, ndim=3, con
             "classes": np.asarray(classes, dtype=np.int64)}
 
 
-def score_label_supervolume(trainer, images, labels, downsample_steps, spacing, classes=None):
+LABEL_BASELINES = ("nearest", "shape")
+
+
+def score_label_supervolume(trainer, images, labels, downsample_steps, spacing, classes=None, baselines=("nearest",)):
     """Score what a multi-channel model makes of every ``downsample_steps``-th slice: ``create_super_volume(labels=)`` keeps those slices,
     synthesises the ones in between and returns a label volume as deep as ``labels``, which is scored against the full-resolution
     ``labels`` -- beside the nearest-slice baseline (``create_simple_interpolation(..., "nearest", align="grid")``, cut and extended the
-    same way), the comparison the multi-channel model exists for.  Returns {"model": scores, "nearest": scores}."""
+    same way), the comparison the multi-channel model exists for.  Returns {"model": scores, "nearest": scores}.  ``baselines`` names the
+    conventional methods scored beside the model on the same reference: "nearest" and / or "shape" (shape-based interpolation,
+    ``evaluate.shape_interp.shape_baseline``); one table each under its name."""
     from .common import create_simple_interpolation, create_super_volume
     f = int(downsample_steps)
     if f < 2:
         raise ValueError("downsample_steps must be at least 2, got %r" % (downsample_steps,))
+    baselines = tuple(baselines)
+    if any(b not in LABEL_BASELINES for b in baselines) or len(set(baselines)) != len(baselines):
+        raise ValueError("baselines=%r: each of %s at most once" % (baselines, ", ".join(LABEL_BASELINES)))
     if tuple(labels.shape) != tuple(images.shape):
         raise ValueError("the labels %s do not match the images %s" % (tuple(labels.shape), tuple(images.shape)))
     alphas = [k / float(f) for k in range(1, f)]
@@ -184,8 +192,15 @@ def score_label_supervolume(trainer, images, labels, downsample_steps, spacing, 
     ref = torch.as_tensor(labels).to("cuda", torch.float32)
     if classes is None:
         classes = _classes(None, ref)
-    near = create_simple_interpolation(ref, spacing, expand_factor=f, interpol_filter="nearest", generate_inbetween_slices=True, align="grid")
-    if tuple(near.array.shape) != tuple(labels.shape):
-        raise ValueError("the nearest-slice volume %s does not match the labels %s" % (tuple(near.array.shape), tuple(labels.shape)))
-    return {"model": segmentation_scores(pred.to("cuda", torch.float32), ref, spacing, classes=classes),
-            "nearest": segmentation_scores(near.array, ref, spacing, classes=classes)}
+    scores = {"model": segmentation_scores(pred.to("cuda", torch.float32), ref, spacing, classes=classes)}
+    for name in baselines:
+        if name == "nearest":
+            vol = create_simple_interpolation(ref, spacing, expand_factor=f, interpol_filter="nearest", generate_inbetween_slices=True,
+                                              align="grid").array
+        else:
+            from .shape_interp import shape_baseline
+            vol = shape_baseline(ref, f, spacing).to(torch.float32)
+        if tuple(vol.shape) != tuple(labels.shape):
+            raise ValueError("the %s volume %s does not match the labels %s" % (name, tuple(vol.shape), tuple(labels.shape)))
+        scores[name] = segmentation_scores(vol, ref, spacing, classes=classes)
+    return scores

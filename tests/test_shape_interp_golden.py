@@ -1,0 +1,324 @@
+"""No GPU: shape-based interpolation of label maps (csrc/shape_interp.h) restated in numpy by brute force, against the fixture that
+tests/make_golden_shape_interp.py wrote with scipy (tests/golden/shape_interp.npz); and the parts of the host layer that need no device.
+
+The restatement is the definition itself, with the device's expression and order: per class, slice and pixel the minimum over the pixels
+of the other side of (dy sy) (dy sy) + (dx sx) (dx sx) in fp64, one sqrt, BIG for a minimum over nothing; then
+v_c = (1 - a) sdm[c][g] + a sdm[c][g1] and the class of the first maximum.  tests/test_gpu_shape_interp.py holds the device to it bit for bit.
+
+Bounds.  Signed maps: within 1e-12 * BIG of scipy's (the fp64 bound test_gpu_z_expand uses for coefficients; scipy may round its squares
+differently).  Labels: equal to the fixture's wherever the margin between the best and the second-best blended value, stored in the
+fixture, exceeds 1e-9 * BIG -- below that a last-bit difference of a map may turn the arg-max -- and the voxels that rule leaves out are
+at most 0.1 % of any case: a condition on the cases (the golden script asserts it when it writes the fixture), not a measurement."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import abi_util as au
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "shape_interp.npz")
+MAP_BOUND = 1e-12          # * BIG: signed maps against scipy
+MARGIN = 1e-9              # * BIG: labels are compared where the stored margin exceeds this
+LEFT_OUT_CAP = 1e-3        # of the voxels of a case
+
+CASES = ["w1", "w63", "w64", "w65", "w130", "h1", "ychunk", "z1", "bgonly", "eight", "oneslice", "z7", "frames"]
+
+_CACHE = {}
+
+
+def fixture():
+    if "rec" not in _CACHE:
+        _CACHE["rec"] = dict(np.load(GOLDEN))
+    return _CACHE["rec"]
+
+
+def case_names():
+    return list(CASES)
+
+
+def case(name):
+    """dict: labels uint8 [N, Z, H, W], classes [C], spacing (sy, sx), gap int64 [J], alpha fp64 [J], sdm fp64 [N, C, Z, H, W] (scipy),
+    out uint8 [N, J, H, W] and margin fp64 [N, J, H, W] (the rule on scipy's maps), big"""
+    rec = fixture()
+    c = {k: rec["%s/%s" % (name, k)] for k in ("labels", "classes", "spacing", "gap", "alpha", "sdm", "out", "margin")}
+    c["classes"] = [int(v) for v in c["classes"]]
+    c["spacing"] = tuple(float(v) for v in c["spacing"])
+    c["big"] = big_of(c["labels"].shape[2], c["labels"].shape[3], *c["spacing"])
+    return c
+
+
+# ---- the restatement ------------------------------------------------------------------------------------------------------------------
+def big_of(H, W, sy, sx):
+    hy, wx = float(H) * float(sy), float(W) * float(sx)
+    return float(np.sqrt(np.float64(hy * hy + wx * wx)))
+
+
+def signed_maps_np(labels, classes, sy, sx):
+    """uint8 [N, Z, H, W] -> fp64 [N, C, Z, H, W] by brute force over all pairs of pixels of a slice"""
+    N, Z, H, W = labels.shape
+    big = big_of(H, W, sy, sx)
+    yi, xi = np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64)
+    dy = (yi[:, None] - yi[None, :]) * np.float64(sy)
+    dx = (xi[:, None] - xi[None, :]) * np.float64(sx)
+    d2 = (dy * dy)[:, None, :, None] + (dx * dx)[None, :, None, :]          # [y, x, y', x']: (dy sy)(dy sy) + (dx sx)(dx sx)
+    out = np.empty((N, len(classes), Z, H, W), dtype=np.float64)
+    for n in range(N):
+        for z in range(Z):
+            for ci, c in enumerate(classes):
+                M = labels[n, z] == c
+                to_class = np.where(M[None, None], d2, np.inf).min(axis=(2, 3))
+                to_other = np.where(~M[None, None], d2, np.inf).min(axis=(2, 3))
+                m = np.where(M, to_other, to_class)
+                mag = np.where(np.isinf(m), big, np.sqrt(np.where(np.isinf(m), 0.0, m)))
+                out[n, ci, z] = np.where(M, mag, -mag)
+    return out
+
+
+def clamp_gap(gap, Z):
+    g = np.clip(np.asarray(gap, dtype=np.int64), 0, max(Z - 2, 0))
+    return g, np.minimum(g + 1, Z - 1)
+
+
+def blend_np(sdm, gap, alpha, classes):
+    """fp64 [N, C, Z, H, W] -> (labels uint8 [N, J, H, W], margin fp64 [N, J, H, W]: best minus second-best blended value, inf for C == 1)"""
+    Z = sdm.shape[2]
+    g, g1 = clamp_gap(gap, Z)
+    a = np.asarray(alpha, dtype=np.float64)[None, None, :, None, None]
+    v = (1.0 - a) * sdm[:, :, g] + a * sdm[:, :, g1]
+    idx = np.argmax(v, axis=1)          # the first maximum: ties go to the smallest class value
+    labels = np.asarray(classes, dtype=np.uint8)[idx]
+    if v.shape[1] == 1:
+        return labels, np.full(labels.shape, np.inf)
+    top = np.sort(v, axis=1)
+    return labels, top[:, -1] - top[:, -2]
+
+
+def restated(name):
+    """(maps, labels) of the restatement for a case; computed once and shared by every test that needs them"""
+    key = "restated/" + name
+    if key not in _CACHE:
+        c = case(name)
+        maps = signed_maps_np(c["labels"], c["classes"], *c["spacing"])
+        maps.setflags(write=False)
+        labels, _ = blend_np(maps, c["gap"], c["alpha"], c["classes"])
+        labels.setflags(write=False)
+        _CACHE[key] = (maps, labels)
+    return _CACHE[key]
+
+
+def left_out(c):
+    """bool [N, J, H, W]: the voxels the margin rule does not compare"""
+    return ~(c["margin"] > MARGIN * c["big"])
+
+
+def assert_labels_match_fixture(got, c, what):
+    skip = left_out(c)
+    assert skip.mean() <= LEFT_OUT_CAP, "%s: the margin rule leaves out %d of %d voxels" % (what, skip.sum(), skip.size)
+    bad = (np.asarray(got) != c["out"]) & ~skip
+    assert not bad.any(), "%s: %d label(s) differ from the fixture where the margin decides, first at %s" % (what, bad.sum(), np.argwhere(bad)[0])
+
+
+# ---- restatement against the fixture --------------------------------------------------------------------------------------------------
+def test_the_fixture_holds_the_cases_the_kernels_can_go_wrong_on():
+    assert [str(n) for n in fixture()["names"]] == CASES
+    shapes = {n: case(n)["labels"].shape for n in case_names()}
+    assert {1, 63, 64, 65, 130} <= {s[3] for s in shapes.values()}
+    assert any(s[2] == 1 for s in shapes.values()) and any(s[2] == 129 and s[3] == 8 for s in shapes.values())
+    assert any((s[2] * s[3]) % 4 for s in shapes.values()) and any((s[2] * s[3]) % 4 == 0 for s in shapes.values())
+    assert {1, 2, 7} <= {s[1] for s in shapes.values()} and any(s[0] == 2 for s in shapes.values())
+    assert {1, 2, 4, 8} <= {len(case(n)["classes"]) for n in case_names()}
+    assert {(1.25, 1.5), (1.0, 1.0)} <= {case(n)["spacing"] for n in case_names()}
+    assert any(len(case(n)["gap"]) == 29 for n in case_names())
+    assert os.path.getsize(GOLDEN) < 512 * 1024
+
+
+@pytest.mark.parametrize("name", case_names())
+def test_restated_maps_are_scipys(name):
+    c = case(name)
+    maps, _ = restated(name)
+    assert maps.shape == c["sdm"].shape and np.isfinite(maps).all()
+    worst = float(np.abs(maps - c["sdm"]).max())
+    print("%s: worst |restatement - scipy| = %.3g, bound %.3g" % (name, worst, MAP_BOUND * c["big"]))
+    assert worst <= MAP_BOUND * c["big"]
+    # exactly one class is positive at every pixel: the one the pixel holds
+    pos = maps > 0
+    assert (pos.sum(axis=1) == 1).all()
+    assert np.array_equal(np.asarray(c["classes"], dtype=np.uint8)[np.argmax(pos, axis=1)], c["labels"])
+    # a class that is absent from a slice or fills it: BIG everywhere in it
+    for ci, cv in enumerate(c["classes"]):
+        M = c["labels"] == cv
+        flat = M.all(axis=(2, 3)) | ~M.any(axis=(2, 3))
+        assert (np.abs(maps[:, ci][flat]) == c["big"]).all() and (np.abs(maps[:, ci][~flat]) < c["big"]).all()
+
+
+@pytest.mark.parametrize("name", case_names())
+def test_restated_labels_are_the_fixtures_under_the_margin_rule(name):
+    c = case(name)
+    _, labels = restated(name)
+    assert labels.shape == c["out"].shape == c["margin"].shape and labels.dtype == np.uint8
+    assert_labels_match_fixture(labels, c, name)
+    # alpha 0 and 1 are input slices, bit for bit
+    g, g1 = clamp_gap(c["gap"], c["labels"].shape[1])
+    for j, a in enumerate(c["alpha"]):
+        if a == 0.0 or a == 1.0:
+            assert np.array_equal(labels[:, j], c["labels"][:, g[j] if a == 0.0 else g1[j]]), (name, j)
+
+
+def test_ties_go_to_the_smallest_class_and_absent_classes_do_not_taper():
+    sdm = np.zeros((1, 3, 2, 1, 2))
+    sdm[0, :, 0, 0, 0], sdm[0, :, 1, 0, 0] = (1.0, -1.0, -1.0), (-1.0, 1.0, 1.0)          # all three tie at a = 0.5
+    sdm[0, :, 0, 0, 1], sdm[0, :, 1, 0, 1] = (-2.0, 1.0, -1.0), (-2.0, -1.0, 1.0)         # classes 5 and 9 tie
+    labels, margin = blend_np(sdm, [0], [0.5], [2, 5, 9])
+    assert labels.reshape(-1).tolist() == [2, 5] and margin.reshape(-1).tolist() == [0.0, 0.0]
+    # a box that one slice holds and the next does not: its map there is -BIG, so a pixel d deep survives only while
+    # (1 - a) d > a BIG -- the class ends at the slice that has it (here, depth <= 3 and BIG = 12.7: gone before a = 0.2), it does not taper
+    lab = np.zeros((1, 2, 9, 9), dtype=np.uint8)
+    lab[0, 0, 2:7, 2:7] = 1
+    maps = signed_maps_np(lab, [0, 1], 1.0, 1.0)
+    out, _ = blend_np(maps, [0, 0, 0, 0], [0.0, 0.05, 0.2, 0.5], [0, 1])
+    assert np.array_equal(out[0, 0], lab[0, 0]) and np.array_equal(out[0, 1], lab[0, 0]) and not out[0, 2].any() and not out[0, 3].any()
+
+
+# ---- the host layer without a device --------------------------------------------------------------------------------------------------
+def test_value_errors_of_the_host_layer():
+    from superresolution_aniso_mri_amd.evaluate import shape_interp as si
+    from superresolution_aniso_mri_amd.evaluate.z_grid import target_grid
+    lab = np.zeros((3, 4, 5), dtype=np.uint8)
+    lab[1, 1:3, 1:3] = 2
+    with pytest.raises(ValueError, match="exactly one"):
+        si.shape_interpolate(lab)
+    with pytest.raises(ValueError, match="exactly one"):
+        si.shape_interpolate(lab, num_interpolations=1, grid=target_grid(3, 10.0, 5.0))
+    with pytest.raises(ValueError, match="grid is for 4 slices"):
+        si.shape_interpolate(lab, grid=target_grid(4, 10.0, 5.0))
+    with pytest.raises(ValueError, match="ZGrid"):
+        si.shape_interpolate(lab, grid=(0, 1))
+    with pytest.raises(ValueError, match="num_interpolations"):
+        si.shape_interpolate(lab, num_interpolations=-1)
+    with pytest.raises(ValueError, match=r"\[Z, H, W\]"):
+        si.shape_interpolate(lab[0], num_interpolations=1)
+    with pytest.raises(ValueError, match="not in classes"):
+        si.shape_interpolate(lab, num_interpolations=1, classes=[0, 1])
+    with pytest.raises(ValueError, match="not in classes"):
+        si.signed_distance_maps(lab, classes=[0])
+    with pytest.raises(ValueError, match="ascending"):
+        si.signed_distance_maps(lab, classes=[2, 0])
+    with pytest.raises(ValueError, match="0..255"):
+        si.signed_distance_maps(lab, classes=[0, 2, 256])
+    with pytest.raises(ValueError, match="0..255"):
+        si.signed_distance_maps(lab.astype(np.float32) + 0.5)
+    nine = (np.arange(60).reshape(3, 4, 5) % 9).astype(np.uint8)
+    with pytest.raises(ValueError, match="1 to 8 classes"):
+        si.signed_distance_maps(nine)
+    with pytest.raises(ValueError, match="1 to 8 classes"):
+        si.shape_interpolate(torch.from_numpy(nine), num_interpolations=2)
+    for bad in ((1.0,), (1.0, 0.0), (1.0, float("inf")), (1.0, -2.0)):
+        with pytest.raises(ValueError, match="spacing_yx"):
+            si.signed_distance_maps(lab, spacing_yx=bad)
+    with pytest.raises(ValueError, match="up to 4096"):
+        si.signed_distance_maps(np.zeros((1, 1, 4097), dtype=np.uint8))
+    assert si.check_classes(None, [3.0, 0, 1]) == [0, 1, 3] and si.check_classes([0, 1, 2, 3], [1]) == [0, 1, 2, 3]
+    if not torch.cuda.is_available():          # no CPU fallback: a valid call says that it needs the GPU
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            si.shape_interpolate(lab, num_interpolations=1)
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            si.signed_distance_maps(lab)
+
+
+def test_baseline_bookkeeping_is_determine_last_slice():
+    from superresolution_aniso_mri_amd.evaluate import shape_interp as si
+    from superresolution_aniso_mri_amd.evaluate.common import determine_last_slice
+    from superresolution_aniso_mri_amd.evaluate.z_grid import target_grid
+    for Z in range(1, 14):
+        for f in (2, 3, 4, 7):
+            kept, last, remain = si.baseline_plan(Z, f)
+            assert kept == list(range(Z))[::f] and last == determine_last_slice(Z, f) == kept[-1] and remain == Z - 1 - last
+            grid = si.resolve_grid(len(kept), num_interpolations=f - 1)          # what shape_baseline interpolates on
+            assert grid.J == last + 1 and grid.J + remain == Z
+            assert [int(s) for s in grid.source[::f]] == list(range(len(kept))) and int(grid.is_original.sum()) == len(kept)
+    with pytest.raises(ValueError, match="at least 2"):
+        si.baseline_plan(5, 1)
+    with pytest.raises(ValueError, match=r"\[z, y, x\]"):
+        si.shape_baseline(np.zeros((2, 3, 4, 5), dtype=np.uint8), 2, (1.0, 1.0, 1.0))
+    with pytest.raises(ValueError, match=r"\(z, y, x\)"):
+        si.shape_baseline(np.zeros((3, 4, 5), dtype=np.uint8), 2, (1.0, 1.0))
+    # the integer grid is the target grid at 1 / (n + 1): one code path
+    a, b = si.resolve_grid(5, num_interpolations=6), target_grid(5, 1.0, 1.0 / 7)
+    assert np.array_equal(a.gap, b.gap) and np.array_equal(a.alpha, b.alpha) and a.J == 29
+
+
+def test_score_label_supervolume_checks_its_baselines_first():
+    from superresolution_aniso_mri_amd.evaluate import seg_metrics
+    x = torch.zeros(4, 5, 6)
+    for bad in (("linear",), ("nearest", "nearest"), ("shape", "model")):
+        with pytest.raises(ValueError, match="baselines"):
+            seg_metrics.score_label_supervolume(None, x, x, 2, (1.0, 1.0, 1.0), baselines=bad)
+    assert seg_metrics.LABEL_BASELINES == ("nearest", "shape")
+
+
+def test_argument_parsing_of_both_tools(capsys):
+    from superresolution_aniso_mri_amd.evaluate import compare_label_methods as clm
+    from superresolution_aniso_mri_amd.evaluate import shape_interp as si
+    _, a = si.parse_args(["--labels_dir", "L", "--output_dir", "O", "--num_interpolations", "6"])
+    assert (a.labels_dir, a.output_dir, a.num_interpolations, a.target_spacing_z, a.method, a.spacing_z, a.spacing) == ("L", "O", 6, None, "shape", None, None)
+    _, a = si.parse_args(["--labels_dir", "L", "--output_dir", "O", "--target_spacing_z", "1.4", "--method", "nearest", "--spacing_z", "10",
+                          "--spacing", "1.25", "1.5"])
+    assert (a.num_interpolations, a.target_spacing_z, a.method, a.spacing_z, a.spacing) == (None, 1.4, "nearest", 10.0, [1.25, 1.5])
+    for bad in (["--labels_dir", "L", "--output_dir", "O"],
+                ["--labels_dir", "L", "--output_dir", "O", "--num_interpolations", "2", "--target_spacing_z", "1.0"],
+                ["--labels_dir", "L", "--output_dir", "O", "--num_interpolations", "17"],
+                ["--labels_dir", "L", "--output_dir", "O", "--target_spacing_z", "-1"],
+                ["--labels_dir", "L", "--output_dir", "O", "--num_interpolations", "2", "--method", "linear"],
+                ["--output_dir", "O", "--num_interpolations", "2"]):
+        with pytest.raises(SystemExit):
+            si.parse_args(bad)
+    assert si.output_name("p01.nii.gz", num_interpolations=6) == "p01_ni06.nii.gz"
+    assert si.output_name("p01.npy", target_spacing_z=1.4) == "p01_sz1.4.npy" and si.output_name("a.b.mha", 2) == "a.b_ni02.mha"
+    with pytest.raises(ValueError):
+        si.output_name("p01.txt", 2)
+    _, a = clm.parse_args(["--labels_dir", "L", "--downsample_steps", "3"])
+    assert (a.labels_dir, a.downsample_steps, a.exper_dir, a.volumes_dir, a.model_nbr, a.classes, a.out, a.spacing) == ("L", 3, None, None, None, None, None, None)
+    _, a = clm.parse_args(["--labels_dir", "L", "--downsample_steps", "2", "--exper_dir", "E", "--volumes_dir", "V", "--model_nbr", "7", "--classes", "1",
+                           "3", "--out", "s.npz", "--spacing", "10", "1.4", "1.4"])
+    assert (a.exper_dir, a.volumes_dir, a.model_nbr, a.classes, a.out, a.spacing) == ("E", "V", 7, [1, 3], "s.npz", [10.0, 1.4, 1.4])
+    for bad in (["--labels_dir", "L"], ["--labels_dir", "L", "--downsample_steps", "1"],
+                ["--labels_dir", "L", "--downsample_steps", "2", "--exper_dir", "E"],
+                ["--labels_dir", "L", "--downsample_steps", "2", "--volumes_dir", "V"],
+                ["--labels_dir", "L", "--downsample_steps", "2", "--model_nbr", "3"]):
+        with pytest.raises(SystemExit):
+            clm.parse_args(bad)
+    capsys.readouterr()
+    table = clm.format_table({"nearest": {k: np.array([[0.5, 1.0]]) for k in clm.TABLE_KEYS}, "shape": {k: np.array([[0.75, np.nan]]) for k in clm.TABLE_KEYS},
+                              "classes": np.array([1, 2]), "names": np.array(["a"])}, 2)
+    assert table.count("\n") == 7 and "nearest" in table and "shape" in table and "hd95" in table and "0.7500" in table
+
+
+# ---- the binding ----------------------------------------------------------------------------------------------------------------------
+def test_the_three_symbols_are_bound_as_their_prototypes_and_are_not_public_abi():
+    from superresolution_aniso_mri_amd import _hip
+    header = os.path.join(ROOT, "superresolution_aniso_mri_amd", "csrc", "shape_interp.h")
+    table, protos = _hip.SHAPE_INTERP_ENTRIES, au.prototypes(header)
+    assert set(protos) == set(table) == {"aesr_shape_workspace_bytes", "aesr_shape_signed_distances", "aesr_shape_interpolate"}
+    lib = ctypes.CDLL(_hip.LIB_PATH)
+    for name, (ret, params) in protos.items():
+        res, args = table[name]
+        assert au.RETURNS[ret] is res, (name, ret, res)
+        assert len(args) == len(params), name
+        for i, ((ctype, pname), bound) in enumerate(zip(params, args)):
+            assert au.compatible(ctype, bound, _hip), "%s: argument %d, %s %s, is bound as %s" % (name, i, ctype, pname, bound)
+        assert getattr(lib, name, None) is not None, "%s is not exported" % name
+        assert getattr(_hip.lib, name).restype == res and getattr(_hip.lib, name).argtypes == args, name
+    # not yet public: in no table of HEADERS, declared by no header under include/, and the table's name keeps it out of the ABI test's sweep
+    for h, t in _hip.HEADERS.items():
+        assert not set(table) & set(t) and not set(table) & au.declared(h), h
+    assert not any(t is table for t in _hip.HEADERS.values())
+    assert not [k for k, v in vars(_hip).items() if v is table and k.startswith("SIGNATURES")]
+    defs = au.defines(header)
+    assert (_hip.SHAPE_MAX_CLASSES, _hip.SHAPE_MAX_W) == (defs["AESR_SHAPE_MAX_CLASSES"], defs["AESR_SHAPE_MAX_W"])
+    # the size query is host code
+    q = _hip.lib.aesr_shape_workspace_bytes
+    assert q(1, 2, 3, 4, 2) == 384 and q(2, 7, 5, 6, 8) % 16 == 0 and q(2, 7, 5, 6, 8) >= 2 * 8 * 2 * 7 * 30 * 4
+    assert q(0, 2, 3, 4, 2) == 0 and q(1, 2, 3, 4, 9) == 0 and q(1, 2, 3, 4097, 2) == 0 and q(1 << 10, 1 << 10, 1 << 10, 2, 1) == 0
