@@ -1048,8 +1048,8 @@ void aesr_adam_state_init(float* state_host8, double steps_done, double beta1, d
     // continues bit for bit like the one that was never stopped
     double b1p = beta1, b2p = beta2;
     for (long k = 0; k < (long)steps_done; ++k) {
-        b1p *= beta1;
-        b2p *= beta2;
+        b1p = aesr_adam_next_power(b1p, beta1);
+        b2p = aesr_adam_next_power(b2p, beta2);
     }
     state_host8[0] = (float)steps_done;
     state_host8[1] = (float)(1.0 - b1p);

@@ -258,6 +258,13 @@ int aesr_launch_mse_bwd(const float* a, const float* b, const float* g, float* d
 int aesr_launch_act_bwd(const float* dout, const float* y, float* dpre, size_t n, int act, float slope, hipStream_t st);
 int aesr_launch_adam(float* p, float* g, float* m, float* v, float* state, size_t n, float lr, double beta1, double beta2,
                      float eps, float wd, int zero_g, hipStream_t st);
+// beta^(t+1) from beta^t: the ONE statement of the chain that adam_step_kernel advances on the device and aesr_adam_state_init replays on the
+// host (a resumed optimizer continues bit for bit).  A power that has left the normal range is 0: the products would otherwise stop at a
+// denormal for ever (5 units * 0.9 rounds back to 5 units: 0.9^100000 stayed 2.5e-323)
+__host__ __device__ inline double aesr_adam_next_power(double power, double beta) {
+    const double q = power * beta;
+    return q < 2.2250738585072014e-308 ? 0.0 : q;
+}
 
 
 int aesr_launch_maxpool2_fwd(const float* x, float* out, int N, int H, int W, int C, hipStream_t st);

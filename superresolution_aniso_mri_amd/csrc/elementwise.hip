@@ -230,7 +230,9 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
 __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, float* __restrict__ state, size_t n, float lr,
                                                         double beta1d, double beta2d, float eps, float wd, int zero_g) {
-    const float beta1 = (float)beta1d, beta2 = (float)beta2d;        // element-wise arithmetic in fp32 as torch's; the powers in double
+    // element-wise arithmetic in fp32 as torch's; the powers in double.  The weights 1 - beta are torch's too: the DOUBLE 1 - beta rounded
+    // once (1.f - (float)0.999 is 1.3e-5 off 0.001: exp_avg_sq 50 times further from fp64 than torch's own fp32 step, tests/test_gpu_adam.py)
+    const float beta2 = (float)beta2d, w1 = (float)(1.0 - beta1d), w2 = (float)(1.0 - beta2d), w1c = 1.f - w1;
     const float bc1 = state[1], bc2s = state[2];
     const float step_size = lr / bc1;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
@@ -238,8 +240,9 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, f
         const float pi = p[i];
         if (zero_g) g[i] = 0.f;
         if (wd != 0.f) gi = fmaf(wd, pi, gi);
-        const float mi = m[i] + (gi - m[i]) * (1.f - beta1);          // torch: exp_avg.lerp_(grad, 1-beta1)
-        const float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;      // exp_avg_sq.mul_(b2).addcmul_(g,g,1-b2)
+        const float d = gi - m[i];                                    // torch: exp_avg.lerp_(grad, 1-beta1); ATen's lerp takes the form
+        const float mi = w1 < 0.5f ? m[i] + d * w1 : gi - d * w1c;    // that is exact at its end for weights >= 0.5 (beta1 = 0: m = g)
+        const float vi = beta2 * v[i] + w2 * gi * gi;                 // exp_avg_sq.mul_(b2).addcmul_(g,g,1-b2)
         m[i] = mi;
         v[i] = vi;
         const float denom = sqrtf(vi) / bc2s + eps;
@@ -251,7 +254,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, f
         unsigned* counter = (unsigned*)(state + 3);
         if (__hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
             double* pw = (double*)(state + 4);
-            const double b1p = pw[0] * beta1d, b2p = pw[1] * beta2d;
+            const double b1p = aesr_adam_next_power(pw[0], beta1d), b2p = aesr_adam_next_power(pw[1], beta2d);
             pw[0] = b1p;
             pw[1] = b2p;
             state[0] += 1.f;

@@ -321,8 +321,23 @@ class HipAdam(torch.optim.Adam):
             p.grad = self.flat_g[off:off + k].view_as(p.data)
             self.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.flat_m[off:off + k].view_as(p.data),
                              "exp_avg_sq": self.flat_v[off:off + k].view_as(p.data)}
+            if p.requires_grad:
+                p.register_hook(self._before_accumulation(p, self.flat_g.data_ptr() + 4 * off))
             off += k
         self.numel = n
+
+    def _before_accumulation(self, p, view_ptr):
+        """Hook on ``p``: stock autograd is about to ADD a gradient to ``p.grad``.  The engine hands autograd ``None`` for every gradient it
+        wrote itself (``engine.SequentialRunner._grad_dst``), and a hook sees that ``None`` and does nothing: no launch on the engine's path.  A gradient
+        that does arrive meets a buffer that ``zero_grad()`` declared zero: under ``lazy_zero`` it still holds the previous step's values and
+        gets its zeros now, and in either mode the buffer is no longer fresh -- a later direct write would drop what was added."""
+        def hook(grad):
+            if grad is None or not getattr(p, "_aesr_grad_fresh", False) or p.grad is None or p.grad.data_ptr() != view_ptr:
+                return
+            if self._pending_zero:
+                p.grad.zero_()
+            p._aesr_grad_fresh = False
+        return hook
 
     def _init_state(self, steps_done):
         """Device state of aesr_adam_step for an optimizer that has taken ``steps_done`` steps (bias corrections of the next one)."""
@@ -349,8 +364,9 @@ class HipAdam(torch.optim.Adam):
 
     def zero_grad(self, set_to_none=False):
         """Gradients count as zero from here on.  ``lazy_zero`` (default): no memset node -- the engine OVERWRITES the gradient of
-        every parameter it differentiates (``_aesr_grad_fresh``), and ``step()`` zeroes the few it did not reach before Adam reads
-        them; until then the buffer of an unreached parameter still holds the previous step's values."""
+        every parameter it differentiates (``_aesr_grad_fresh``), a gradient that comes through stock autograd accumulation finds its
+        buffer zeroed just before it is added (``_before_accumulation``), and ``step()`` zeroes the few no backward pass reached before
+        Adam reads them; until then the buffer of an unreached parameter still holds the previous step's values."""
         self._check_views()
         if not self.lazy_zero:
             self.flat_g.zero_()

@@ -567,6 +567,8 @@ def test_lerp_mse_act_adam(hip):
         # zero_grad: the gradient buffer is left at zero (odd k) or untouched (even k); the step counter advances once per launch
         assert float(gd.abs().max()) == 0.0 if k % 2 else torch.equal(gd.cpu(), gr)
         assert float(state[0]) == k + 1 and state.view(torch.int32)[3].item() == 0
+    # (rel-L2 1e-6 on parameters of size ~1 lets every update of ~1e-3 be 0.1 % off: tests/test_gpu_adam.py holds p, exp_avg and exp_avg_sq
+    # of every step to 4 x torch's own fp32 error against fp64, which makes this bound redundant -- kept as the coarse first line)
     assert rel_l2(pd, pt.detach()) < 1e-6 and float(state[0]) == 3.0
 
 

@@ -319,6 +319,25 @@ def test_trainer_steps_vs_reference_trainers(tag):
     assert nbt["enc.5.num_batches_tracked"] == n and nbt["decoder_head2.2.num_batches_tracked"] == (n if tag == "plain" else 2 * n)
 
 
+@pytest.mark.parametrize("tag", ["plain", "caisr_lpips"])
+def test_first_optimizer_step_is_adam(tag):
+    """The first optimizer step, element by element, against -lr * g / (|g| + eps) on the fixture's ``grad0/*`` (tests/adam_util.py:
+    first_step_check; as tests/test_gpu_step.py::test_first_optimizer_step_is_adam): every trainable tensor, >= 75 % of each."""
+    import adam_util as au
+    rec = tm.load("step_k3_mc_%s.npz" % tag)
+    tr = make_trainer("ae" if tag == "plain" else "ae_combined", "perceptual" if tag.endswith("lpips") else "mse",
+                      {k[3:]: torch.from_numpy(v) for k, v in rec.items() if k.startswith("p0/")})
+    group = tr.opt_ae.param_groups[0]
+    assert group["lr"] == 1e-3 and float(tr.opt_ae.dev_state[0]) == 0.0
+    p0 = {k: p.detach().cpu().numpy().copy() for k, p in tr.model.named_parameters() if p.requires_grad}
+    tr.train({"image": torch.from_numpy(rec["image_0"]), "slice_between": torch.from_numpy(rec["between_0"])}, keep_predictions=False)
+    assert float(tr.opt_ae.dev_state[0]) == 1.0                                       # one optimizer step per train()
+    p1 = {k: p.detach().cpu().numpy().copy() for k, p in tr.model.named_parameters() if p.requires_grad}
+    share, where, worst = au.first_step_check(p0, p1, {k[6:]: v for k, v in rec.items() if k.startswith("grad0/")}, group["lr"], group["eps"],
+                                              group["weight_decay"])
+    print("mc %s: first step within %.4f lr of -lr g / (|g| + eps); smallest share compared %.3f (%s)" % (tag, worst, share, where))
+
+
 def test_trainers_are_single_process_and_eval_steps_do_not_move_parameters():
     rec = tm.load("step_k3_mc_caisr_mse.npz")
     tr = make_trainer("ae_combined", "mse", {k[3:]: torch.from_numpy(v) for k, v in rec.items() if k.startswith("p0/")})

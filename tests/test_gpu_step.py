@@ -214,6 +214,26 @@ def test_three_train_steps(tag, record_property):
                                        err_msg=k)
 
 
+@pytest.mark.parametrize("tag", ["cardiac_mse", "brain_lpips", "ae_plain", "cardiac_percept", "cardiac_mse_s3"])
+def test_first_optimizer_step_is_adam(tag):
+    """The first optimizer step of the trainer, element by element: with zero moments Adam moves a parameter by -lr * g / (|g| + eps) whatever
+    the betas, so p - p0 is checked against that expression on the fixture's ``grad0/*`` wherever the gradient is clear of rounding
+    (tests/adam_util.py: first_step_check -- bound 0.02 lr + ulp(p), >= 75 % of EVERY trainable tensor compared).  The trajectory bounds of
+    test_three_train_steps (2 lr per step, 97 % within 0.2 lr) cannot see a parameter that never trains or a step of the wrong size."""
+    import adam_util as au
+    rec = dict(np.load(os.path.join(GOLDEN, "step_k3_%s.npz" % tag)))
+    trainer = make_trainer(tag, rec)
+    group = trainer.opt_ae.param_groups[0]
+    assert group["lr"] == STEP_CASES[tag][1] and float(trainer.opt_ae.dev_state[0]) == 0.0
+    p0 = {k: p.detach().cpu().numpy().copy() for k, p in trainer.model.named_parameters() if p.requires_grad}
+    trainer.train(_batch(rec, 0), keep_predictions=False)
+    assert float(trainer.opt_ae.dev_state[0]) == 1.0                                  # one optimizer step per train()
+    p1 = {k: p.detach().cpu().numpy().copy() for k, p in trainer.model.named_parameters() if p.requires_grad}
+    share, where, worst = au.first_step_check(p0, p1, {k[6:]: v for k, v in rec.items() if k.startswith("grad0/")}, group["lr"], group["eps"],
+                                              group["weight_decay"])
+    print("%s: first step within %.4f lr of -lr g / (|g| + eps); smallest share compared %.3f (%s)" % (tag, worst, share, where))
+
+
 @pytest.mark.skipif(DIRECT_CONTROL, reason="this IS the control run")
 def test_direct_kernels_hold_the_round1_bounds():
     """Control for the looser Winograd-path bounds: the same golden step fixtures through the exact-fp32 direct kernels (implicit GEMM
