@@ -3,7 +3,7 @@
 90 x 224 x 224 at 1.4 x 1.4 x 1.1 mm:
   lax      -> 30 x 3 x 256 x 256: a long-axis stack (1.25 x 1.25 x 6 mm) through the volume's centre, tilted off its z axis
   rotated  -> 30 x 90 x 224 x 224: a grid of the same size turned 30 degrees about the oblique axis (1, 2, 3) through the centre
-Needs the GPU; prints a table and writes it to ``--out`` (kept in profiles/reslice.txt).
+Needs the GPU; prints a table and appends it to ``--out`` (profiles/reslice.txt, which also holds hand-written notes and compiler remarks).
 
 - call:   HIP events around ``evaluate.reslice.reslice_affine`` / ``reslice_grid`` on device tensors (the matrix on the host, the output's
           allocation, one launch), after ``--warmup`` calls; median / min / max of ``--reps`` calls.
@@ -15,7 +15,12 @@ Needs the GPU; prints a table and writes it to ``--out`` (kept in profiles/resli
           8 TB/s HBM peak is those bytes over the kernel time.
 - torch:  ``torch.nn.functional.grid_sample(mode='bilinear', padding_mode='zeros', align_corners=True)`` on the same device, with the grid
           expanded over the frames ([N, 1, Z, H, W] input) and with the frames as channels ([1, N, Z, H, W] input, one grid), and the largest
-          difference between its result and the kernel's."""
+          difference between its result and the kernel's.
+- taps:   the higher-order interpolators of csrc/reslice_taps.hip on the same two workloads, each launch timed alone: the B-spline's
+          pre-filter (``aesr_bspline_prefilter_3d``, three passes) apart from its 64-tap gather, ``lanczos`` and ``cosine`` at radius 5
+          (1000 taps).  GMAC/s: fp64 multiply-adds of the tap sum (taps x frames x voxels inside the source) over the kernel time;
+          "x linear": the kernel time over the trilinear kernel's, measured again in the same run.  Beside them
+          ``scipy.ndimage.map_coordinates(order=3, mode='mirror')`` on the host for ONE frame (``--no-scipy`` skips it)."""
 import argparse
 import os
 import statistics
@@ -93,6 +98,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=5)
+    ap.add_argument("--no-scipy", dest="scipy", action="store_false", help="skip the host's map_coordinates(order=3) row (seconds per case)")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "reslice.txt"))
     args = ap.parse_args()
     assert torch.cuda.is_available(), "reslice_bench.py measures on the GPU; there is no CPU fallback"
@@ -113,6 +119,8 @@ def main():
         c = coordinates(M, shape)
         n_out, n_src = Zo * Ho * Wo, touched_voxels(c, SAX_SHAPE)
         grid = torch.from_numpy((c / ((size - 1) / 2) - 1).astype(np.float32)).cuda()
+        n_inside = int(((c >= -0.5) & (c < size - 0.5)).all(axis=-1).sum())          # the voxels the higher-order kernels compute
+        zyx = np.ascontiguousarray(np.moveaxis(c[..., ::-1], -1, 0))
         del c
         m = np.ascontiguousarray(M[:3], np.float64)
         mp = m.ctypes.data_as(_hip.DP)
@@ -142,6 +150,38 @@ def main():
             call_txt = "%9.1f %9.1f %9.1f" % (statistics.median(tc) * 1e6, min(tc) * 1e6, max(tc) * 1e6) if tc else "%29s" % "-"
             say("%-22s %-26s | %s | %9.1f %9.1f %9.1f | %8.1f %7.1f%% | %.1f" % (name, label, call_txt, med * 1e6, min(tk) * 1e6, max(tk) * 1e6,
                                                                             nbytes / med / 1e9, 100 * nbytes / med / HBM_PEAK, nbytes / 1e6))
+        # the higher-order interpolators (csrc/reslice_taps.hip) beside the trilinear row of this run
+        t_linear = statistics.median([t / args.batch for t in event_times(affine(y, 1), 1, args.reps)])
+        coef = rl.bspline_coefficients_3d(x)
+
+        def taps(kernel, radius):
+            src_p, coef_p = (None, _hip.ptr(coef)) if kernel == _hip.TAPS_BSPLINE3 else (_hip.ptr(x), None)
+            return lambda: _hip.check(_hip.lib.aesr_reslice_taps_affine(src_p, coef_p, _hip.ptr(y), N, Zs, Hs, Ws, Zo, Ho, Wo, mp, kernel, radius, 0,
+                                                                          _hip.stream()), "taps")
+
+        def prefilter():
+            _hip.check(_hip.lib.aesr_bspline_prefilter_3d(_hip.ptr(x), _hip.ptr(coef), N, Zs, Hs, Ws, _hip.stream()), "prefilter")
+        reps = max(3, args.reps // 4)
+        say("%-22s %-26s | %-29s | %10s %10s | %s" % (name, "path (%d of %d voxels inside)" % (n_inside, n_out), "kernel med/min/max [us]", "GMAC/s",
+                                                      "x linear", "fp64 multiply-adds"))
+        for label, fn, macs in (("bspline pre-filter (3 passes)", prefilter, None), ("bspline gather", taps(_hip.TAPS_BSPLINE3, 5), 64.0 * N * n_inside),
+                                ("lanczos r=5", taps(_hip.TAPS_LANCZOS, 5), 1000.0 * N * n_inside), ("cosine r=5", taps(_hip.TAPS_COSINE, 5), 1000.0 * N * n_inside)):
+            tk = event_times(fn, 1, reps)
+            med = statistics.median(tk)
+            rate = "%10.1f" % (macs / med / 1e9) if macs else "%10s" % "-"
+            say("%-22s %-26s | %9.1f %9.1f %9.1f | %s %10.2f | %s" % (name, label, med * 1e6, min(tk) * 1e6, max(tk) * 1e6, rate, med / t_linear,
+                                                                   "%.3g" % macs if macs else "-"))
+        del coef
+        torch.cuda.empty_cache()
+        if args.scipy:
+            from scipy import ndimage
+            import time
+            frame = x[0].cpu().numpy().astype(np.float64)
+            t0 = time.perf_counter()
+            ndimage.map_coordinates(frame, zyx, order=3, mode="mirror", output=np.float64)
+            say("%-22s %-50s | %9.1f us for ONE frame (pre-filter included)" % (name, "scipy.ndimage.map_coordinates(order=3) on the host",
+                                                                               (time.perf_counter() - t0) * 1e6))
+        del zyx
         ours = rl.reslice_affine(x, M, shape, "linear")
         g5 = grid.unsqueeze(0)
         forms = (("torch grid_sample, grid expanded over the frames", lambda: torch.nn.functional.grid_sample(
@@ -156,8 +196,9 @@ def main():
         del ours, grid, g5, spare, y, y4
         torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    # appended: the file also holds the prose around earlier runs and the compiler's resource-usage remarks, which a run must not erase
+    with open(args.out, "a") as f:
+        f.write("\n" + "\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":

@@ -243,6 +243,14 @@ SHAPE_INTERP_ENTRIES = {
     "aesr_shape_interpolate": (c_int, [P, P, P, P] + [c_int] * 6 + [IP, P]),
 }
 SHAPE_MAX_CLASSES, SHAPE_MAX_W = 8, 4096          # AESR_SHAPE_* of csrc/shape_interp.h
+# Reslicing with a cubic B-spline or a windowed sinc (csrc/reslice_taps.hip).  As above: exported and bound by _load(), declared in
+# csrc/reslice_taps.h and not under include/, so not in HEADERS and not named SIGNATURES*; tests/test_reslice_taps_golden.py checks the table
+# against the prototypes.
+RESLICE_TAPS_ENTRIES = {
+    "aesr_bspline_prefilter_3d": (c_int, [P, P] + [c_int] * 4 + [P]),
+    "aesr_reslice_taps_affine": (c_int, [P, P, P] + [c_int] * 7 + [DP, c_int, c_int, c_int, P]),
+}
+TAPS_BSPLINE3, TAPS_LANCZOS, TAPS_COSINE, TAPS_MIN_RADIUS, TAPS_MAX_RADIUS = 0, 1, 2, 3, 5          # AESR_TAPS_* of csrc/reslice_taps.h
 # The C ABI, header by header in the order the headers were added: each table must list every symbol its header under include/ declares,
 # with the types of the prototype, and no symbol may stand in two (tests/test_abi.py checks all of it against the headers and the library).
 # _load() binds exactly these tables; include/ is not read at run time.
@@ -285,7 +293,7 @@ def _load():
             "libaesr_hip.so not found at %s -- build it with `python __graft_entry__.py` (or `make -C "
             "superresolution_aniso_mri_amd/csrc`). The HIP extension is mandatory: there is no CPU/eager fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for table in list(HEADERS.values()) + [SHAPE_INTERP_ENTRIES]:
+    for table in list(HEADERS.values()) + [SHAPE_INTERP_ENTRIES, RESLICE_TAPS_ENTRIES]:
         for name, (res, args) in table.items():
             fn = getattr(lib, name, None)
             if fn is None:

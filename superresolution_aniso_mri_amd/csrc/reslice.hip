@@ -19,15 +19,12 @@
 #include "../../include/aesr_hip_reslice.h"
 #include "aesr_kernels.h"
 #include "aesr_hostcheck.h"
+#include "reslice_position.h"
 
 #pragma clang fp contract(off)
 
 #define RSL_THREADS 256
 #define RSL_LX 64          // lanes along the output x: one wave is one row segment of a tile
-
-struct RslAffine {
-    double m[12];          // rows of the 3x4 matrix: source (x, y, z) = M * (xo, yo, zo, 1)
-};
 
 // one axis of the trilinear rule: position c on an axis of n samples -> clamped indices of the two neighbours, their weights and validity
 __device__ __forceinline__ void rsl_axis_linear(double c, int n, int idx[2], double w[2], bool ok[2]) {
@@ -74,9 +71,7 @@ __global__ __launch_bounds__(RSL_THREADS) void reslice_kernel(const float* __res
             p[1] = ((double)g[1] + 1.0) / 2.0 * (double)(Hs - 1);
             p[2] = ((double)g[2] + 1.0) / 2.0 * (double)(Zs - 1);
         } else {
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-                p[a] = ((A.m[4 * a] * (double)xo + A.m[4 * a + 1] * (double)yo) + A.m[4 * a + 2] * (double)zo) + A.m[4 * a + 3];
+            rsl_affine_position(A, xo, yo, (int)zo, p);
         }
         if (LINEAR) {
             int ix[2], iy[2], iz[2];

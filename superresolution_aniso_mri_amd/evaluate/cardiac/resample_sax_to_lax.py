@@ -18,7 +18,9 @@ Deviations from the reference, on purpose:
   - ``make_transform`` raises ValueError for a SAX side of 1, where the reference divides by zero.
 
 Command line:  python -m superresolution_aniso_mri_amd.evaluate.cardiac.resample_sax_to_lax --sax S.nii.gz --lax L.nii.gz --out O.nii.gz
-[--interp linear|nearest]: every frame of the SAX file on the grid of the LAX file (float64 affine path), written with the LAX header."""
+[--interp linear|nearest|bspline|lanczos|cosine] [--radius 3|4|5] [--clamp01]: every frame of the SAX file on the grid of the LAX file
+(float64 affine path), written with the LAX header.  ``cosine`` with radius 5 is the interpolator of the reference's
+kwatsch/create_nifti_from_dicom.py (``sitk.sitkCosineWindowedSinc``); csrc/reslice_taps.hip."""
 import argparse
 import sys
 
@@ -111,7 +113,11 @@ def parse_args(argv=None):
     ap.add_argument("--sax", required=True, help="the short-axis volume, 3-D or 4-D (.nii, .nii.gz, .mha, .mhd)")
     ap.add_argument("--lax", required=True, help="the long-axis scan whose grid and header the output takes")
     ap.add_argument("--out", required=True, help="the file to write (.nii, .nii.gz, .mha, .mhd)")
-    ap.add_argument("--interp", choices=sorted(_reslice.INTERPS), default="linear")
+    ap.add_argument("--interp", choices=list(_reslice.AFFINE_INTERPS), default="linear",
+                    help="bspline: cubic B-spline; lanczos, cosine: windowed sincs (cosine is the reference's sitkCosineWindowedSinc)")
+    ap.add_argument("--radius", type=int, choices=list(_reslice.RADII), default=5, help="radius of lanczos and cosine (default 5)")
+    ap.add_argument("--clamp01", action="store_true", help="clamp the result of bspline, lanczos or cosine to [0, 1] (linear and nearest "
+                                                            "cannot leave the range of the samples and ignore it)")
     return ap.parse_args(argv)
 
 
@@ -122,7 +128,7 @@ def main(argv=None):
         if str(getattr(args, flag)).lower().endswith(".npy"):
             sys.exit("--%s %s: a .npy file has no geometry (spacing, origin, direction); give a NIfTI or MetaImage file" % (flag, getattr(args, flag)))
     sax, lax = volume_io.read_volume(args.sax), volume_io.read_volume(args.lax)
-    res = _reslice.reslice_like(sax, lax, interp=args.interp)
+    res = _reslice.reslice_like(sax, lax, interp=args.interp, radius=args.radius, clamp01=args.clamp01)
     spacing = list(lax.spacing[:3])
     if res.ndim == 4:
         spacing.append(sax.spacing[3] if len(sax.spacing) > 3 else 1.0)

@@ -7,7 +7,13 @@ A ``Geometry`` is what SimpleITK calls spacing, origin and direction, in its (x,
 sits at ``origin + direction @ (spacing * (i, j, k))``, i.e. at ``T @ R @ S @ (i, j, k, 1)`` (``index_to_world``).  All matrix algebra is
 float64 on the host; the kernel receives the 3x4 matrix that takes an OUTPUT voxel index to a SOURCE voxel index and evaluates it in fp64.
 Interpolation is trilinear with zero padding (a corner outside the source contributes nothing) or nearest (halves to even), exactly
-``torch.nn.functional.grid_sample(..., padding_mode='zeros', align_corners=True)`` on a 5-D input."""
+``torch.nn.functional.grid_sample(..., padding_mode='zeros', align_corners=True)`` on a 5-D input.
+
+The affine path also takes three higher-order interpolators (csrc/reslice_taps.hip, csrc/reslice_taps.h): ``bspline``, the cubic B-spline
+over a separable 3-D pre-filter (``scipy.ndimage.map_coordinates(order=3, mode='mirror')``), and the windowed sincs ``lanczos`` and
+``cosine`` of radius 3, 4 or 5 (ITK's WindowedSincInterpolateImageFunction; ``cosine`` is what the reference's
+kwatsch/create_nifti_from_dicom.py reslices with).  They follow ITK's buffer rule: a voxel is computed only where
+``-0.5 <= p < size - 0.5`` on every axis and is 0 elsewhere.  DESIGN.md section 2 has the definitions and what pins them."""
 import numpy as np
 import torch
 
@@ -15,6 +21,9 @@ from .. import _hip
 from .._hip import check, lib, ptr, stream
 
 INTERPS = {"nearest": _hip.RESLICE_NEAREST, "linear": _hip.RESLICE_LINEAR}
+TAP_KERNELS = {"bspline": _hip.TAPS_BSPLINE3, "lanczos": _hip.TAPS_LANCZOS, "cosine": _hip.TAPS_COSINE}          # the affine path only
+AFFINE_INTERPS = tuple(sorted(INTERPS)) + tuple(sorted(TAP_KERNELS))
+RADII = tuple(range(_hip.TAPS_MIN_RADIUS, _hip.TAPS_MAX_RADIUS + 1))
 
 
 class Geometry:
@@ -59,6 +68,25 @@ def _interp_code(interp):
     return INTERPS[interp]
 
 
+def _check_affine_interp(interp, radius):
+    if interp not in AFFINE_INTERPS:
+        raise ValueError("interp=%r: expected one of %s" % (interp, ", ".join(AFFINE_INTERPS)))
+    if isinstance(radius, bool) or radius not in RADII:
+        raise ValueError("radius=%r: the radius of a windowed sinc is one of %s" % (radius, RADII))
+    return int(radius)
+
+
+def bspline_coefficients_3d(x4):
+    """CUDA float32 [N, Z, H, W] -> CUDA float64 coefficients of the same shape: ``scipy.ndimage.spline_filter(order=3, mode='mirror')`` of
+    every frame (three launches, y and x in place)."""
+    _hip.require_gpu_tensor(x4, "x4")
+    N, Z, H, W = (int(s) for s in x4.shape)
+    coef = torch.empty((N, Z, H, W), device=x4.device, dtype=torch.float64)
+    with torch.cuda.device(x4.device):
+        check(lib.aesr_bspline_prefilter_3d(ptr(x4), ptr(coef), N, Z, H, W, stream()), "aesr_bspline_prefilter_3d")
+    return coef
+
+
 def _to_device(src):
     """(CUDA float32 contiguous [N, Z, H, W], was 3-D, was numpy)"""
     is_np = not torch.is_tensor(src)
@@ -85,11 +113,14 @@ def _out_shape(ref_shape):
     return shape
 
 
-def reslice_affine(src, matrix, ref_shape, interp="linear"):
+def reslice_affine(src, matrix, ref_shape, interp="linear", radius=5, clamp01=False):
     """``matrix`` ([3, 4] or [4, 4], float64): source voxel (x, y, z) = matrix @ (xo, yo, zo, 1) for every voxel of the output grid
     ``ref_shape`` = [z, y, x].  ``src``: [Z, Y, X] or [T, Z, Y, X]; numpy in -> numpy out (one upload, one download), a CUDA tensor in -> a
-    new CUDA tensor out.  All frames are one launch; nothing is synchronised for device input."""
-    code = _interp_code(interp)
+    new CUDA tensor out.  All frames are one launch (``bspline``: the pre-filter's launches into a float64 buffer of the source's shape
+    first); nothing is synchronised for device input.  ``interp``: one of AFFINE_INTERPS; ``radius`` (3, 4 or 5) is the radius of
+    ``lanczos`` and ``cosine``, validated and otherwise ignored; ``clamp01`` clamps the fp32 result of those three to [0, 1] in the
+    kernel; like ``radius`` it is ignored by ``linear`` and ``nearest``, which cannot leave the range of the samples."""
+    radius = _check_affine_interp(interp, radius)
     m = np.ascontiguousarray(np.asarray(matrix, dtype=np.float64)[:3, :4])
     if m.shape != (3, 4) or not np.isfinite(m).all():
         raise ValueError("matrix must be a finite 3x4 or 4x4 (got shape %s)" % (np.shape(matrix),))
@@ -98,14 +129,24 @@ def reslice_affine(src, matrix, ref_shape, interp="linear"):
     N, Zs, Hs, Ws = (int(s) for s in x4.shape)
     out = torch.empty((N, Zo, Ho, Wo), device=x4.device, dtype=torch.float32)
     with torch.cuda.device(x4.device):
-        check(lib.aesr_reslice_affine(ptr(x4), ptr(out), N, Zs, Hs, Ws, Zo, Ho, Wo, m.ctypes.data_as(_hip.DP), code, stream()), "aesr_reslice_affine")
+        if interp in INTERPS:
+            check(lib.aesr_reslice_affine(ptr(x4), ptr(out), N, Zs, Hs, Ws, Zo, Ho, Wo, m.ctypes.data_as(_hip.DP), INTERPS[interp], stream()),
+                  "aesr_reslice_affine")
+        else:
+            coef = bspline_coefficients_3d(x4) if interp == "bspline" else None
+            check(lib.aesr_reslice_taps_affine(None if coef is not None else ptr(x4), ptr(coef), ptr(out), N, Zs, Hs, Ws, Zo, Ho, Wo,
+                                               m.ctypes.data_as(_hip.DP), TAP_KERNELS[interp], radius, int(bool(clamp01)), stream()),
+                  "aesr_reslice_taps_affine")
     out = out[0] if was3d else out
     return out.cpu().numpy() if is_np else out
 
 
 def reslice_grid(src, grid, interp="linear"):
     """``grid``: [Zo, Yo, Xo, 3] = (x, y, z) normalised to [-1, 1] (``grid_sample`` with ``align_corners=True``), numpy or tensor, one grid
-    for all frames.  Otherwise as ``reslice_affine``."""
+    for all frames.  Otherwise as ``reslice_affine``, with ``linear`` and ``nearest`` only: the higher-order interpolators are on the
+    affine path."""
+    if interp in TAP_KERNELS:
+        raise ValueError("interp=%r is on the affine path only (reslice_affine, reslice, reslice_like); a grid takes 'linear' or 'nearest'" % (interp,))
     code = _interp_code(interp)
     x4, was3d, is_np = _to_device(src)
     g = grid if torch.is_tensor(grid) else torch.from_numpy(np.ascontiguousarray(grid, dtype=np.float32))
@@ -121,12 +162,13 @@ def reslice_grid(src, grid, interp="linear"):
     return out.cpu().numpy() if is_np else out
 
 
-def reslice(src, src_geom, ref_geom, ref_shape, interp="linear"):
+def reslice(src, src_geom, ref_geom, ref_shape, interp="linear", radius=5, clamp01=False):
     """``src`` ([Z, Y, X] or [T, Z, Y, X]) with geometry ``src_geom`` on the grid ``ref_shape`` = [z, y, x] of geometry ``ref_geom``."""
-    return reslice_affine(src, affine_between(src_geom, ref_geom), ref_shape, interp)
+    return reslice_affine(src, affine_between(src_geom, ref_geom), ref_shape, interp, radius=radius, clamp01=clamp01)
 
 
-def reslice_like(src_volume, ref_volume, interp="linear"):
+def reslice_like(src_volume, ref_volume, interp="linear", radius=5, clamp01=False):
     """A ``volume_io.Volume`` on the grid of another: every frame of ``src_volume`` on the [z, y, x] grid of ``ref_volume``; float32
     [z, y, x] or [T, z, y, x] with T the frame count of the SOURCE."""
-    return reslice(src_volume.array, Geometry.from_volume(src_volume), Geometry.from_volume(ref_volume), ref_volume.array.shape[-3:], interp)
+    return reslice(src_volume.array, Geometry.from_volume(src_volume), Geometry.from_volume(ref_volume), ref_volume.array.shape[-3:], interp,
+                   radius=radius, clamp01=clamp01)
