@@ -8,7 +8,11 @@ file plus --cuda-device-only -S, drops comment lines, .file / .ident / .loc and 
 per kernel: mangled name, sgpr / vgpr / spilled-vgpr counts of the metadata, instructions, "identical" or "DIFFERENT".  A source that
 only one tree has counts as one without kernels in the other.  Kernels are compared as a set and the rest of a listing as a bag of
 lines: another order of instantiation is reported as that.  Exit status 1 unless every file has the same kernels, each identical, and
-the same lines."""
+the same lines.
+
+--sub-new REGEX REPL (repeatable) rewrites every line of the NEW tree's listings before the comparison: a kernel that gained a template
+parameter has another mangled name, and with its default value's suffix taken out again (e.g. 'ELb0EEv9WgradArgs' 'EEv9WgradArgs') the
+instantiations that existed before are compared with their old selves; the ones that are new stay listed as "only in the new tree"."""
 import argparse
 import concurrent.futures
 import os
@@ -29,7 +33,7 @@ def makefile(csrc):
     return srcs, lambda name: base + extra.get(name, [])
 
 
-def listing(csrc, name, tmp):
+def listing(csrc, name, tmp, subs=()):
     if not os.path.exists(os.path.join(csrc, name)):
         return []
     out = os.path.join(tmp, name + ".s")
@@ -40,6 +44,8 @@ def listing(csrc, name, tmp):
         t = l.strip()
         if t.startswith(";") or t.startswith((".file", ".ident", ".loc")) or "__hip_cuid_" in l:
             continue
+        for pat, repl in subs:
+            l = re.sub(pat, repl, l)
         keep.append(l.rstrip())
     return keep
 
@@ -54,7 +60,8 @@ def kernels(lines):
     res = {}
     for name in meta:           # label .. .Lfunc_end: the instructions and the kernel descriptor
         m = re.search(r"^" + re.escape(name) + r":.*?\n(.*?)^\.Lfunc_end\d+:", text, re.S | re.M)
-        res[name] = (m.group(1).split("\n"), meta[name])
+        # (.LBB<f>_<n>: f is the function's ordinal in its file -- an instantiation added in front renumbers the labels, not the code)
+        res[name] = (re.sub(r"\.LBB\d+_", ".LBB_", m.group(1)).split("\n"), meta[name])
     return res
 
 
@@ -64,6 +71,7 @@ def main():
     ap.add_argument("new")
     ap.add_argument("files", nargs="*")
     ap.add_argument("-o", "--out")
+    ap.add_argument("--sub-new", nargs=2, action="append", default=[], metavar=("REGEX", "REPL"))
     args = ap.parse_args()
     if not args.files:
         old_srcs, new_srcs = makefile(args.old)[0], makefile(args.new)[0]
@@ -71,7 +79,7 @@ def main():
     rows, same = [], True
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
         with concurrent.futures.ThreadPoolExecutor(8) as ex:          # the compiles run side by side
-            jobs = [(ex.submit(listing, args.old, name, ta), ex.submit(listing, args.new, name, tb)) for name in args.files]
+            jobs = [(ex.submit(listing, args.old, name, ta), ex.submit(listing, args.new, name, tb, args.sub_new)) for name in args.files]
         for name, (ja, jb) in zip(args.files, jobs):
             la, lb = ja.result(), jb.result()
             ka, kb = kernels(la), kernels(lb)
@@ -84,7 +92,10 @@ def main():
                 same &= not ka and not kb
             for k in sorted(set(ka) | set(kb)):
                 if k not in ka or k not in kb:
-                    rows.append("  %s\n    only in the %s tree" % (k, "old" if k in ka else "new"))
+                    body, f = (ka if k in ka else kb)[k]
+                    rows.append("  %s\n    sgpr %s vgpr %s vgpr_spill %s instructions %d  only in the %s tree" % (
+                        k, f["sgpr_count"], f["vgpr_count"], f["vgpr_spill_count"],
+                        sum(1 for l in body if l.startswith("\t") and not l.strip().startswith(".")), "old" if k in ka else "new"))
                     continue
                 body, f = kb[k]
                 ninstr = sum(1 for l in body if l.startswith("\t") and not l.strip().startswith("."))
@@ -92,7 +103,8 @@ def main():
                     ka[k][1]["sgpr_count"], ka[k][1]["vgpr_count"], ka[k][1]["vgpr_spill_count"])
                 rows.append("  %s\n    sgpr %s vgpr %s vgpr_spill %s instructions %d  %s" % (
                     k, f["sgpr_count"], f["vgpr_count"], f["vgpr_spill_count"], ninstr, verdict))
-    report = ("device listings (hipcc <the Makefile's CXXFLAGS of each file> --cuda-device-only -S), normalised, old tree against new\n" + "\n".join(rows)
+    report = ("device listings (hipcc <the Makefile's CXXFLAGS of each file> --cuda-device-only -S), normalised, old tree against new\n"
+              + "".join("new tree's lines rewritten: s/%s/%s/\n" % tuple(sr) for sr in args.sub_new) + "\n".join(rows)
               + "\n%s\n" % ("every kernel identical" if same else "NOT the same"))
     sys.stdout.write(report)
     if args.out:

@@ -79,6 +79,7 @@ __device__ __forceinline__ f32x4 ww_sub4(f32x4 a, f32x4 b) {
     asm("v_pk_add_f32 %0, %1, %2 " WW_M_SUB : "=v"(hi) : "v"(ahi), "v"(bhi));
     return (f32x4){lo.x, lo.y, hi.x, hi.y};
 }
+#define WW_Z4 ((f32x4){0.f, 0.f, 0.f, 0.f})     /* a literal, not a variable: a lambda would capture it, and the listing moves with the closure */
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));       // a 16-byte store to an address that is only 4-byte aligned
 
 // A spatial tile this workgroup visits; all uniform (SGPRs)
@@ -96,9 +97,22 @@ struct WwTile {
 constexpr int WW_NTS = 10;          // 0 entry, 1 DMAs of tiles 0 / 1 issued, 2 tile 0 landed + barrier, 3 first MFMA, 4 loop end, 5 drain wait + barrier,
                                     // 6 dg done, 7 exchange barrier, 8 slab stores issued, 9 stores retired (exit)
 constexpr int WW_DBG_WAVES = 4096 * 4;
-template <int TH, int TW, bool STAMP, bool LEAN>
+// the k-th position that is computed (all 16, or the nine 4 r + k with r, k in {0, 1, 3}); a position that is not: dU is +0 there
+template <bool NINE>
+__host__ __device__ constexpr int ww_xi(int k) { return NINE ? 4 * (k / 3 == 2 ? 3 : k / 3) + (k % 3 == 2 ? 3 : k % 3) : k; }
+template <bool NINE>
+__host__ __device__ constexpr bool ww_dead(int x) { return NINE && ((x >> 2) == 2 || (x & 3) == 2); }
+
+// NINE (x_up2, the layer behind a nearest Upsample(x2); AESR_WINO_UP2_NINE=0 selects the 16-position instantiation, same results bit for
+// bit): a Winograd tile starts at an even pixel, so rows 1 and 2 of its 4 x 4 patch are the same stored row and columns 1 and 2 the same
+// stored column (at every border too: H and W are even).  Row 2 of B^T is d2 - d1: V[2][.] and V[.][2] are exactly +0, and so is
+// dU_xi = sum V_xi dM_xi at the 7 positions xi = 4 r + k with r == 2 or k == 2.  Only the other nine are computed: 36 accumulator quads
+// (144 accumulation registers), 36 MFMAs per k-step instead of 64, and the transform statements that feed nothing else are left out; the
+// epilogue takes +0 where the 16-position form reads those accumulators.
+template <int TH, int TW, bool STAMP, bool LEAN, bool NINE = false>
 __global__ __launch_bounds__(256, 1) void conv_wgrad_wino_f32(WgradArgs a) {
     constexpr int CIT = 32, COT = 32;
+    constexpr int NPOS = NINE ? 9 : 16, NQ = 4 * NPOS;              // positions computed, the k-th of them is ww_xi<NINE>(k); MFMAs of a k-step
     static_assert((TH == 16 && TW == 8) || (TH == 8 && TW == 16), "tiles: 8 k-steps, rows of whole 8-pixel DMA segments");
     constexpr int PH = TH + 2, PWL = TW == 8 ? 16 : 32, TWL = TW;     // LDS row strides in pixels
     constexpr int XFL = PH * PWL * 32, DFL = TH * TWL * 32;            // floats of one X / dY buffer
@@ -197,7 +211,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_wino_f32(WgradArgs a) {
         });
     };
 
-    f32x4 acc[16][2][2];                    // [position][ci block][co block]: D rows = ci 4g..4g+3, column = co l15
+    f32x4 acc[16][2][2];                    // [position][ci block][co block]: D rows = ci 4g..4g+3, column = co l15 (NINE: dead positions are never touched)
     if constexpr (!LEAN) {
 #pragma unroll
         for (int x = 0; x < 16; ++x)
@@ -262,7 +276,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_wino_f32(WgradArgs a) {
                 constexpr int s_ = decltype(Sc)::value;
                 WW_PK(Vp[nb][i][s_][0], T[s_][0], T[s_][2], WW_M_SUB);
                 WW_PK(Vp[nb][i][s_][1], T[s_][1], T[s_][2], WW_M_ADD);
-                WW_PK(Vp[nb][i][s_][2], T[s_][2], T[s_][1], WW_M_SUB);
+                if constexpr (!NINE) WW_PK(Vp[nb][i][s_][2], T[s_][2], T[s_][1], WW_M_SUB);      // column 2 feeds dead positions only
                 WW_PK(Vp[nb][i][s_][3], T[s_][1], T[s_][3], WW_M_SUB);
             });
         });
@@ -273,16 +287,16 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_wino_f32(WgradArgs a) {
             WW_PK(Mp[nb][o][4], Mp[nb][o][0], Mp[nb][o][1], WW_M_LL);
             WW_PK(Mp[nb][o][7], Mp[nb][o][0], Mp[nb][o][1], WW_M_HH);
             WW_PK(Mp[nb][o][5], Mp[nb][o][2], Mp[nb][o][3], WW_M_LL);
-            WW_PK(Mp[nb][o][6], Mp[nb][o][2], Mp[nb][o][3], WW_M_HH);
+            if constexpr (!NINE) WW_PK(Mp[nb][o][6], Mp[nb][o][2], Mp[nb][o][3], WW_M_HH);        // M' row 2, columns 1 and 2: dead positions only
             accb[o] += Mp[nb][o][5][0];     // (y00 + y10) + (y01 + y11)
         });
     };
-    // MFMAs [Q0, Q0 + N) of the 64 of a k-step: A = V (M = ci), B = M' (N = co), K = the 4 tiles of the k-step.  The accumulators
+    // MFMAs [Q0, Q0 + N) of the NQ (64; NINE: 36, position ww_xi<NINE>(q >> 2)) of a k-step: A = V (M = ci), B = M' (N = co), K = the 4 tiles of the k-step.  The accumulators
     // are pinned to the accumulation registers ("+a"): left to itself the allocator moves parts of them through the (full) vector
     // registers and scratch.  Operands are a k-step old and an accumulator is touched once per k-step: no MFMA hazard is near.
     auto mfmas = [&](auto Q0c, auto Nc, int cb) {
         ww_rep<decltype(Nc)::value>([&](auto Dc) {
-            constexpr int q = decltype(Q0c)::value + decltype(Dc)::value, x = q >> 2, i = (q >> 1) & 1, o = q & 1;
+            constexpr int q = decltype(Q0c)::value + decltype(Dc)::value, x = ww_xi<NINE>(q >> 2), i = (q >> 1) & 1, o = q & 1;
             constexpr int r = x >> 2, k = x & 3;
             constexpr int mi = k == 0 ? (r == 0 || r == 3 ? 0 : 2) : k == 3 ? (r == 0 || r == 3 ? 1 : 3) : 4 + r;
             constexpr int mh = k == 0 || k == 3 ? (r >= 2 ? 1 : 0) : k - 1;
@@ -294,9 +308,10 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_wino_f32(WgradArgs a) {
     // uniform LDS float offsets of k-step ks = wave + 4 j: tile (tyl, 4 kx + g) has its top-left patch pixel at (2 tyl, 8 kx + 2 g)
     auto step_xu = [&](int j, int buf) { const int ks = wave + 4 * j, tyl = ks / KPR, kx = ks - tyl * KPR; return buf * XFL + ((2 * tyl) * PWL + 8 * kx) * 32; };
     auto step_du = [&](int j, int buf) { const int ks = wave + 4 * j, tyl = ks / KPR, kx = ks - tyl * KPR; return buf * DFL + ((2 * tyl) * TWL + 8 * kx) * 32; };
+    // the k-step's MFMAs in quarters: [0, Q1) behind the LDS reads, [Q1, Q2) behind the DMA issue, the rest behind the transform
     using C0 = std::integral_constant<int, 0>;
-    using C16 = std::integral_constant<int, 16>;
-    using C32 = std::integral_constant<int, 32>;
+    using Q1 = std::integral_constant<int, NQ / 4>;
+    using Q2 = std::integral_constant<int, NQ / 2>;
 
     // debug instantiation of the same loop (STAMP, AESR_WGRAD_WINO_DBG=1): cycles per wave in the k-step loop and at the barrier
     long long tph[3] = {0, 0, 0}, tq = 0;
@@ -325,9 +340,9 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_wino_f32(WgradArgs a) {
         // the accumulators are zeroed HERE, behind the DMA issue (the empty asm makes each zero a value of its own that exists from this
         // point on: left as plain constants they are written in front of the loop, after the wait)
         __builtin_amdgcn_sched_barrier(0);
-        ww_rep<64>([&](auto Qc) {
+        ww_rep<NQ>([&](auto Qc) {
             constexpr int q = decltype(Qc)::value;
-            f32x4& acc_ = acc[q >> 2][(q >> 1) & 1][q & 1];
+            f32x4& acc_ = acc[ww_xi<NINE>(q >> 2)][(q >> 1) & 1][q & 1];
             acc_ = (f32x4){0.f, 0.f, 0.f, 0.f};
             asm volatile("" : "+a"(acc_));
         });
@@ -353,9 +368,9 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_wino_f32(WgradArgs a) {
         // k-step 0 of the tile: MFMAs on operand set 0, the operands of k-step 1 into set 1
         __builtin_amdgcn_sched_barrier(0);
         op_read(step_xu(1, buf), step_du(1, buf), 1);
-        mfmas(C0{}, C16{}, 0);
+        mfmas(C0{}, Q1{}, 0);
         op_transform(1);
-        mfmas(C16{}, std::integral_constant<int, 48>{}, 0);
+        mfmas(Q1{}, std::integral_constant<int, NQ - NQ / 4>{}, 0);
         __builtin_amdgcn_sched_barrier(0);
         WW_STAMP(0)
         // The wait is OURS to place: the LDS reads of this kernel are asm statements the compiler does not see, so its own
@@ -367,13 +382,13 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_wino_f32(WgradArgs a) {
         // k-step 1: MFMAs on set 1, the first operands of the NEXT tile into set 0, the DMA of the tile after it into `buf`
         __builtin_amdgcn_sched_barrier(0);
         op_read(step_xu(0, buf ^ 1), step_du(0, buf ^ 1), 0);
-        mfmas(C0{}, C16{}, 1);
+        mfmas(C0{}, Q1{}, 1);
         __builtin_amdgcn_sched_barrier(0);
         fetch(t2, buf);
         __builtin_amdgcn_sched_barrier(0);
-        mfmas(C16{}, C16{}, 1);
+        mfmas(Q1{}, Q1{}, 1);
         op_transform(0);
-        mfmas(C32{}, C32{}, 1);
+        mfmas(Q2{}, Q2{}, 1);
         __builtin_amdgcn_sched_barrier(0);
         t0 = t1;
         t1 = t2;
@@ -399,7 +414,9 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_wino_f32(WgradArgs a) {
                 f32x4 R[3][4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const f32x4 u0_ = acc[0 + j][i][o], u1 = acc[4 + j][i][o], u2 = acc[8 + j][i][o], u3 = -acc[12 + j][i][o];
+                    // (NINE: +0 where a position is not computed -- what the 16-position form holds there)
+                    const f32x4 u0_ = ww_dead<NINE>(0 + j) ? WW_Z4 : acc[0 + j][i][o], u1 = ww_dead<NINE>(4 + j) ? WW_Z4 : acc[4 + j][i][o];
+                    const f32x4 u2 = ww_dead<NINE>(8 + j) ? WW_Z4 : acc[8 + j][i][o], u3 = -(ww_dead<NINE>(12 + j) ? WW_Z4 : acc[12 + j][i][o]);
                     const f32x4 s = j == 3 ? (f32x4){-1.f, -1.f, -1.f, -1.f} : (f32x4){1.f, 1.f, 1.f, 1.f};
                     R[0][j] = s * (u0_ + 0.5f * (u1 + u2));
                     R[1][j] = s * (0.5f * (u1 - u2));
@@ -478,7 +495,8 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_wino_f32(WgradArgs a) {
             f32x4 R[3][4];                                      // R[.][3]: the NEGATED column
             ww_rep<4>([&](auto Jc) {
                 constexpr int j = decltype(Jc)::value;
-                const f32x4 u0_ = acc[0 + j][i][o], u1 = acc[4 + j][i][o], u2 = acc[8 + j][i][o], u3n = acc[12 + j][i][o];
+                const f32x4 u0_ = ww_dead<NINE>(0 + j) ? WW_Z4 : acc[0 + j][i][o], u1 = ww_dead<NINE>(4 + j) ? WW_Z4 : acc[4 + j][i][o];
+                const f32x4 u2 = ww_dead<NINE>(8 + j) ? WW_Z4 : acc[8 + j][i][o], u3n = ww_dead<NINE>(12 + j) ? WW_Z4 : acc[12 + j][i][o];
                 const f32x4 h = 0.5f * (u1 + u2);
                 R[0][j] = u0_ + h;
                 R[1][j] = 0.5f * ww_sub4(u1, u2);
@@ -555,12 +573,12 @@ size_t aesr_wgrad_wino_lds_bytes(int TH, int TW) {
 // the tiles the kernel is built for: 8 k-steps ((TH / 2) * (TW / 8)), rows of whole 8-pixel DMA segments split evenly over 4 waves
 bool aesr_wgrad_wino_tile_ok(int TH, int TW) { return (TH == 16 && TW == 8) || (TH == 8 && TW == 16); }
 
-template <int TH, int TW, bool LEAN>
+template <int TH, int TW, bool LEAN, bool NINE = false>
 static int launch_wgrad_wino(const WgradArgs& a, hipStream_t st) {
     const size_t shmem = aesr_wgrad_wino_lds_bytes(TH, TW);
     static bool attr_set[AESR_MAX_DEVICES] = {}, attr_set_dbg[AESR_MAX_DEVICES] = {};
-    if (int e = aesr_lds_opt_in((const void*)conv_wgrad_wino_f32<TH, TW, false, LEAN>, "conv_wgrad_wino_f32", attr_set)) return e;
-    (void)aesr_lds_opt_in((const void*)conv_wgrad_wino_f32<TH, TW, true, LEAN>, "conv_wgrad_wino_f32", attr_set_dbg);        // the stamped form
+    if (int e = aesr_lds_opt_in((const void*)conv_wgrad_wino_f32<TH, TW, false, LEAN, NINE>, "conv_wgrad_wino_f32", attr_set)) return e;
+    (void)aesr_lds_opt_in((const void*)conv_wgrad_wino_f32<TH, TW, true, LEAN, NINE>, "conv_wgrad_wino_f32", attr_set_dbg);        // the stamped form
     dim3 grid(a.S * (a.CinP / 32) * (a.CoutP / 32));
     if (getenv("AESR_WGRAD_WINO_DBG") && grid.x * 4 <= (unsigned)WW_DBG_WAVES) {     // debug: per-phase stamps, printed after a host sync
         constexpr size_t dbytes = (size_t)WW_DBG_WAVES * (3 * sizeof(float) + WW_NTS * sizeof(unsigned long long));
@@ -568,7 +586,7 @@ static int launch_wgrad_wino(const WgradArgs& a, hipStream_t st) {
         if (!dbuf) (void)hipMalloc(&dbuf, dbytes);
         WgradArgs b = a;
         b.dbgbuf = dbuf;
-        hipLaunchKernelGGL((conv_wgrad_wino_f32<TH, TW, true, LEAN>), grid, dim3(256), shmem, st, b);
+        hipLaunchKernelGGL((conv_wgrad_wino_f32<TH, TW, true, LEAN, NINE>), grid, dim3(256), shmem, st, b);
         (void)hipStreamSynchronize(st);
         static float host[dbytes / sizeof(float)];
         (void)hipMemcpy(host, dbuf, dbytes, hipMemcpyDeviceToHost);
@@ -578,7 +596,7 @@ static int launch_wgrad_wino(const WgradArgs& a, hipStream_t st) {
         const double visits = (double)((a.ntiles + a.S - 1) / a.S);
         const int nks = (TH >> 1) * (TW >> 3);
         fprintf(stderr, "[wgrad-wino stamps] grid=%u tile %dx%d S=%d lean=%d (%.0f visits, %d k-steps = %d MFMA cycles per wave and visit) per visit, cycles: "
-                "k-step loop %.0f | barrier %.0f || fill %.0f\n", grid.x, TH, TW, a.S, (int)LEAN, visits, nks, nks / 4 * 64 * 32,
+                "k-step loop %.0f | barrier %.0f || fill %.0f\n", grid.x, TH, TW, a.S, (int)LEAN, visits, nks, nks / 4 * (NINE ? 36 : 64) * 32,
                 s3[0] / grid.x / 4 / visits, s3[1] / grid.x / 4 / visits, s3[2] / grid.x / 4);
         // the wave's life in wall-clock time (10 ns ticks): mean over the waves of every phase, entry skew behind the grid's first wave
         const unsigned long long* ts = (const unsigned long long*)(host + WW_DBG_WAVES * 3);
@@ -603,7 +621,7 @@ static int launch_wgrad_wino(const WgradArgs& a, hipStream_t st) {
                 ph[1] + ph[2] + ph[3] + ph[5] + ph[6] + ph[7] + ph[8] + ph[9]);
         return AESR_OK;
     }
-    hipLaunchKernelGGL((conv_wgrad_wino_f32<TH, TW, false, LEAN>), grid, dim3(256), shmem, st, a);
+    hipLaunchKernelGGL((conv_wgrad_wino_f32<TH, TW, false, LEAN, NINE>), grid, dim3(256), shmem, st, a);
     AESR_LAUNCH_CHECK("conv_wgrad_wino_f32");
     return AESR_OK;
 }
@@ -631,6 +649,12 @@ int aesr_launch_conv_wgrad_wino(const WgradArgs& a, hipStream_t st) {
     // loop, 4-byte slab stores); read once
     static const bool lean_env = [] { const char* e = getenv("AESR_WGRAD_WINO_LEAN"); return !(e && *e && atoi(e) == 0); }();
     const bool lean = lean_env && (size_t)a.CinP * a.CoutP * 40 < ((size_t)1 << 32);      // its 32-bit byte offsets inside one slab (10 planes)
-    if (a.TH == 16) return lean ? launch_wgrad_wino<16, 8, true>(a, st) : launch_wgrad_wino<16, 8, false>(a, st);
-    return lean ? launch_wgrad_wino<8, 16, true>(a, st) : launch_wgrad_wino<8, 16, false>(a, st);
+    // behind a folded Upsample(x2) (even sizes: checked above): the nine-position instantiations, unless AESR_WINO_UP2_NINE=0
+    // (named last: the compiler emits kernels in the order they are first named, and the listings of the 16-position ones stay what they were)
+    if (!(a.x_up2 && aesr_wino_up2_nine())) {
+        if (a.TH == 16) return lean ? launch_wgrad_wino<16, 8, true>(a, st) : launch_wgrad_wino<16, 8, false>(a, st);
+        return lean ? launch_wgrad_wino<8, 16, true>(a, st) : launch_wgrad_wino<8, 16, false>(a, st);
+    }
+    if (a.TH == 16) return lean ? launch_wgrad_wino<16, 8, true, true>(a, st) : launch_wgrad_wino<16, 8, false, true>(a, st);
+    return lean ? launch_wgrad_wino<8, 16, true, true>(a, st) : launch_wgrad_wino<8, 16, false, true>(a, st);
 }

@@ -68,6 +68,8 @@ __global__ __launch_bounds__(WN_NT, 2) void conv_wino_f32(WinoArgs a) {
     float* const ldsBias = ldsW0 + 2 * WN_WFL;           // [CoutP] (zeros when there is no bias)
     for (int c = tid; c < a.CoutP; c += WN_NT) ldsBias[c] = (a.bias && c < a.Cout) ? a.bias[c] : 0.f;
 
+    // (in_up2 / out_sum2 calls compute all 16 positions here; the 7 that an upsampled patch leaves at zero are skipped by the resident-filter
+    // kernel only -- conv_wino_res.hip, NINE -- which serves both upsample-folded layers of every benchmarked configuration)
     const int inH = a.in_up2 ? a.H >> 1 : a.H, inW = a.in_up2 ? a.W >> 1 : a.W;            // stored size of the input tensor
     const int outH = a.out_sum2 ? a.H >> 1 : a.H, outW = a.out_sum2 ? a.W >> 1 : a.W;      // stored size of the output tensor
     const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, (int)((size_t)a.N * inH * inW * a.Cin * 4), 0x00020000);

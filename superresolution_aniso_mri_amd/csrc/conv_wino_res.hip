@@ -38,14 +38,31 @@ constexpr int WR_NT = 512;          // threads per workgroup: 8 independent wave
 constexpr int WR_RP = 260;          // floats between patch rows: 16 pixel slots x 16 channels + 4 (shifts a row by one 16-byte bank group)
 constexpr int WR_PFL = 10 * WR_RP;  // floats of a wave's patch buffer (10 rows)
 
+// the k-th position that is computed: all 16, or (NINE) the nine 4 i + j with i, j in {0, 1, 3}
+template <bool NINE>
+__host__ __device__ constexpr int wr_xi(int k) { return NINE ? 4 * (k / 3 == 2 ? 3 : k / 3) + (k % 3 == 2 ? 3 : k % 3) : k; }
+
 // POST: eval-mode BatchNorm (a per-channel affine behind the activation) and the AvgPool2d(2) that follows it, in the epilogue -- a lane
 // holds one 2 x 2 output tile, which IS one pooling window; an instantiation of its own, so that the training kernels' code is untouched
 // STAMP (debug, AESR_WINO_RES_DBG=1): wall-clock stamps (s_memrealtime, 10 ns) of the phases of every wave's FIRST item -> a.dbgbuf as
 // [workgroup][wave][16] 64-bit ticks: 0 entry, 1 DMAs of the prologue issued, 2 behind the prologue barrier, 3 + 2 c patch of chunk c landed,
 // 4 + 2 c MFMAs of chunk c issued (c < 4), 11 stores of the item issued, 12 exit, 13 items of the wave
-template <int WR_TN, bool MASK, bool POST = false, bool STAMP = false>
+// NINE (the layers behind a nearest Upsample(x2): in_up2 forward, out_sum2 data gradient; AESR_WINO_UP2_NINE=0 selects the 16-position
+// instantiation): only the positions xi = 4 i + j with i, j in {0, 1, 3} are computed -- 9 U reads, 9 column transforms, 36 NB MFMAs per
+// chunk instead of 64 NB.
+//  * in_up2: a tile starts at an even pixel, so its patch rows (2k-1, 2k, 2k+1, 2k+2) are the stored rows (k-1, k, k, k+1): rows 1 and 2
+//    are the same numbers (at every border too: H and W are even), and so are columns 1 and 2.  Row 2 of B^T is d2 - d1: V[2][.] and
+//    V[.][2] are exactly +0, M = sum U V there is +0 (an accumulator that starts from +0 never becomes -0), and the output transform
+//    without those 7 terms gives every bit it gave with them (x + 0 == x unless x is -0, and no partial sum below can be: each has an
+//    operand that started from +0; x - 0 == x always).
+//  * out_sum2: the stored value is the SUM of the tile's 2 x 2 outputs, 1^T A^T M A 1 with 1^T A^T = [1, 2, 0, -1]: row 2 and column 2
+//    of M carry weight 0.  The 16-position form adds and subtracts them (they cancel in exact arithmetic only); without them dx moves
+//    by rounding, towards the exact value.
+template <int WR_TN, bool MASK, bool POST = false, bool STAMP = false, bool NINE = false>
 __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
+    static_assert(!NINE || (!MASK && !POST && !STAMP), "the nine-position form: plain forward / 2x2-summing data gradient only");
     constexpr int WR_NB = WR_TN / 16;
+    constexpr int NPOS = NINE ? 9 : 16;             // positions computed; the k-th of them is wr_xi<NINE>(k)
     constexpr int WR_WFL = 16 * 4 * WR_TN * 4;      // floats of one U chunk (16 positions x 16 ci x TN co)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -174,12 +191,13 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
         const float* wb = wbl + cc * WR_WFL;
         // PP positions per MFMA group: with ONE accumulator register set per position (16-cout workgroups) the four MFMAs of a position
         // form a dependent chain -- 40 cycles each instead of the 32 of independent ones -- so two positions are interleaved there
-        constexpr int PP = (WR_NB == 1) ? 2 : 1;
+        // (three of the nine: an odd count leaves no lone chain behind)
+        constexpr int PP = (WR_NB == 1) ? (NINE ? 3 : 2) : 1;
         f32x4 wnx[PP][WR_NB];
 #pragma unroll
         for (int pp = 0; pp < PP; ++pp)
 #pragma unroll
-            for (int nb = 0; nb < WR_NB; ++nb) wnx[pp][nb] = *(const f32x4*)(wb + pp * (4 * WR_TN * 4) + nb * 64);
+            for (int nb = 0; nb < WR_NB; ++nb) wnx[pp][nb] = *(const f32x4*)(wb + wr_xi<NINE>(pp) * (4 * WR_TN * 4) + nb * 64);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         // the patch is in registers: request the next one (next chunk, or chunk 0 of the next item) into the same buffer
         const int cur_n = in_n, cur_y0 = in_y0, cur_x0 = in_x0;
@@ -194,7 +212,7 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
         } else {
             fetch(item, cc + 1);
         }
-        // row half of the transform (B^T d)
+        // row half of the transform (B^T d); NINE: nothing reads t[2][.], and the compiler drops its subtractions
         WINO_ROW_HALF(t)
         // column half, one position ahead of the MFMAs that consume it: V[i][j] = (t[i] B)[j].  In the FIRST chunk of an item the
         // MFMA of each accumulator's first use takes 0 (the bias in position (1,1)) as its C operand: nothing is zeroed between items
@@ -202,9 +220,9 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
             constexpr bool FIRST = decltype(firstc)::value;
             f32x4 vnx[PP];
 #pragma unroll
-            for (int pp = 0; pp < PP; ++pp) vnx[pp] = WINO_V(t, pp >> 2, pp & 3);
+            for (int pp = 0; pp < PP; ++pp) vnx[pp] = WINO_V(t, wr_xi<NINE>(pp) >> 2, wr_xi<NINE>(pp) & 3);
 #pragma unroll
-            for (int grp = 0; grp < 16 / PP; ++grp) {
+            for (int grp = 0; grp < NPOS / PP; ++grp) {
                 f32x4 wc[PP][WR_NB], vc[PP];
 #pragma unroll
                 for (int pp = 0; pp < PP; ++pp) {
@@ -212,10 +230,10 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
 #pragma unroll
                     for (int nb = 0; nb < WR_NB; ++nb) wc[pp][nb] = wnx[pp][nb];
                 }
-                if (grp + 1 < 16 / PP) {
+                if (grp + 1 < NPOS / PP) {
 #pragma unroll
                     for (int pp = 0; pp < PP; ++pp) {
-                        const int xn = (grp + 1) * PP + pp;
+                        const int xn = wr_xi<NINE>((grp + 1) * PP + pp);
 #pragma unroll
                         for (int nb = 0; nb < WR_NB; ++nb) wnx[pp][nb] = *(const f32x4*)(wb + xn * (4 * WR_TN * 4) + nb * 64);
                         vnx[pp] = WINO_V(t, xn >> 2, xn & 3);
@@ -228,7 +246,7 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
                     for (int pp = 0; pp < PP; ++pp)
 #pragma unroll
                         for (int nb = 0; nb < WR_NB; ++nb) {
-                            const int xi = grp * PP + pp;
+                            const int xi = wr_xi<NINE>(grp * PP + pp);
                             f32x4 c = acc[xi][nb];
                             if (FIRST && r == 0) c = xi == 5 ? *(const f32x4*)(ldsBias + nb * 16 + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
                             acc[xi][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[pp][nb][r], vc[pp][r], c, 0, 0, 0);
@@ -250,7 +268,11 @@ __global__ __launch_bounds__(WR_NT, 2) void conv_wino_res_f32(WinoArgs a) {
         // ---- item finished: output transform Y = A^T M A, activation, (data gradient) derivative mask, store ----------
         {
             const int y0 = cur_y0 + 2 * ty, x0 = cur_x0 + 2 * tx;
-            WINO_STORE_TILE(WR_NB, MASK, POST, true, cur_n, y0, x0, co0, g, 0)
+            if constexpr (NINE) {
+                WINO_STORE_TILE9(WR_NB, true, cur_n, y0, x0, co0, g, 0)
+            } else {
+                WINO_STORE_TILE(WR_NB, MASK, POST, true, cur_n, y0, x0, co0, g, 0)
+            }
         }
         after_stores = !MASK && !halfout;           // exactly 4 NB stores follow the next patch's DMAs
         WR_STAMP(11)
@@ -366,11 +388,11 @@ static int wino_res_stamped(const WinoArgs& b_in, int grid, size_t shmem, hipStr
     return AESR_OK;
 }
 
-template <int WR_TN, bool MASK, bool POST = false>
+template <int WR_TN, bool MASK, bool POST = false, bool NINE = false>
 static int wino_res_launch_one(const WinoArgs& a, hipStream_t st) {
     const size_t shmem = wino_res_lds_bytes(a.CinP, WR_TN);
     static bool attr_set[AESR_MAX_DEVICES] = {};
-    if (int e = aesr_lds_opt_in((const void*)conv_wino_res_f32<WR_TN, MASK, POST>, "conv_wino_res_f32", attr_set)) return e;
+    if (int e = aesr_lds_opt_in((const void*)conv_wino_res_f32<WR_TN, MASK, POST, false, NINE>, "conv_wino_res_f32", attr_set)) return e;
     const int ncot = a.CoutP / WR_TN;
     int grid = 256 / ncot * ncot;                          // one workgroup per CU, a whole number of them per cout tile
     if (const char* e = getenv("AESR_WINO_GRID")) grid = atoi(e) / ncot * ncot;
@@ -386,12 +408,19 @@ static int wino_res_launch_one(const WinoArgs& a, hipStream_t st) {
     // (the XCD map hands every XCD a contiguous run of 8 x its workers blocks per round: with fewer blocks than waves it would fill the first
     // XCDs' workgroups with eight blocks each and leave the others idle)
     b.xcd_map = (xmap_on && grid % (8 * ncot) == 0 && a.nblk >= 8 * (grid / ncot)) ? 1 : 0;
-    if constexpr (!MASK && !POST) {
+    if constexpr (!MASK && !POST && !NINE) {
         if (getenv("AESR_WINO_RES_DBG")) return wino_res_stamped<WR_TN>(b, grid, shmem, st);
     }
-    hipLaunchKernelGGL((conv_wino_res_f32<WR_TN, MASK, POST>), dim3(grid), dim3(WR_NT), shmem, st, b);
+    hipLaunchKernelGGL((conv_wino_res_f32<WR_TN, MASK, POST, false, NINE>), dim3(grid), dim3(WR_NT), shmem, st, b);
     AESR_LAUNCH_CHECK("conv_wino_res_f32");
     return AESR_OK;
+}
+
+// AESR_WINO_UP2_NINE=0: the upsample-folded layers run the 16-position instantiations, forward, data gradient and weight gradient
+// (conv_wgrad_wino.hip) alike; read once
+bool aesr_wino_up2_nine() {
+    static const bool on = [] { const char* e = getenv("AESR_WINO_UP2_NINE"); return !(e && *e && atoi(e) == 0); }();
+    return on;
 }
 
 // called by aesr_launch_conv_wino (which has validated the arguments) when aesr_wino_res_ok(a)
@@ -421,6 +450,12 @@ int aesr_launch_conv_wino_res(const WinoArgs& a_in, hipStream_t st) {
         }
         return TN == 32 ? wino_res_launch_one<32, false, true>(a, st) : wino_res_launch_one<16, false, true>(a, st);
     }
-    if (TN == 32) return a.ysave ? wino_res_launch_one<32, true>(a, st) : wino_res_launch_one<32, false>(a, st);
-    return a.ysave ? wino_res_launch_one<16, true>(a, st) : wino_res_launch_one<16, false>(a, st);
+    // behind a folded Upsample(x2), either direction: the nine-position form (aesr_launch_conv_wino has checked that H and W are even;
+    // out_sum2 comes without mask, activation and bias).  Named last: the compiler emits kernels in the order they are first named, and
+    // the listings of the 16-position ones stay what they were.
+    if (!((a.in_up2 || a.out_sum2) && !a.ysave && aesr_wino_up2_nine())) {
+        if (TN == 32) return a.ysave ? wino_res_launch_one<32, true>(a, st) : wino_res_launch_one<32, false>(a, st);
+        return a.ysave ? wino_res_launch_one<16, true>(a, st) : wino_res_launch_one<16, false>(a, st);
+    }
+    return TN == 32 ? wino_res_launch_one<32, false, false, true>(a, st) : wino_res_launch_one<16, false, false, true>(a, st);
 }

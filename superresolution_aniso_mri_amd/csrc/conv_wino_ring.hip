@@ -78,6 +78,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino_ring_f32(WinoArgs a) {
     float* const ldsBias = lds + RG_SLOTS * RG_WFL + NW * a.patch_fl;   // [CoutP]
     __shared__ unsigned cnt[4];                                         // [3] arrival counters (static: the compiler must see LDS, not flat, accesses)
 
+    // (in_up2 / out_sum2 calls compute all 16 positions here; the 7 that an upsampled patch leaves at zero are skipped by the resident-filter
+    // kernel only -- conv_wino_res.hip, NINE -- which serves both upsample-folded layers of every benchmarked configuration)
     const int sh = a.in_up2 ? 1 : 0;
     const int inH = a.H >> sh, inW = a.W >> sh;                                              // stored size of the input tensor
     const bool halfout = a.out_sum2 || (POST && a.post_pool);

@@ -125,3 +125,52 @@ __device__ __forceinline__ float wino_slope(int act, float slope) { return act =
             }                                                                                                                                \
         }                                                                                                                                    \
     }
+
+// The same epilogue where only the positions 4 i + j with i, j in {0, 1, 3} exist (conv_wino_res.hip, NINE: the layers behind a folded
+// Upsample(x2); no mask, no POST).  A macro of its own, so that the expansion above stays what it is.
+//  * plain stores (in_up2 forward): the missing accumulators are exact +0 in the 16-position form, and this is WINO_STORE_TILE's
+//    expression tree with those terms left out: P[0][j] = acc[j] + acc[4 + j] (+ 0), P[1][j] = (acc[4 + j] - 0) - acc[12 + j],
+//    Y[0] = P[p][0] + P[p][1] (+ 0), Y[1] = (P[p][1] - 0) - P[p][3] -- the same bits.
+//  * out_sum2: s = 1^T A^T M A 1 with 1^T A^T = [1, 2, 0, -1]:  Q[j] = (acc[j] + 2 acc[4 + j]) - acc[12 + j] for j in {0, 1, 3},
+//    s = (Q[0] + 2 Q[1]) - Q[3].  Row 2 and column 2 of M have weight 0 (WINO_STORE_TILE adds and subtracts them): equal in exact
+//    arithmetic, rounded differently.
+#define WINO_STORE_TILE9(NB, okn, n, y0, x0, co0, g, so)                                                                                     \
+    {                                                                                                                                        \
+        int ob[2][2];                                                                                                                        \
+        _Pragma("unroll") for (int p = 0; p < 2; ++p)                                                                                        \
+            _Pragma("unroll") for (int q = 0; q < 2; ++q)                                                                                    \
+                ob[p][q] = ((okn) && (y0) + p < a.H && (x0) + q < a.W) ? (((n) * a.H + (y0) + p) * a.W + (x0) + q) * a.Cout * 4 : WINO_OOB; \
+        _Pragma("unroll") for (int nb = 0; nb < (NB); ++nb) {                                                                                \
+            const int co = (co0) + nb * 16 + 4 * (g);                                                                                        \
+            const int cob = co < a.Cout ? co * 4 : WINO_OOB;                                                                                 \
+            if (a.out_sum2) {                                                                                                                \
+                const f32x4 Q0 = aesr_sub4(acc[0][nb] + 2.f * acc[4][nb], acc[12][nb]);                                                      \
+                const f32x4 Q1 = aesr_sub4(acc[1][nb] + 2.f * acc[5][nb], acc[13][nb]);                                                      \
+                const f32x4 Q3 = aesr_sub4(acc[3][nb] + 2.f * acc[7][nb], acc[15][nb]);                                                      \
+                const f32x4 s = aesr_sub4(Q0 + 2.f * Q1, Q3);                                                                                \
+                const int obs = ((okn) && (y0) < a.H && (x0) < a.W) ? (((n) * outH + ((y0) >> 1)) * outW + ((x0) >> 1)) * a.Cout * 4 : WINO_OOB; \
+                wino_st(rs_out, obs + cob + (so), s);                                                                                        \
+                continue;                                                                                                                    \
+            }                                                                                                                                \
+            f32x4 P[2][4];                                                                                                                   \
+            _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                                                  \
+                if (j == 2) continue;                                                                                                        \
+                P[0][j] = acc[0 + j][nb] + acc[4 + j][nb];                                                                                   \
+                P[1][j] = aesr_sub4(acc[4 + j][nb], acc[12 + j][nb]);                                                                        \
+            }                                                                                                                                \
+            _Pragma("unroll") for (int p = 0; p < 2; ++p) {                                                                                  \
+                f32x4 Y[2];                                                                                                                  \
+                Y[0] = P[p][0] + P[p][1];                                                                                                    \
+                Y[1] = aesr_sub4(P[p][1], P[p][3]);                                                                                          \
+                _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                                              \
+                    f32x4 o = Y[q];                                                                                                          \
+                    const f32x4 os = o * nslope;                                                                                             \
+                    _Pragma("unroll") for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], os[e]);                                                 \
+                    if (sigm) {                                                                                                              \
+                        _Pragma("unroll") for (int e = 0; e < 4; ++e) o[e] = 1.f / (1.f + expf(-o[e]));                                      \
+                    }                                                                                                                        \
+                    wino_st(rs_out, ob[p][q] + cob + (so), o);                                                                               \
+                }                                                                                                                            \
+            }                                                                                                                                \
+        }                                                                                                                                    \
+    }
