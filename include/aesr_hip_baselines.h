@@ -48,6 +48,9 @@ extern "C" {
 #define AESR_ZX_ALIGN_GRID 1
 #define AESR_ZX_CLAMP 0
 #define AESR_ZX_MIRROR 1
+/* the limits of aesr_z_expand: factor and taps above these are AESR_ERR_UNSUPPORTED */
+#define AESR_ZX_MAX_FACTOR 16
+#define AESR_ZX_MAX_TAPS 10
 
 /* Output slices of an expansion by `factor`: Z * factor (AESR_ZX_ALIGN_ITK) or (Z - 1) * factor + 1 (AESR_ZX_ALIGN_GRID).  0 when Z < 1,
  * factor < 1, align is neither, or the count does not fit an int.  Host only. */

@@ -8,7 +8,7 @@ file plus --cuda-device-only -S, drops comment lines, .file / .ident / .loc and 
 per kernel: mangled name, sgpr / vgpr / spilled-vgpr counts of the metadata, instructions, "identical" or "DIFFERENT".  A source that
 only one tree has counts as one without kernels in the other.  Kernels are compared as a set and the rest of a listing as a bag of
 lines: another order of instantiation is reported as that.  Exit status 1 unless every file has the same kernels, each identical, and
-the same lines.
+the same lines.  A kernel that one file lost and another gained is also compared across the move ("moved from ... to ...").
 
 --sub-new REGEX REPL (repeatable) rewrites every line of the NEW tree's listings before the comparison: a kernel that gained a template
 parameter has another mangled name, and with its default value's suffix taken out again (e.g. 'ELb0EEv9WgradArgs' 'EEv9WgradArgs') the
@@ -60,8 +60,9 @@ def kernels(lines):
     res = {}
     for name in meta:           # label .. .Lfunc_end: the instructions and the kernel descriptor
         m = re.search(r"^" + re.escape(name) + r":.*?\n(.*?)^\.Lfunc_end\d+:", text, re.S | re.M)
-        # (.LBB<f>_<n>: f is the function's ordinal in its file -- an instantiation added in front renumbers the labels, not the code)
-        res[name] = (re.sub(r"\.LBB\d+_", ".LBB_", m.group(1)).split("\n"), meta[name])
+        # (.LBB<f>_<n>, and BB<f>_<n> in the loop comments: f is the function's ordinal in its file -- an instantiation added or taken away
+        # in front renumbers the labels, not the code)
+        res[name] = (re.sub(r"BB\d+_", "BB_", m.group(1)).split("\n"), meta[name])
     return res
 
 
@@ -76,7 +77,7 @@ def main():
     if not args.files:
         old_srcs, new_srcs = makefile(args.old)[0], makefile(args.new)[0]
         args.files = new_srcs + [f for f in old_srcs if f not in new_srcs]
-    rows, same = [], True
+    rows, same, gone, came = [], True, {}, {}          # gone, came: kernel -> (file, kernel) of those only one tree has in that file
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
         with concurrent.futures.ThreadPoolExecutor(8) as ex:          # the compiles run side by side
             jobs = [(ex.submit(listing, args.old, name, ta), ex.submit(listing, args.new, name, tb, args.sub_new)) for name in args.files]
@@ -92,6 +93,7 @@ def main():
                 same &= not ka and not kb
             for k in sorted(set(ka) | set(kb)):
                 if k not in ka or k not in kb:
+                    (gone if k in ka else came)[k] = (name, (ka if k in ka else kb)[k])
                     body, f = (ka if k in ka else kb)[k]
                     rows.append("  %s\n    sgpr %s vgpr %s vgpr_spill %s instructions %d  only in the %s tree" % (
                         k, f["sgpr_count"], f["vgpr_count"], f["vgpr_spill_count"],
@@ -103,6 +105,8 @@ def main():
                     ka[k][1]["sgpr_count"], ka[k][1]["vgpr_count"], ka[k][1]["vgpr_spill_count"])
                 rows.append("  %s\n    sgpr %s vgpr %s vgpr_spill %s instructions %d  %s" % (
                     k, f["sgpr_count"], f["vgpr_count"], f["vgpr_spill_count"], ninstr, verdict))
+    for k in sorted(set(gone) & set(came)):          # a kernel that changed files is compared with itself across the move
+        rows.append("moved from %s to %s: %s\n    %s" % (gone[k][0], came[k][0], k, "identical" if gone[k][1] == came[k][1] else "DIFFERENT"))
     report = ("device listings (hipcc <the Makefile's CXXFLAGS of each file> --cuda-device-only -S), normalised, old tree against new\n"
               + "".join("new tree's lines rewritten: s/%s/%s/\n" % tuple(sr) for sr in args.sub_new) + "\n".join(rows)
               + "\n%s\n" % ("every kernel identical" if same else "NOT the same"))

@@ -233,24 +233,17 @@ SIGNATURES_COMPONENTS = {
     "aesr_components_overlap_runs": (c_int, [P] * 5 + [ctypes.c_longlong, P, c_size_t] + [c_int] * 4 + [IP, c_int, c_int, P]),
     "aesr_components_apply_table": (c_int, [P, P, P, IP, P, P, c_size_t, P] + [c_int] * 4 + [IP, c_int, c_int, P]),
 }
-# Shape-based label interpolation (csrc/shape_interp.hip).  NOT in HEADERS, and on purpose not named SIGNATURES*: libaesr_hip.so exports
-# these three symbols, but they are declared in csrc/shape_interp.h, not under include/ -- the public ABI is pinned header by header
-# (tests/test_abi.py, tests/golden/abi_symbols.json, with the GPU test module that guards each header), and they join it in a change whose
-# subject is the ABI.  _load() binds this table beside the public ones; tests/test_shape_interp_golden.py checks it against the prototypes.
-SHAPE_INTERP_ENTRIES = {
+# shape-based label interpolation
+SIGNATURES_SHAPE = {
     "aesr_shape_workspace_bytes": (c_size_t, [c_int] * 5),
     "aesr_shape_signed_distances": (c_int, [P, P, P, c_size_t] + [c_int] * 4 + [IP, c_int, c_double, c_double, P]),
     "aesr_shape_interpolate": (c_int, [P, P, P, P] + [c_int] * 6 + [IP, P]),
 }
-SHAPE_MAX_CLASSES, SHAPE_MAX_W = 8, 4096          # AESR_SHAPE_* of csrc/shape_interp.h
-# Reslicing with a cubic B-spline or a windowed sinc (csrc/reslice_taps.hip).  As above: exported and bound by _load(), declared in
-# csrc/reslice_taps.h and not under include/, so not in HEADERS and not named SIGNATURES*; tests/test_reslice_taps_golden.py checks the table
-# against the prototypes.
-RESLICE_TAPS_ENTRIES = {
+# reslicing with a cubic B-spline or a windowed sinc
+SIGNATURES_RESLICE_TAPS = {
     "aesr_bspline_prefilter_3d": (c_int, [P, P] + [c_int] * 4 + [P]),
     "aesr_reslice_taps_affine": (c_int, [P, P, P] + [c_int] * 7 + [DP, c_int, c_int, c_int, P]),
 }
-TAPS_BSPLINE3, TAPS_LANCZOS, TAPS_COSINE, TAPS_MIN_RADIUS, TAPS_MAX_RADIUS = 0, 1, 2, 3, 5          # AESR_TAPS_* of csrc/reslice_taps.h
 # The C ABI, header by header in the order the headers were added: each table must list every symbol its header under include/ declares,
 # with the types of the prototype, and no symbol may stand in two (tests/test_abi.py checks all of it against the headers and the library).
 # _load() binds exactly these tables; include/ is not read at run time.
@@ -266,13 +259,17 @@ HEADERS = {
     "aesr_hip_bnpool.h": SIGNATURES_BNPOOL,
     "aesr_hip_labelprep.h": SIGNATURES_LABELPREP,
     "aesr_hip_components.h": SIGNATURES_COMPONENTS,
+    "aesr_hip_shape.h": SIGNATURES_SHAPE,
+    "aesr_hip_reslice_taps.h": SIGNATURES_RESLICE_TAPS,
 }
+SHAPE_MAX_CLASSES, SHAPE_MAX_W = 8, 4096          # AESR_SHAPE_* of include/aesr_hip_shape.h
+TAPS_BSPLINE3, TAPS_LANCZOS, TAPS_COSINE, TAPS_MIN_RADIUS, TAPS_MAX_RADIUS = 0, 1, 2, 3, 5          # AESR_TAPS_* of include/aesr_hip_reslice_taps.h
 COMPONENTS_MAX_CLASSES, COMPONENTS_COLUMNS, COMPONENTS_MAX_PER_CLASS = 8, 8, 1 << 24          # AESR_COMPONENTS_* of include/aesr_hip_components.h
 SURFACE_MAX_CLASSES, SURFACE_COUNTS, SURFACE_MAX_W = 8, 7, 4096          # AESR_SURFACE_* of include/aesr_hip_surface.h
 SEG_MIN_CLASSES, SEG_MAX_CLASSES = 2, 8
 RESLICE_NEAREST, RESLICE_LINEAR = 0, 1          # AESR_RESLICE_* (RS_* below are the modes of aesr_resample2_*)
 ZX_ALIGN_ITK, ZX_ALIGN_GRID, ZX_CLAMP, ZX_MIRROR = 0, 1, 0, 1
-ZX_MAX_FACTOR, ZX_MAX_TAPS = 16, 10          # ZX_MAXF, ZX_MAXT of csrc/z_expand.hip
+ZX_MAX_FACTOR, ZX_MAX_TAPS = 16, 10          # AESR_ZX_MAX_* of include/aesr_hip_baselines.h
 P2P_HANDLE_BYTES, P2P_SLOTS = 64, 32
 COMM_ID_BYTES = 128
 COMM_F32, COMM_F64, COMM_SUM, COMM_MAX = 0, 1, 0, 1
@@ -293,7 +290,7 @@ def _load():
             "libaesr_hip.so not found at %s -- build it with `python __graft_entry__.py` (or `make -C "
             "superresolution_aniso_mri_amd/csrc`). The HIP extension is mandatory: there is no CPU/eager fallback." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for table in list(HEADERS.values()) + [SHAPE_INTERP_ENTRIES, RESLICE_TAPS_ENTRIES]:
+    for table in HEADERS.values():
         for name, (res, args) in table.items():
             fn = getattr(lib, name, None)
             if fn is None:

@@ -19,12 +19,9 @@
 #include "../../include/aesr_hip_reslice.h"
 #include "aesr_kernels.h"
 #include "aesr_hostcheck.h"
-#include "reslice_position.h"
+#include "reslice_common.h"
 
 #pragma clang fp contract(off)
-
-#define RSL_THREADS 256
-#define RSL_LX 64          // lanes along the output x: one wave is one row segment of a tile
 
 // one axis of the trilinear rule: position c on an axis of n samples -> clamped indices of the two neighbours, their weights and validity
 __device__ __forceinline__ void rsl_axis_linear(double c, int n, int idx[2], double w[2], bool ok[2]) {
@@ -47,18 +44,15 @@ __device__ __forceinline__ int rsl_axis_nearest(double c, int n, bool& ok) {
     return ok ? (int)r : 0;
 }
 
-// A tile is RSL_LX lanes x 4 rows; grid.x: tiles_x * tiles_y * Zo tiles, x fastest.
 // LINEAR: 1 = trilinear, 0 = nearest.  GRID: positions from `grid` ([Zo][Ho][Wo][3] normalised), else from the affine A.
 template <int LINEAR, bool GRID>
 __global__ __launch_bounds__(RSL_THREADS) void reslice_kernel(const float* __restrict__ src, const float* __restrict__ grid, float* __restrict__ out,
                                                               RslAffine A, int N, int Zs, int Hs, int Ws, int Zo, int Ho, int Wo,
                                                               unsigned int tiles_x, unsigned int tiles_y) {
-    constexpr int LX = RSL_LX, K = LINEAR ? 8 : 1;
-    const unsigned int tx = blockIdx.x % tiles_x, rest = blockIdx.x / tiles_x;
-    const unsigned int ty = rest % tiles_y, zo = rest / tiles_y;          // zo < Zo: the launcher sized the grid for it
-    const int xo = (int)(tx * LX + (threadIdx.x & (LX - 1)));
-    const int yo = (int)(ty * (RSL_THREADS / LX) + threadIdx.x / LX);
-    if (xo >= Wo || yo >= Ho) return;
+    constexpr int K = LINEAR ? 8 : 1;
+    int xo, yo;
+    unsigned int zo;
+    if (!rsl_tile_voxel(tiles_x, tiles_y, Ho, Wo, xo, yo, zo)) return;
     const size_t row = ((size_t)zo * Ho + yo) * Wo;
     int off[K];
     double w[K];
@@ -123,12 +117,9 @@ static int rsl_check(const char* fn, const float* src, const float* out, int N, 
     AESR_CHECK_ARG(out, "%s: out is a null pointer", fn);
     AESR_CHECK_ARG((uintptr_t)src % 4 == 0, "%s: src is not 4-byte aligned", fn);
     AESR_CHECK_ARG((uintptr_t)out % 4 == 0, "%s: out is not 4-byte aligned", fn);
-    AESR_CHECK_ARG(N > 0, "%s: N=%d must be positive", fn, N);
-    AESR_CHECK_ARG(Zs > 0 && Hs > 0 && Ws > 0, "%s: Zs, Hs, Ws = %d, %d, %d must all be positive", fn, Zs, Hs, Ws);
-    AESR_CHECK_ARG(Zo > 0 && Ho > 0 && Wo > 0, "%s: Zo, Ho, Wo = %d, %d, %d must all be positive", fn, Zo, Ho, Wo);
+    if (const int rc = rsl_check_sizes(fn, N, Zs, Hs, Ws, Zo, Ho, Wo)) return rc;
     AESR_CHECK_ARG(interp == AESR_RESLICE_NEAREST || interp == AESR_RESLICE_LINEAR, "%s: interp=%d is neither 0 (nearest) nor 1 (linear)", fn, interp);
-    AESR_CHECK_ARG((double)N * Zs * Hs * Ws < 2147483648.0, "%s: N * Zs * Hs * Ws = %d x %d x %d x %d has 2^31 elements or more", fn, N, Zs, Hs, Ws);
-    AESR_CHECK_ARG((double)N * Zo * Ho * Wo < 2147483648.0, "%s: N * Zo * Ho * Wo = %d x %d x %d x %d has 2^31 elements or more", fn, N, Zo, Ho, Wo);
+    if (const int rc = rsl_check_counts(fn, N, Zs, Hs, Ws, Zo, Ho, Wo)) return rc;
     if (aesr_overlap(out, (size_t)4 * N * Zo * Ho * Wo, src, (size_t)4 * N * Zs * Hs * Ws)) {
         aesr_set_error("%s: out overlaps src", fn);
         return AESR_ERR_UNSUPPORTED;

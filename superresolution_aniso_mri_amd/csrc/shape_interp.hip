@@ -1,6 +1,6 @@
 // Shape-based interpolation of label maps on the device (Raya & Udupa 1990, Herman et al. 1992): signed Euclidean distance maps of every
 // class in every slice, then per output slice a linear blend of the maps of the two neighbouring input slices and an arg-max over the
-// classes.  csrc/shape_interp.h states the definitions; the three entry points are exported but not yet public ABI (see there).
+// classes.  include/aesr_hip_shape.h states the definitions.
 //
 //   signed distances (aesr_shape_signed_distances), the structure of seg_metrics.hip's distance transform, 2-D per slice:
 //     x pass   one wave per line (n, class, z, y): the line's pixels of the class as 64-bit ballot masks in LDS, and the complement of the
@@ -16,7 +16,7 @@
 // alone, and every loop is bounded by a size argument.
 #include "aesr_kernels.h"
 #include "aesr_hostcheck.h"
-#include "shape_interp.h"
+#include "../../include/aesr_hip_shape.h"
 
 #include <cmath>
 

@@ -1,6 +1,6 @@
 // Conventional through-plane interpolation of a [N][Z][H][W] volume by an integer factor (the reference's evaluate/common.py:74-118
-// create_simple_interpolation, SimpleITK's ExpandImageFilter with a linear, cubic B-spline or Lanczos-windowed-sinc interpolator) and the
-// recursive cubic B-spline pre-filter along z.  include/aesr_hip_baselines.h.
+// create_simple_interpolation, SimpleITK's ExpandImageFilter with a linear, cubic B-spline or Lanczos-windowed-sinc interpolator).
+// include/aesr_hip_baselines.h; the B-spline's pre-filter is bspline_prefilter.hip.
 //   - in-plane coordinates are integers, so every method is a 1-D filter along z of every (y, x) column whose taps depend on the output
 //     PHASE p = o % factor only: out[q * factor + p] = sum_k w[p][k] * src[bound(q + base[p] + k)].  The host makes base and w in float64
 //     (evaluate/z_interp.py: the rule of inplane.hip) and they travel by value in the kernel ARGUMENTS; the kernel only looks up;
@@ -12,19 +12,15 @@
 //     workgroup (plus the z halo of the neighbouring run), not once per tap and phase, and every output slice is written once;
 //   - each output is sum_k in ascending k, accumulated in double without contraction, rounded to fp32 once, then clamped to [0, 1] if asked.
 //     An output slice index is the same in every lane of a wave, so the weights are read with scalar loads.
-// The pre-filter: one thread per (frame, y, x) column runs scipy.ndimage.spline_filter1d(order = 3, mode = 'mirror') along z in double --
-// gain 6, exact mirror initialisation over the whole line with the powers of the pole as running products, causal and anti-causal
-// recursion.  Lanes are neighbouring columns: every load and store of a wave is one contiguous row segment.
-// No workspace beyond the caller's `coef`, no copy, no synchronisation, no atomics, no scratch.
+// No workspace, no copy, no synchronisation, no atomics, no scratch.
 #include <math.h>
 
 #include "../../include/aesr_hip_baselines.h"
 #include "aesr_kernels.h"
+#include "bspline_prefilter.h"
 
 #pragma clang fp contract(off)
 
-#define ZX_MAXF 16
-#define ZX_MAXT 10
 #define ZX_THREADS 256
 #define ZX_LDS_BYTES (48 * 1024)
 #define ZX_MIN_QB 4               // source positions per run at least (while the window allows): the halo re-read stays bounded
@@ -32,8 +28,8 @@
 #define ZX_MAX_BASE 4096          // |base_host[p]|: far beyond any interpolator, small enough that q + base + k cannot overflow
 
 struct ZxTables {
-    double w[ZX_MAXF * ZX_MAXT];          // w[p * taps + k]
-    int base[ZX_MAXF];
+    double w[AESR_ZX_MAX_FACTOR * AESR_ZX_MAX_TAPS];          // w[p * taps + k]
+    int base[AESR_ZX_MAX_FACTOR];
 };
 
 // V consecutive pixels of a slice of S: the unit a lane loads, stages and (as float) stores
@@ -41,12 +37,7 @@ template <typename S, int V>
 struct alignas(V == 4 ? 16 : sizeof(S)) ZxPack { S v[V]; };
 
 __device__ __forceinline__ int zx_bound(int i, int n, int boundary) {
-    if (boundary == 0) return i < 0 ? 0 : (i >= n ? n - 1 : i);
-    if (n == 1) return 0;
-    const int p = 2 * n - 2;          // whole-sample mirror: c b | a b c d | c b
-    int m = i % p;
-    if (m < 0) m += p;
-    return m < n ? m : p - m;
+    return boundary == 0 ? (i < 0 ? 0 : (i >= n ? n - 1 : i)) : aesr_mirror_index(i, n);
 }
 
 // S: float (samples) or double (coefficients); V = 4 with SU = 64 units per staged slice, or V = 1 with SU = 256.  units: units per slice
@@ -98,42 +89,6 @@ __global__ __launch_bounds__(ZX_THREADS) void z_expand_kernel(const ZxPack<S, V>
     }
 }
 
-// one thread per column; cols = N * HW columns, column c of frame n starts at n * Z * HW + c and has stride HW
-__global__ __launch_bounds__(ZX_THREADS) void bspline_prefilter_kernel(const float* __restrict__ in, double* __restrict__ coef, unsigned int cols,
-                                                                       unsigned int HW, int Z) {
-    const unsigned int col = blockIdx.x * ZX_THREADS + threadIdx.x;
-    if (col >= cols) return;
-    const size_t off = (size_t)(col / HW) * Z * HW + col % HW;
-    const float* __restrict__ x = in + off;
-    double* __restrict__ c = coef + off;
-    if (Z == 1) {
-        c[0] = (double)x[0];
-        return;
-    }
-    const double z1 = sqrt(3.0) - 2.0, gain = 6.0;
-    double zn1 = 1.0;
-    for (int i = 0; i < Z - 1; ++i) zn1 *= z1;          // z1^(Z-1) as a running product
-    double c0 = (double)x[0] * gain + zn1 * ((double)x[(size_t)(Z - 1) * HW] * gain), zi = z1;
-    for (int i = 1; i < Z - 1; ++i) {
-        c0 += zi * ((double)x[(size_t)i * HW] * gain + zn1 * ((double)x[(size_t)(Z - 1 - i) * HW] * gain));
-        zi *= z1;
-    }
-    c0 /= 1.0 - zn1 * zn1;
-    c[0] = c0;
-    double prev = c0;
-    for (int i = 1; i < Z; ++i) {          // causal
-        prev = (double)x[(size_t)i * HW] * gain + z1 * prev;
-        c[(size_t)i * HW] = prev;
-    }
-    // anti-causal: prev is c[Z-1] of the causal pass, c[Z-2] comes back from memory (this thread's own store)
-    double next = z1 / (z1 * z1 - 1.0) * (z1 * c[(size_t)(Z - 2) * HW] + prev);
-    c[(size_t)(Z - 1) * HW] = next;
-    for (int i = Z - 2; i >= 0; --i) {
-        next = z1 * (next - c[(size_t)i * HW]);
-        c[(size_t)i * HW] = next;
-    }
-}
-
 extern "C" {
 
 int aesr_z_expand_out_slices(int Z, int factor, int align) {
@@ -150,21 +105,6 @@ size_t aesr_bspline_coef_bytes(int N, int Z, int H, int W) {
     return N > 0 && Z > 0 && H > 0 && W > 0 ? (size_t)8 * N * Z * H * W : 0;
 }
 
-int aesr_bspline_prefilter_z(const float* in, double* coef, int N, int Z, int H, int W, void* stream) {
-    AESR_CHECK_ARG(in, "aesr_bspline_prefilter_z: in is a null pointer");
-    AESR_CHECK_ARG(coef, "aesr_bspline_prefilter_z: coef is a null pointer");
-    AESR_CHECK_ARG((uintptr_t)in % 4 == 0, "aesr_bspline_prefilter_z: in is not 4-byte aligned");
-    AESR_CHECK_ARG((uintptr_t)coef % 8 == 0, "aesr_bspline_prefilter_z: coef is not 8-byte aligned");
-    AESR_CHECK_ARG(N > 0 && Z > 0 && H > 0 && W > 0, "aesr_bspline_prefilter_z: N, Z, H, W = %d, %d, %d, %d must all be positive", N, Z, H, W);
-    AESR_CHECK_ARG((size_t)N * Z * H * W < ((size_t)1 << 31), "aesr_bspline_prefilter_z: N * Z * H * W = %d x %d x %d x %d has 2^31 elements or more",
-                   N, Z, H, W);
-    const unsigned int HW = (unsigned int)H * W, cols = HW * N;
-    hipLaunchKernelGGL(bspline_prefilter_kernel, dim3((cols + ZX_THREADS - 1) / ZX_THREADS), dim3(ZX_THREADS), 0, (hipStream_t)stream, in, coef, cols,
-                       HW, Z);
-    AESR_LAUNCH_CHECK("bspline_prefilter_z");
-    return AESR_OK;
-}
-
 int aesr_z_expand(const float* in, const double* coef, float* out, int N, int Z, int H, int W, int factor, int Zo, int taps, const int* base_host,
                   const double* weights_host, int boundary, int clamp01, void* stream) {
     AESR_CHECK_ARG((in != nullptr) != (coef != nullptr), "aesr_z_expand: exactly one of in and coef must be given (%s are)", in ? "both" : "neither");
@@ -178,12 +118,12 @@ int aesr_z_expand(const float* in, const double* coef, float* out, int N, int Z,
     AESR_CHECK_ARG(Z <= (1 << 30), "aesr_z_expand: Z=%d exceeds 2^30", Z);
     AESR_CHECK_ARG(factor >= 1, "aesr_z_expand: factor=%d must be at least 1", factor);
     AESR_CHECK_ARG(taps >= 1, "aesr_z_expand: taps=%d must be at least 1", taps);
-    if (factor > ZX_MAXF) {
-        aesr_set_error("aesr_z_expand: factor=%d exceeds the supported %d", factor, ZX_MAXF);
+    if (factor > AESR_ZX_MAX_FACTOR) {
+        aesr_set_error("aesr_z_expand: factor=%d exceeds the supported %d", factor, AESR_ZX_MAX_FACTOR);
         return AESR_ERR_UNSUPPORTED;
     }
-    if (taps > ZX_MAXT) {
-        aesr_set_error("aesr_z_expand: taps=%d exceeds the supported %d (Lanczos radius above 5)", taps, ZX_MAXT);
+    if (taps > AESR_ZX_MAX_TAPS) {
+        aesr_set_error("aesr_z_expand: taps=%d exceeds the supported %d (Lanczos radius above 5)", taps, AESR_ZX_MAX_TAPS);
         return AESR_ERR_UNSUPPORTED;
     }
     AESR_CHECK_ARG(boundary == AESR_ZX_CLAMP || boundary == AESR_ZX_MIRROR, "aesr_z_expand: boundary=%d is neither 0 (clamp) nor 1 (mirror)", boundary);
@@ -193,8 +133,8 @@ int aesr_z_expand(const float* in, const double* coef, float* out, int N, int Z,
                    aesr_z_expand_out_slices(Z, factor, AESR_ZX_ALIGN_ITK), aesr_z_expand_out_slices(Z, factor, AESR_ZX_ALIGN_GRID));
     AESR_CHECK_ARG((size_t)N * Zo * H * W < ((size_t)1 << 31), "aesr_z_expand: N * Zo * H * W = %d x %d x %d x %d has 2^31 elements or more", N, Zo, H, W);
     ZxTables tb;
-    for (int i = 0; i < ZX_MAXF * ZX_MAXT; ++i) tb.w[i] = 0.0;
-    for (int p = 0; p < ZX_MAXF; ++p) tb.base[p] = 0;
+    for (int i = 0; i < AESR_ZX_MAX_FACTOR * AESR_ZX_MAX_TAPS; ++i) tb.w[i] = 0.0;
+    for (int p = 0; p < AESR_ZX_MAX_FACTOR; ++p) tb.base[p] = 0;
     int lo = base_host[0], hi = base_host[0];
     for (int p = 0; p < factor; ++p) {
         AESR_CHECK_ARG(base_host[p] >= -ZX_MAX_BASE && base_host[p] <= ZX_MAX_BASE, "aesr_z_expand: base_host[%d]=%d is outside [-%d, %d]", p,

@@ -9,7 +9,7 @@ float64 on the host; the kernel receives the 3x4 matrix that takes an OUTPUT vox
 Interpolation is trilinear with zero padding (a corner outside the source contributes nothing) or nearest (halves to even), exactly
 ``torch.nn.functional.grid_sample(..., padding_mode='zeros', align_corners=True)`` on a 5-D input.
 
-The affine path also takes three higher-order interpolators (csrc/reslice_taps.hip, csrc/reslice_taps.h): ``bspline``, the cubic B-spline
+The affine path also takes three higher-order interpolators (csrc/reslice_taps.hip, include/aesr_hip_reslice_taps.h): ``bspline``, the cubic B-spline
 over a separable 3-D pre-filter (``scipy.ndimage.map_coordinates(order=3, mode='mirror')``), and the windowed sincs ``lanczos`` and
 ``cosine`` of radius 3, 4 or 5 (ITK's WindowedSincInterpolateImageFunction; ``cosine`` is what the reference's
 kwatsch/create_nifti_from_dicom.py reslices with).  They follow ITK's buffer rule: a voxel is computed only where

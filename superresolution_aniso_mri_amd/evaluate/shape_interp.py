@@ -3,7 +3,7 @@ for a denser segmentation, and what a model that super-resolves label maps has t
 
 Per class and slice the signed Euclidean distance to the class boundary (positive inside, in mm of the in-plane spacing); the maps of the
 two neighbouring slices are blended linearly at the output slice's position and the class with the largest blended value wins, ties going
-to the smallest class value.  csrc/shape_interp.hip computes both steps, csrc/shape_interp.h states the definitions, and
+to the smallest class value.  csrc/shape_interp.hip computes both steps, include/aesr_hip_shape.h states the definitions, and
 ``evaluate.z_grid`` says where the output slices sit -- the integer grid of ``num_interpolations`` and the grid of a target slice spacing
 are one code path.  A class that a slice does not hold has the distance ``-BIG`` everywhere in it (``BIG`` = the slice's diagonal, DESIGN.md
 section 6b): such a class ends at the slice that has it, it does not taper.
@@ -113,7 +113,7 @@ def resolve_grid(Z, num_interpolations=None, grid=None):
 
 
 def store_path(out, HW):
-    """Which stores ``aesr_shape_interpolate`` takes for this output, by the rule of csrc/shape_interp.h: "word4" (4 labels per lane, one
+    """Which stores ``aesr_shape_interpolate`` takes for this output, by the rule of include/aesr_hip_shape.h: "word4" (4 labels per lane, one
     32-bit store) when H * W is a multiple of 4 and ``out`` is 4-byte aligned, else "byte1".  The values do not depend on it."""
     return "word4" if int(HW) % 4 == 0 and out.data_ptr() % 4 == 0 else "byte1"
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Generate tests/golden/reslice_taps.npz for the higher-order affine reslice (csrc/reslice_taps.h).  A script, not a test (pytest does not
+"""Generate tests/golden/reslice_taps.npz for the higher-order affine reslice (include/aesr_hip_reslice_taps.h).  A script, not a test (pytest does not
 collect it); scipy and numpy only.  Only data is written, per case:
 
   vol       uint16 counts of 1/1024 in [0, 1] (exact in fp32), [N, Z, Y, X]

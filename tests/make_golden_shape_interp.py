@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Writes tests/golden/shape_interp.npz: small label volumes and what shape-based interpolation (csrc/shape_interp.h) makes of them when the
+"""Writes tests/golden/shape_interp.npz: small label volumes and what shape-based interpolation (include/aesr_hip_shape.h) makes of them when the
 signed distance maps come from scipy.  scipy and numpy only; run from the repository root:  python tests/make_golden_shape_interp.py
 
 Per case: the label volume (uint8 [N, Z, H, W]), classes, spacing (sy, sx), the grid (gap, alpha), scipy's signed maps --

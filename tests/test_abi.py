@@ -38,6 +38,10 @@ def test_no_name_is_declared_or_listed_twice():
     assert au.headers() == sorted(_hip.HEADERS), "include/*.h and _hip.HEADERS differ"
     tables = _tables()
     assert sorted(map(id, tables.values())) == sorted(map(id, _hip.HEADERS.values())), "a SIGNATURES* table of _hip is not in HEADERS, or is in it twice"
+    # whatever it is called: a module-level dict of (restype, [argtypes]) pairs is a table of entry points, and HEADERS has every one
+    for k, v in vars(_hip).items():
+        if isinstance(v, dict) and v and all(isinstance(e, tuple) and len(e) == 2 and isinstance(e[1], list) for e in v.values()):
+            assert any(v is t for t in _hip.HEADERS.values()), "_hip.%s is a table of entry points that is not in HEADERS" % k
     for what, sets in (("declared in", {h: au.declared(h) for h in au.headers()}), ("listed in", {k: set(t) for k, t in tables.items()})):
         seen = {}
         for where, names in sets.items():
@@ -82,15 +86,18 @@ def test_structures_are_the_headers():
 
 # ---- constants -----------------------------------------------------------------------------------------------------------------------
 # (_hip name, header, #define).  Not here, because they mirror a definition of csrc/ that no public header states: ACT_* (the enum of
-# csrc/aesr_common.h), REDUCE_MAX_JOBS (csrc/aesr_kernels.h), ZX_MAX_FACTOR / ZX_MAX_TAPS (ZX_MAXF / ZX_MAXT of csrc/z_expand.hip) and
-# SEG_MIN_CLASSES / SEG_MAX_CLASSES (the limits written out in csrc/seg_head.hip).
+# csrc/aesr_common.h), REDUCE_MAX_JOBS (csrc/aesr_kernels.h) and SEG_MIN_CLASSES / SEG_MAX_CLASSES (the limits written out in
+# csrc/seg_head.hip).
 MIRRORED = ([(n, "aesr_hip.h", "AESR_" + n) for n in (
     "PREP_PACK", "PREP_WINO_PACK", "PREP_STEM_FOLD", "PREP_COUT1_FLIP", "RS_POOL", "RS_NEAREST", "RS_BILINEAR", "BN_NONE", "BN_POOL", "BN_UP",
     "BN_NWG", "LPIPS_NCH", "MSE_NPART", "MSE3_WS", "P2P_HANDLE_BYTES", "P2P_SLOTS", "COMM_ID_BYTES", "COMM_F32", "COMM_F64", "COMM_SUM", "COMM_MAX")]
-            + [(n, "aesr_hip_baselines.h", "AESR_" + n) for n in ("ZX_ALIGN_ITK", "ZX_ALIGN_GRID", "ZX_CLAMP", "ZX_MIRROR")]
+            + [(n, "aesr_hip_baselines.h", "AESR_" + n) for n in ("ZX_ALIGN_ITK", "ZX_ALIGN_GRID", "ZX_CLAMP", "ZX_MIRROR", "ZX_MAX_FACTOR",
+                                                                     "ZX_MAX_TAPS")]
             + [(n, "aesr_hip_reslice.h", "AESR_" + n) for n in ("RESLICE_NEAREST", "RESLICE_LINEAR")]
             + [(n, "aesr_hip_surface.h", "AESR_" + n) for n in ("SURFACE_MAX_CLASSES", "SURFACE_COUNTS", "SURFACE_MAX_W")]
-            + [(n, "aesr_hip_components.h", "AESR_" + n) for n in ("COMPONENTS_MAX_CLASSES", "COMPONENTS_COLUMNS", "COMPONENTS_MAX_PER_CLASS")])
+            + [(n, "aesr_hip_components.h", "AESR_" + n) for n in ("COMPONENTS_MAX_CLASSES", "COMPONENTS_COLUMNS", "COMPONENTS_MAX_PER_CLASS")]
+            + [(n, "aesr_hip_shape.h", "AESR_" + n) for n in ("SHAPE_MAX_CLASSES", "SHAPE_MAX_W")]
+            + [(n, "aesr_hip_reslice_taps.h", "AESR_" + n) for n in ("TAPS_BSPLINE3", "TAPS_LANCZOS", "TAPS_COSINE", "TAPS_MIN_RADIUS", "TAPS_MAX_RADIUS")])
 # integer #defines of the headers that _hip has no use for
 NOT_MIRRORED = {"AESR_ABI_VERSION", "AESR_ERR_ARG", "AESR_ERR_HIP", "AESR_ERR_UNSUPPORTED", "AESR_MSE3_NPART", "AESR_P2P_REC_BYTES"}
 
@@ -128,6 +135,9 @@ GUARDS = {
                           ("test_guard_bands_poisons_and_offset_pointers", "test_refusals_write_nothing"), (("GUARD_CASES", "CASES"),)),
     "aesr_hip_labelprep.h": ("test_gpu_labelled", set(), ("test_guard_bands_poisons_and_offset_pointers", "test_refusals_write_nothing"), ()),
     "aesr_hip_components.h": ("test_gpu_components", {"aesr_components_workspace_bytes"}, ("test_guard_bands_poisons_and_shifted_pointers",), ()),
+    "aesr_hip_shape.h": ("test_gpu_shape_interp", {"aesr_shape_workspace_bytes"}, ("test_guard_bands_poisons_and_shifted_pointers",), ()),
+    "aesr_hip_reslice_taps.h": ("test_gpu_reslice_taps", set(),
+                                ("test_taps_guard_bands_poisons_and_offset_pointers", "test_prefilter_guard_bands_poisons_and_offset_pointers"), ()),
 }
 MAIN_HOST_SUFFIXES = ("_supported", "_floats", "_bytes", "_words", "_doubles", "_kernel", "_timeouts")
 MAIN_HOST_NAMES = ("aesr_version", "aesr_last_error_string", "aesr_adam_state_init")

@@ -1,5 +1,5 @@
 """-m gpu: affine reslicing with a cubic B-spline or a windowed sinc on the device -- aesr_bspline_prefilter_3d and aesr_reslice_taps_affine
-(csrc/reslice_taps.hip, csrc/reslice_taps.h), ``evaluate.reslice`` and the command line of ``evaluate.cardiac.resample_sax_to_lax``.
+(csrc/reslice_taps.hip, csrc/bspline_prefilter.hip, include/aesr_hip_reslice_taps.h), ``evaluate.reslice`` and the command line of ``evaluate.cardiac.resample_sax_to_lax``.
 
 - Every case of tests/golden/reslice_taps.npz and every kernel against the fixture (scipy for ``bspline``, the closed form for the sincs) and
   against the float64 restatement of tests/test_reslice_taps_golden.py: 1e-6 absolute, the bound of the sibling kernels for fp32 results on
@@ -7,7 +7,8 @@
 - Exact: the identity and the integer flip with a sinc reproduce the input; N frames equal their single-frame calls; ``clamp01`` equals
   ``torch.clamp`` (with voxels that it changes); a device tensor in gives a device tensor out and the input is unchanged.
 - Cross-checks: ``diag(1, 1, 1 / f)`` with a sinc against ``z_expand(align="grid", method="lanczos")``; ``bspline`` at the identity.
-- The pre-filter at line lengths around the staged block (32 columns), the workgroup's rows (64) and one, against ``spline_filter1d`` thrice.
+- The pre-filter at line lengths around the staged block (32 columns), the workgroup's rows (64) and one, against ``spline_filter1d`` thrice;
+  its y pass bit for bit against ``aesr_bspline_prefilter_z`` on the same lines (one recursion, csrc/bspline_prefilter.h).
 - Both launch entry points between the guard bands of tests/memguard.py: NaN and 3e38 poisons, pointers shifted by 4, 8 and 12 bytes
   (``coef`` by 8), output widths 47, 48, 131, 132; refusals write nothing.
 - The command line on small NIfTI files."""
@@ -22,6 +23,9 @@ import memguard as mg
 import test_reslice_taps_golden as tt
 
 pytestmark = pytest.mark.gpu
+# GUARDED_ENTRIES and EXEMPT partition ``_hip.SIGNATURES_RESLICE_TAPS`` (tests/test_abi.py checks that without a GPU)
+GUARDED_ENTRIES = ("aesr_reslice_taps_affine", "aesr_bspline_prefilter_3d")
+EXEMPT = {}
 
 TOL, TOL_COEF = tt.TOL, tt.TOL_COEF
 KERNELS = (("bspline", 5),) + tt.SINCS          # (interp, radius): what the fixture stores
@@ -175,6 +179,20 @@ def test_prefilter_shapes_vs_spline_filter1d_thrice(shape):
     print("%s: max |kernel - spline_filter1d x 3| = %.3g (bound %.3g)" % (shape, err, TOL_COEF))
     assert got.shape == want.shape and err <= TOL_COEF, (shape, err)
     mg.assert_unchanged(x, saved, "in")
+
+
+@pytest.mark.parametrize("H", (2, 3, 5, 67))
+def test_the_y_pass_is_the_z_recursion_bit_for_bit(H):
+    """On [N, 1, H, 1] only the y pass of aesr_bspline_prefilter_3d acts (z copies, x is skipped): its coefficients equal those of
+    aesr_bspline_prefilter_z on the same data seen as [N, H, 1, 1], in every bit."""
+    from superresolution_aniso_mri_amd import _hip as hip
+    N = 2
+    x = torch.from_numpy((np.random.RandomState(100 + H).randint(0, 1025, size=(N, H)) / tt.Q).astype(np.float32)).cuda()
+    got, want = torch.full((N, H), float("nan"), dtype=torch.float64, device="cuda"), torch.full((N, H), float("nan"), dtype=torch.float64, device="cuda")
+    hip.check(hip.lib.aesr_bspline_prefilter_3d(hip.ptr(x), hip.ptr(got), N, 1, H, 1, hip.stream()), "aesr_bspline_prefilter_3d")
+    hip.check(hip.lib.aesr_bspline_prefilter_z(hip.ptr(x), hip.ptr(want), N, H, 1, 1, hip.stream()), "aesr_bspline_prefilter_z")
+    torch.cuda.synchronize()
+    assert not torch.isnan(want).any() and torch.equal(got.view(torch.int64), want.view(torch.int64)), H
 
 
 # ---- the launch entry points between guard bands --------------------------------------------------------------------------------------

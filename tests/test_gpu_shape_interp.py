@@ -20,6 +20,12 @@ import test_shape_interp_golden as tm
 
 pytestmark = pytest.mark.gpu
 CASES = tm.CASES
+# GUARDED_ENTRIES and EXEMPT partition ``_hip.SIGNATURES_SHAPE`` (tests/test_abi.py checks that without a GPU)
+GUARDED_ENTRIES = {
+    "aesr_shape_signed_distances": "test_guard_bands_poisons_and_shifted_pointers",
+    "aesr_shape_interpolate": "test_guard_bands_poisons_and_shifted_pointers",
+}
+EXEMPT = {"aesr_shape_workspace_bytes": "a size query on the host: it is given no buffer"}
 _DEVICE = {}
 
 

@@ -1,4 +1,4 @@
-"""No GPU: shape-based interpolation of label maps (csrc/shape_interp.h) restated in numpy by brute force, against the fixture that
+"""No GPU: shape-based interpolation of label maps (include/aesr_hip_shape.h) restated in numpy by brute force, against the fixture that
 tests/make_golden_shape_interp.py wrote with scipy (tests/golden/shape_interp.npz); and the parts of the host layer that need no device.
 
 The restatement is the definition itself, with the device's expression and order: per class, slice and pixel the minimum over the pixels
@@ -296,29 +296,9 @@ def test_argument_parsing_of_both_tools(capsys):
     assert table.count("\n") == 7 and "nearest" in table and "shape" in table and "hd95" in table and "0.7500" in table
 
 
-# ---- the binding ----------------------------------------------------------------------------------------------------------------------
-def test_the_three_symbols_are_bound_as_their_prototypes_and_are_not_public_abi():
+# ---- the size query ------------------------------------------------------------------------------------------------------------------
+def test_the_workspace_query_is_host_code():
     from superresolution_aniso_mri_amd import _hip
-    header = os.path.join(ROOT, "superresolution_aniso_mri_amd", "csrc", "shape_interp.h")
-    table, protos = _hip.SHAPE_INTERP_ENTRIES, au.prototypes(header)
-    assert set(protos) == set(table) == {"aesr_shape_workspace_bytes", "aesr_shape_signed_distances", "aesr_shape_interpolate"}
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    for name, (ret, params) in protos.items():
-        res, args = table[name]
-        assert au.RETURNS[ret] is res, (name, ret, res)
-        assert len(args) == len(params), name
-        for i, ((ctype, pname), bound) in enumerate(zip(params, args)):
-            assert au.compatible(ctype, bound, _hip), "%s: argument %d, %s %s, is bound as %s" % (name, i, ctype, pname, bound)
-        assert getattr(lib, name, None) is not None, "%s is not exported" % name
-        assert getattr(_hip.lib, name).restype == res and getattr(_hip.lib, name).argtypes == args, name
-    # not yet public: in no table of HEADERS, declared by no header under include/, and the table's name keeps it out of the ABI test's sweep
-    for h, t in _hip.HEADERS.items():
-        assert not set(table) & set(t) and not set(table) & au.declared(h), h
-    assert not any(t is table for t in _hip.HEADERS.values())
-    assert not [k for k, v in vars(_hip).items() if v is table and k.startswith("SIGNATURES")]
-    defs = au.defines(header)
-    assert (_hip.SHAPE_MAX_CLASSES, _hip.SHAPE_MAX_W) == (defs["AESR_SHAPE_MAX_CLASSES"], defs["AESR_SHAPE_MAX_W"])
-    # the size query is host code
     q = _hip.lib.aesr_shape_workspace_bytes
     assert q(1, 2, 3, 4, 2) == 384 and q(2, 7, 5, 6, 8) % 16 == 0 and q(2, 7, 5, 6, 8) >= 2 * 8 * 2 * 7 * 30 * 4
     assert q(0, 2, 3, 4, 2) == 0 and q(1, 2, 3, 4, 9) == 0 and q(1, 2, 3, 4097, 2) == 0 and q(1 << 10, 1 << 10, 1 << 10, 2, 1) == 0
